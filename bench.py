@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json configs[1]: one Mamba-2 block (OmniMamba-1.3B shape), forward + backward,
 B=8 L=4096 d_model=2048 d_state=128, bf16 autocast over fp32 parameters, synthetic data, on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE
 in the environment) or started plainly, in which case it re-executes itself under torch.distributed.run on 127.0.0.1.
@@ -24,6 +24,11 @@ is reported separately under `sustained`.
                             to the CPU selective_scan_ref restatement on the host cores
   scan_target               the north-star target shape: the scan alone at L = 8192, d_model 2048, B = 8 and B = 1
   decode_1p3b               BASELINE configs[2]: 1.3B T2I greedy decode, 72-token prompt + 256 tokens: time to first token, ms/token
+
+--dump-outputs DIR writes, on rank 0, what the LAST of the K timed steps handed its caller: DIR/y.npy (the block output),
+DIR/du.npy (the input gradient) and DIR/grad.<parameter>.npy, all float32.  Weights and inputs are seeded, so two builds run with
+the same arguments can be compared output for output.  An array of more than DUMP_SAMPLE elements is cut to DUMP_SAMPLE flat
+positions drawn from a generator seeded with 0 (the same positions on every run; 1-D), the rest keep their shapes: ~17 MB in all.
 """
 import argparse
 import json
@@ -44,6 +49,20 @@ D_SCAN = H * HEADDIM
 HBM_PEAK_GBS = 8000.0                  # MI355X_MICROARCH.md: 8 TB/s spec
 SCAN_FWD_BYTES_PER_TOK = 2 * D_SCAN * 2 + 2 * D_STATE * 2 + H * 2      # x in, y out, B, C, dt   = 17,024 B
 SCAN_BWD_BYTES_PER_TOK = 3 * D_SCAN * 2 + 4 * D_STATE * 2 + 2 * H * 2  # x, dy in, dx out, B, C, dB, dC, dt, ddt = 25,856 B
+DUMP_SAMPLE = 1 << 20                  # --dump-outputs: elements kept of a larger array (y, du, in_proj / out_proj gradients: 4 x 4 MB)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32; one of more than DUMP_SAMPLE elements as the DUMP_SAMPLE flat positions a
+    generator seeded with 0 draws for its size (arrays of one size share the positions)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(seconds_budget=20.0):
@@ -438,7 +457,11 @@ def main():
     ap.add_argument("--dry-launch", action="store_true", help="only initialise the process group and report ranks (CPU test of the launch path)")
     ap.add_argument("--force-dist", action="store_true", help="take the multi-rank path (launcher, process group, DDP, barriers, max over ranks) even with --gpus 1: "
                                                               "runs the exact code of the N > 1 scaling runs on RCCL where only one GPU exists")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32; "
+                                                                          "large arrays as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -500,22 +523,26 @@ def main():
     u = torch.randn(B_LOCAL, SEQ, D_MODEL, device=dev, dtype=torch.bfloat16)
     dy = torch.randn(B_LOCAL, SEQ, D_MODEL, device=dev, dtype=torch.bfloat16)
 
-    def step():
+    last = {}                                  # what the last step of timed(n, keep_last=True) returned to its caller (--dump-outputs)
+
+    def step(keep=False):
         ur = u.detach().requires_grad_()
         with torch.autocast("cuda", dtype=torch.bfloat16):
             y = model(ur)
         y.backward(dy)
+        if keep:
+            last.update(y=y, du=ur.grad, **{"grad." + n: p.grad for n, p in block.named_parameters()})
         for p in block.parameters():
             p.grad = None
 
-    def timed(n):
+    def timed(n, keep_last=False):
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(n):
-            step()
+        for i in range(n):
+            step(keep_last and i == n - 1)
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -533,7 +560,10 @@ def main():
     nsteps = args.steps
     _prof.ENABLED = True
     _prof.reset()
-    elapsed = timed(nsteps)
+    elapsed = timed(nsteps, keep_last=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    last.clear()
     ms_per_step = elapsed / nsteps * 1e3
     value = world * B_LOCAL * SEQ * D_SCAN / (elapsed / nsteps) / 1e6
     # ---- a sustained region behind it (same step, >= --min-seconds): the driver's utilisation sampler has a 5 s period, K = 20

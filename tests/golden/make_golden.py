@@ -15,6 +15,9 @@ own Python from /root/reference, which never travels to the GPU box):
   vq_tail_reference.npz  the reference's UNMODIFIED llamagen_tokenizer/tokenizer_image/vq_model.py classes (VectorQuantizer, Decoder at
                        a small width, a 1x1 post_quant_conv) composed the way VQModel.decode_code composes them: state dict, sampled
                        ids, the codebook entries and the decoded image -- pins omnimamba_amd.vq_tail.VQDecodeTail
+  reference_block.npz  the reference's UNMODIFIED models/stage2/block.py::Block (fused add + RMSNorm, fp32 residual) on the
+                       oracle-backed provider, with a Mamba2 mixer alone and with a second add + norm and a GatedMLP: state dicts,
+                       inputs, (hidden, residual) outputs, and a bf16-autocast first-block call -- pins tests/test_reference_dropin.py
 """
 import importlib.util
 import os
@@ -182,6 +185,55 @@ def reference_model():
     print("state dict keys:", [k[3:] for k in out if k.startswith("sd.")])
 
 
+def block_reference():
+    """The reference's UNMODIFIED models/stage2/block.py::Block built the way create_block builds it (fused add + RMSNorm, fp32
+    residual) on the oracle-backed provider: a Mamba2 mixer alone, and the same with a second add + norm and a GatedMLP
+    (d_intermediate > 0: no shipped config, mixer_seq_simple.py:168-230).  The provider has no GatedMLP (the shipped configs never
+    build one), so the published module is restated here on plain PyTorch."""
+    from functools import partial
+    import torch.nn.functional as F
+    import oracle.provider as P
+    P.install()
+    spec = importlib.util.spec_from_file_location("ref_block", "/root/reference/models/stage2/block.py")
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+
+    class GatedMLP(torch.nn.Module):
+        def __init__(self, d, hidden_features, out_features, multiple_of):
+            super().__init__()
+            hidden = (hidden_features + multiple_of - 1) // multiple_of * multiple_of
+            self.fc1 = torch.nn.Linear(d, 2 * hidden, bias=False)
+            self.fc2 = torch.nn.Linear(hidden, out_features, bias=False)
+
+        def forward(self, x, task_types=None):
+            y, gate = self.fc1(x).chunk(2, dim=-1)
+            return self.fc2(y * F.silu(gate))
+
+    mixer = partial(P.Mamba2, layer_idx=0, d_state=16, headdim=8, chunk_size=16)
+    norm = partial(P.RMSNorm, eps=1e-5)
+    out = {}
+    for key, seed, mlp in (("mixer", 0, torch.nn.Identity), ("mlp", 1, partial(GatedMLP, hidden_features=40, out_features=32, multiple_of=16))):
+        torch.manual_seed(seed)
+        blk = ref.Block(32, mixer, mlp, norm_cls=norm, fused_add_norm=True, residual_in_fp32=True)
+        with torch.no_grad():
+            for n, p in blk.named_parameters():
+                if "norm" in n:
+                    p.mul_(1.0 + 0.2 * torch.randn_like(p))     # RMSNorm weights start at 1: make a wrong norm weight visible
+        h, res = torch.randn(2, 9, 32), torch.randn(2, 9, 32)
+        with torch.no_grad():
+            y, r = blk(h, res)
+            out.update({f"{key}.h": h.numpy(), f"{key}.res": res.numpy(), f"{key}.y": y.numpy(), f"{key}.r": r.numpy()})
+            if key == "mixer":
+                with torch.autocast("cpu", dtype=torch.bfloat16):      # training runs under bf16 AMP (train_stage2.py:21,37)
+                    ya, ra = blk(h.bfloat16(), None)                # first block: residual None, bf16 activations, fp32 residual out
+                assert ya.dtype == torch.bfloat16 and ra.dtype == torch.float32
+                out.update({"mixer.amp_y": ya.float().numpy(), "mixer.amp_r": ra.numpy()})
+        for k, v in blk.state_dict().items():
+            out[f"{key}.sd.{k}"] = v.numpy()
+    np.savez_compressed(os.path.join(HERE, "reference_block.npz"), **out)
+    print("reference_block.npz:", {k: v.shape for k, v in out.items() if ".sd." not in k})
+
+
 def vq_tail_reference():
     spec = importlib.util.spec_from_file_location("ref_vq_model", "/root/reference/llamagen_tokenizer/tokenizer_image/vq_model.py")
     mod = importlib.util.module_from_spec(spec)
@@ -224,9 +276,11 @@ def vq_tail_reference():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["lora", "ops", "model", "vq"]
+    which = sys.argv[1:] or ["lora", "ops", "model", "vq", "block"]
     if "vq" in which:
         vq_tail_reference()
+    if "block" in which:
+        block_reference()
     if "lora" in which:
         lora_reference()
     if "ops" in which:

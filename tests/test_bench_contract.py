@@ -58,6 +58,36 @@ def test_bench_times_exactly_k_steps_and_reports_the_sustained_region_separately
     assert j["roofline"]["launches_timed"] == 3 + su["steps"]        # the scan launches are HIP-event timed over both regions
 
 
+@pytest.mark.gpu
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the block output, the input gradient and every parameter gradient of the last timed step as float32 .npy
+    files, 64 MB at most.  The inputs are seeded and do not depend on --steps / --warmup: two runs that differ only there dump the
+    same numbers (up to the summation order of fp32 atomics)."""
+    import numpy as np
+    dumps = []
+    for steps, warmup in ((2, 1), (3, 0)):
+        d = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--min-seconds", "0",
+                            "--no-cpu-baseline", "--no-train-1p3b", "--no-selscan-cfg1", "--no-scan-target", "--no-decode", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][0])["steps"] == steps
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert sum((d / f).stat().st_size for f in os.listdir(d)) <= 64 * 2 ** 20
+    names = {"y", "du"} | {"grad." + n for n in ("in_proj.weight", "conv1d.weight", "conv1d.bias", "dt_bias", "A_log", "D", "norm.weight",
+                                                 "out_proj.weight")}
+    assert set(dumps[0]) == names and set(dumps[1]) == names
+    for k in sorted(names):
+        a, b = dumps[0][k], dumps[1][k]
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all() and np.abs(a).max() > 0, k
+        assert np.linalg.norm(a.astype(np.float64) - b) <= 1e-4 * np.linalg.norm(a.astype(np.float64)), k
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_launches_itself_for_n_gpus(n):
     """The driver runs `python bench.py --gpus N` WITHOUT a launcher: bench.py must re-execute itself under
