@@ -349,3 +349,214 @@ def test_device_loop_sampled_decode_is_reproducible_and_in_range(lm_1p3b):
     assert not torch.equal(c, c2)      # successive calls are independent draws, as with the reference's torch.multinomial
     assert int(a[:, Pn:].min()) >= 0 and int(a[:, Pn:].max()) < model.cfg.vqvae_vocab_size
     assert torch.equal(f1, f2) and not torch.equal(f1, g) and int(f1[:, Pn:].min()) >= 0 and int(f1[:, Pn:].max()) < model.cfg.vqvae_vocab_size
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Production-shape backward parity of the non-scan ops (1.3B geometry: B 8, L 4096, d_model 2048, d_ssm 4096, xBC 4352, zxbcdt 8512),
+# bounds of tolerances.op_bound: fp64 references from exactly the tensors each kernel reads, computed on the device in row chunks.
+# ---------------------------------------------------------------------------------------------------------------------------------
+from tolerances import OP_ARITH, op_bound  # noqa: E402
+
+
+class _Err:
+    """Relative L2 error, and the op_bound quantisation term, accumulated over row chunks of one output."""
+
+    def __init__(self, dtype):
+        self.dtype, self.d2, self.r2, self.q2 = dtype, 0.0, 0.0, 0.0
+
+    def add(self, got, ref):
+        ref = ref.double()
+        self.d2 += (got.double() - ref).pow(2).sum().item()
+        self.r2 += ref.pow(2).sum().item()
+        if self.dtype not in (torch.float32, torch.float64):
+            self.q2 += (ref.to(self.dtype).double() - ref).pow(2).sum().item()
+
+    def result(self):
+        r2 = max(self.r2, 1e-300)
+        e, q = math.sqrt(self.d2 / r2), math.sqrt(self.q2 / r2)
+        return e, 1.1 * math.sqrt(q * q + OP_ARITH * OP_ARITH)
+
+
+def _assert_table(name, errs, extra=()):
+    """errs: {output: (error, bound)}; writes the table first, so that a failing run still leaves every number."""
+    lines = [f"{'output':28s} {'rel-L2 error':>12s} {'bound':>10s}"] + [f"{k:28s} {e:12.3e} {b:10.3e}" for k, (e, b) in errs.items()]
+    _write_parity_table(name, lines + list(extra))
+    bad = {k: v for k, v in errs.items() if not v[0] <= v[1]}
+    assert not bad, bad
+
+
+def test_prod_conv1d_bwd_on_the_xbc_view():
+    """causal_conv1d backward on the xBC view of zxbcdt (B 8, L 4096, C 4352, W 4, channel-last): conv1d_bwd_cl4_kernel over 34 channel
+    blocks and the fold of B x 16 partial rows.  dx on sampled channel slices (channels are independent), dw / db over all 8 batch
+    elements for those channels, against fp64."""
+    from omnimamba_amd.causal_conv1d import causal_conv1d_fn
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(21)
+    zx = torch.randn(8, 4096, 8512, generator=g).bfloat16()
+    w, bias = torch.randn(4352, 4, generator=g) * 0.5, torch.randn(4352, generator=g) * 0.1
+    gout = torch.randn(8, 4096, 4352, generator=g).bfloat16()
+    zxd = zx.clone().to(dev).requires_grad_()
+    wr, br = w.clone().to(dev).requires_grad_(), bias.clone().to(dev).requires_grad_()
+    out = causal_conv1d_fn(zxd[..., 4096:4096 + 4352].transpose(1, 2), wr, br, activation="silu")
+    out.backward(gout.to(dev).transpose(1, 2))
+    torch.cuda.synchronize()
+    dzx, dw, db = zxd.grad, wr.grad.cpu(), br.grad.cpu()
+    assert float(dzx[..., :4096].abs().max()) == 0.0 and float(dzx[..., 4096 + 4352:].abs().max()) == 0.0   # z and dt untouched
+    chans = torch.cat([torch.arange(0, 64), torch.arange(2100, 2164), torch.arange(4096, 4352)])   # x, the middle, B and C
+    errs = {k: _Err(dt_) for k, dt_ in (("out", torch.bfloat16), ("dx", torch.bfloat16), ("dweight", torch.float32), ("dbias", torch.float32))}
+    xs = zx[..., 4096 + chans].transpose(1, 2).double().requires_grad_()
+    ws, bs = w[chans].double().requires_grad_(), bias[chans].double().requires_grad_()
+    od = O.causal_conv1d_ref(xs, ws, bs, activation="silu", compute_dtype=torch.float64)
+    od.backward(gout[..., chans].transpose(1, 2).double())
+    errs["out"].add(out.detach()[:, chans].cpu(), od.detach())
+    errs["dx"].add(dzx[..., 4096 + chans].transpose(1, 2).cpu(), xs.grad)
+    errs["dweight"].add(dw[chans], ws.grad)
+    errs["dbias"].add(db[chans], bs.grad)
+    _assert_table("prod_conv1d_bwd.txt", {k: v.result() for k, v in errs.items()}, [f"channels: {len(chans)} of 4352, all 8 x 4096 tokens"])
+
+
+@pytest.mark.parametrize("rows", [32768, 32768 + 3])
+def test_prod_gated_norm_bwd_w8(rows):
+    """The 4096-wide gated RMSNorm (one group, bf16, gate after the norm): forward lean kernel and norm_gated_bwd_w8_kernel at the
+    production row count (every one of 512 workgroups walks 64 rows; + 3: a ragged last round) and its 512-row fold.  dx, dz of every
+    row and dw over all rows against fp64."""
+    from omnimamba_amd.layernorm_gated import rmsnorm_fn
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(22)
+    x = torch.randn(rows, 4096, generator=g, device=dev).bfloat16()
+    z = torch.randn(rows, 4096, generator=g, device=dev).bfloat16()
+    w = torch.randn(4096, generator=g, device=dev)
+    gy = torch.randn(rows, 4096, generator=g, device=dev).bfloat16()
+    xr, zr, wr = x.clone().requires_grad_(), z.clone().requires_grad_(), w.clone().requires_grad_()
+    y = rmsnorm_fn(xr, wr, None, z=zr, eps=1e-5, group_size=None, norm_before_gate=False)
+    y.backward(gy)
+    torch.cuda.synchronize()
+    errs = {k: _Err(torch.bfloat16 if k != "dweight" else torch.float32) for k in ("y", "dx", "dz", "dweight")}
+    wd = w.double().requires_grad_()
+    for r0 in range(0, rows, 4096):
+        s = slice(r0, min(rows, r0 + 4096))
+        xd, zd = x[s].double().requires_grad_(), z[s].double().requires_grad_()
+        yd = O.rmsnorm_gated_ref(xd, wd, None, z=zd, eps=1e-5, group_size=None, norm_before_gate=False, compute_dtype=torch.float64)
+        yd.backward(gy[s].double())
+        errs["y"].add(y[s].detach(), yd.detach())
+        errs["dx"].add(xr.grad[s], xd.grad)
+        errs["dz"].add(zr.grad[s], zd.grad)
+    errs["dweight"].add(wr.grad, wd.grad)
+    _assert_table(f"prod_gated_norm_bwd_{rows}.txt", {k: v.result() for k, v in errs.items()})
+
+
+def test_prod_add_norm_fwd_bwd_residual_in_fp32():
+    """add + RMSNorm at 32 768 x 2048 as the model runs it (bf16 x, fp32 residual stream): the {8,1,4} plan, the wvec forward's
+    two-block-row grid (32 768 rows > 2048 workgroups), the backward's 1024 partial rows and their fold.  The backward's reference
+    takes the forward's saved residual_out and rstd."""
+    from omnimamba_amd.layer_norm import layer_norm_fn
+    dev = torch.device("cuda:0")
+    rows, cols = 32768, 2048
+    g = torch.Generator(device=dev).manual_seed(23)
+    x = torch.randn(rows, cols, generator=g, device=dev).bfloat16()
+    res = torch.randn(rows, cols, generator=g, device=dev) * 2
+    w = torch.randn(cols, generator=g, device=dev)
+    gy = torch.randn(rows, cols, generator=g, device=dev).bfloat16()
+    gr = torch.randn(rows, cols, generator=g, device=dev)
+    xr, rr, wr = x.clone().requires_grad_(), res.clone().requires_grad_(), w.clone().requires_grad_()
+    y, ro = layer_norm_fn(xr, wr, None, residual=rr, eps=1e-5, prenorm=True, residual_in_fp32=True, is_rms_norm=True)
+    xsum, _, _, _, rstd = y.grad_fn.saved_tensors
+    torch.autograd.backward([y, ro], [gy, gr])
+    torch.cuda.synchronize()
+    errs = {k: _Err(dt_) for k, dt_ in (("y", torch.bfloat16), ("residual_out", torch.float32), ("rstd", torch.float32),
+                                        ("dx", torch.bfloat16), ("dresidual", torch.float32), ("dweight", torch.float32),
+                                        ("dx end-to-end", torch.bfloat16))}
+    dw64 = torch.zeros(cols, dtype=torch.float64, device=dev)
+    for r0 in range(0, rows, 4096):
+        s = slice(r0, r0 + 4096)
+        r64 = x[s].double() + res[s].double()
+        rs64 = torch.rsqrt(r64.pow(2).mean(-1, keepdim=True) + 1e-5)
+        errs["y"].add(y[s].detach(), r64 * rs64 * w.double())
+        errs["residual_out"].add(ro[s].detach(), r64)
+        errs["rstd"].add(rstd[s], rs64[:, 0])
+        # backward from its own inputs: saved xsum (fp32 residual_out) and rstd
+        xhat = xsum[s].double() * rstd[s].double()[:, None]
+        wdy = w.double() * gy[s].double()
+        dx64 = (wdy - xhat * (xhat * wdy).mean(-1, keepdim=True)) * rstd[s].double()[:, None] + gr[s].double()
+        errs["dx"].add(xr.grad[s], dx64)
+        errs["dresidual"].add(rr.grad[s], dx64)
+        dw64 += (gy[s].double() * xhat).sum(0)
+        # end to end (the old 1.5e-2 regime): from x and residual alone
+        xh = r64 * rs64
+        errs["dx end-to-end"].add(xr.grad[s], (wdy - xh * (xh * wdy).mean(-1, keepdim=True)) * rs64 + gr[s].double())
+    errs["dweight"].add(wr.grad, dw64)
+    table = {k: v.result() for k, v in errs.items()}
+    table["dx end-to-end"] = (table["dx end-to-end"][0], 1.5e-2)
+    _assert_table("prod_add_norm.txt", table)
+
+
+def test_prod_lora_add_and_up_bwd():
+    """omk_lora_add and omk_lora_up_bwd at the training shape (T 16 384, N 8 512, r 8: 34 column blocks x 15 token chunks, a ragged
+    last chunk): the output, dh and the folded dB against fp64."""
+    from omnimamba_amd import lora_add as LA
+    dev = torch.device("cuda:0")
+    T, N = 16384, 8512
+    g = torch.Generator(device=dev).manual_seed(24)
+    res = torch.randn(T, N, generator=g, device=dev).bfloat16()
+    h = torch.randn(T, 8, generator=g, device=dev).bfloat16()
+    Bw = torch.randn(N, 8, generator=g, device=dev) * 0.1
+    dy = torch.randn(T, N, generator=g, device=dev).bfloat16()
+    out = res.clone()
+    assert LA.applies(out, h, Bw) and LA.up_bwd_applies(dy, h, Bw)
+    LA.lora_add_(out, h, Bw, 2.0)
+    dh, dB = LA.lora_up_bwd(dy, h, Bw)
+    torch.cuda.synchronize()
+    errs = {"lora_add out": _Err(torch.bfloat16), "up_bwd dh": _Err(torch.float32), "up_bwd dB": _Err(torch.float32)}
+    for t0 in range(0, T, 2048):
+        s = slice(t0, t0 + 2048)
+        errs["lora_add out"].add(out[s], res[s].double() + 2.0 * h[s].double() @ Bw.double().t())
+        errs["up_bwd dh"].add(dh[s], dy[s].double() @ Bw.bfloat16().double())   # (lora_b as bf16 MFMA fragments)
+    errs["up_bwd dB"].add(dB, dy.double().t() @ h.double())
+    table = {k: v.result() for k, v in errs.items()}
+    for k in ("up_bwd dh", "up_bwd dB"):                 # test_lora_up_bwd's bound, tighter than op_bound's fp32 allowance
+        table[k] = (table[k][0], min(table[k][1], 1e-5))
+    _assert_table("prod_lora.txt", table)
+
+
+def test_prod_fused_split_conv_scan_backward():
+    """MambaSplitConv1dScanCombinedFn backward with the gated norm at the 1.3B width (B 8, L 4096, H 64, P 64, N 128, G 1, W 4) against
+    autograd through the oracle composition (conv -> scan -> gated norm, fp32, with the pipeline's two bf16 rounding points:
+    conv output and pre-norm y).  The z / xBC / dt slices of d zxbcdt of one batch
+    element of the B 8 call; the parameter gradients (conv weight / bias, A, D, dt_bias, norm weight: sums over the batch) from a call
+    on that element alone.  Wiring errors are O(1): gradients through the scan keep the bounds of
+    test_cfg2_scan_backward_production_shape_vs_oracle (5e-3 / 4e-3)."""
+    import omnimamba_amd.ssd_combined as S
+    dev = torch.device("cuda:0")
+    Bsz, L, H, P, N, G, W = 8, 4096, 64, 64, 128, 1, 4
+    d_ssm, Ct = H * P, H * P + 2 * G * N
+    g = torch.Generator().manual_seed(25)
+    zxbcdt = (torch.randn(Bsz, L, 2 * d_ssm + 2 * G * N + H, generator=g) * 0.8).bfloat16()
+    cw, cb = torch.randn(Ct, W, generator=g) * 0.4, torch.randn(Ct, generator=g) * 0.2
+    dtb, A, D = torch.randn(H, generator=g) * 0.5 - 2.0, -(torch.rand(H, generator=g) * 8 + 0.5), torch.randn(H, generator=g)
+    nw = torch.rand(d_ssm, generator=g) + 0.5
+    gy = torch.randn(Bsz, L, d_ssm, generator=g).bfloat16()
+    b = 3
+
+    def fused(zx, gout):
+        leaves = [t.clone().to(dev).requires_grad_() for t in (zx, cw, cb, dtb, A, D, nw)]
+        out = S.mamba_split_conv1d_scan_combined(leaves[0], leaves[1], leaves[2], leaves[3], leaves[4], leaves[5], 256, rmsnorm_weight=leaves[6],
+                                                 rmsnorm_eps=1e-5, headdim=P, ngroups=G, norm_before_gate=False)
+        out.backward(gout.to(dev))
+        torch.cuda.synchronize()
+        return [t.grad.float().cpu() for t in leaves]
+
+    full = fused(zxbcdt, gy)
+    one = fused(zxbcdt[b:b + 1], gy[b:b + 1])
+    ref = [t.float().requires_grad_() for t in (zxbcdt[b:b + 1], cw, cb, dtb, A, D, nw)]
+    yr = O.mamba_split_conv1d_scan_combined_ref(ref[0], ref[1], ref[2], ref[3], ref[4], ref[5], 256, rmsnorm_weight=ref[6], rmsnorm_eps=1e-5,
+                                                headdim=P, ngroups=G, norm_before_gate=False, round_intermediates=True)
+    yr.backward(gy[b:b + 1].float())
+    dz_ref = ref[0].grad[0]
+    sl = {"d zxbcdt: z": slice(0, d_ssm), "d zxbcdt: xBC": slice(d_ssm, d_ssm + Ct), "d zxbcdt: dt": slice(d_ssm + Ct, None)}
+    table = {}
+    for k, s in sl.items():
+        table[k] = (rel(full[0][b][:, s], dz_ref[:, s]), 4e-3 if k.endswith("dt") else 5e-3)
+        table[k + " (B 1 call)"] = (rel(one[0][0][:, s], dz_ref[:, s]), table[k][1])
+    for i, k in ((1, "conv weight"), (2, "conv bias"), (3, "dt_bias"), (4, "A"), (5, "D"), (6, "norm weight")):
+        table[k] = (rel(one[i], ref[i].grad), 5e-3)
+    _assert_table("prod_fused_split_conv_scan_bwd.txt", table, [f"d zxbcdt of batch element {b} of the B 8 call; parameters from a B 1 call on it"])

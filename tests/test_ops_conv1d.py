@@ -125,3 +125,50 @@ def test_conv1d_update(dev, dtype):
     o = causal_conv1d_update(xsd[:, :, :5], st3, wd, bd, activation=None)
     o0 = O.causal_conv1d_update_ref(xs[:, :, :5], st30, w, b, activation=None)
     assert rel(o, o0) < (1e-5 if dtype == torch.float32 else 6e-3) and torch.equal(st3.float().cpu(), st30.float())
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("W", [2, 3, 4])
+@pytest.mark.parametrize("C", [136, 264])
+def test_conv1d_channel_blocks_and_bwd_folds(dev, monkeypatch, C, W, dtype):
+    """Channel-last 16-bit rows wide enough for several channel blocks of 128 (the grid's ceil(C / 2 / 64)): C 136 / 264 leave a partial
+    last block.  L 300 >= 256 takes conv1d_fwd_cl8_kernel and conv1d_bwd_cl4_kernel (f16_t instantiations for fp16) with two 256-token
+    strips, the second ragged.  dweight / dbias through the partial-row fold (B x ceil(L / 256) rows) and through OMK_CONV_BWD_ATOMICS=1;
+    with and without initial states.  Bounds: tolerances.op_bound against fp64 of the tensors the kernels read."""
+    from omnimamba_amd.causal_conv1d import causal_conv1d_fn
+    from tolerances import op_bound
+    g = torch.Generator().manual_seed(C + W)
+    B, L = 2, 300
+    base = torch.randn(B, L, C + 8, generator=g).to(dtype)
+    x = base[:, :, 8:].transpose(1, 2)
+    xdev = base.to(dev)[:, :, 8:].transpose(1, 2)
+    w, b = torch.randn(C, W, generator=g) * 0.5, torch.randn(C, generator=g)
+    init = torch.randn(B, C, W - 1, generator=g).to(dtype)
+    gout = torch.randn(B, L, C, generator=g).to(dtype).transpose(1, 2)   # channel-last, like x
+
+    def check(got, want, what):
+        e, bnd = rel(got, want), op_bound(want, got.dtype)
+        assert e <= bnd, (what, e, bnd)
+
+    for fold in ("parts", "atomics"):
+        if fold == "atomics":
+            monkeypatch.setenv("OMK_CONV_BWD_ATOMICS", "1")
+        for use_init in (False, True):
+            xr = xdev.detach().requires_grad_()
+            wr, br = w.clone().to(dev).requires_grad_(), b.clone().to(dev).requires_grad_()
+            ir = init.clone().to(dev).requires_grad_() if use_init else None
+            out, fin = causal_conv1d_fn(xr, wr, br, initial_states=ir, return_final_states=True, activation="silu")
+            out.backward(gout.to(dev))
+            xd, wd, bd = x.double().requires_grad_(), w.double().requires_grad_(), b.double().requires_grad_()
+            idd = init.double().requires_grad_() if use_init else None
+            od, fd = O.causal_conv1d_ref(xd, wd, bd, initial_states=idd, return_final_states=True, activation="silu", compute_dtype=torch.float64)
+            od.backward(gout.double())
+            tag = (fold, use_init)
+            check(out.detach(), od.detach(), ("out",) + tag)
+            assert torch.equal(fin.cpu().double(), fd.detach()), tag                      # a copy of the last W - 1 inputs
+            check(xr.grad, xd.grad, ("dx",) + tag)
+            check(wr.grad, wd.grad, ("dw",) + tag)
+            check(br.grad, bd.grad, ("db",) + tag)
+            if use_init:
+                check(ir.grad, idd.grad, ("dinit",) + tag)
+            assert rel(xr.grad, xd.grad) < 1.5e-2 and rel(wr.grad, wd.grad) < 1.5e-2    # today's bounds

@@ -61,3 +61,114 @@ def test_lora_up_bwd(dev, T, N):
     Bq = Bw.bfloat16().double()                      # the kernel holds lora_b as bf16 MFMA fragments
     assert dh.dtype == torch.float32 and rel(dh, dy.double() @ Bq) < 1e-5
     assert db.dtype == torch.float32 and rel(db, dy.double().t() @ h.double()) < 1e-5
+
+
+def _b_view(N, R, kind, dtype, g):
+    """lora_b (N, R) as the kernel may receive it: contiguous (a.bvec: 16-byte requests of the lane's weights) or a view whose rows are
+    not R apart (columns of a wider tensor: a.bvec = 0, per-element loads)."""
+    vals = (torch.randn(N, R, generator=g) * 0.1).to(dtype)
+    if kind == "contiguous":
+        return vals
+    wide = torch.zeros(N, 2 * R, dtype=dtype)
+    wide[:, 3:3 + R] = vals
+    return wide[:, 3:3 + R]
+
+
+@pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float16, torch.float32])
+@pytest.mark.parametrize("b_dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("b_kind", ["contiguous", "strided"])
+def test_lora_add_b_operand_paths(dev, monkeypatch, out_dtype, b_dtype, b_kind):
+    """omk_lora_add for every lora_b form and output dtype the entry accepts: a.bvec (contiguous, aligned B rows) against the per-element
+    loads of a strided view or OMK_LORA_ADD_NOVEC -- the same bits -- and both against fp64 (tolerances.op_bound).  T 70 x N 264: a ragged
+    token block and a partial column block."""
+    from omnimamba_amd import lora_add as LA
+    from tolerances import op_bound
+    g = torch.Generator().manual_seed(7)
+    T, N, R = 70, 264, 8
+    res, h = torch.randn(T, N, generator=g).to(out_dtype), torch.randn(T, R, generator=g).to(out_dtype)
+    Bw = _b_view(N, R, b_kind, b_dtype, g)
+    ref = res.double() + 4.0 * h.double() @ Bw.double().t()
+
+    def run():
+        od = res.clone().to(dev)
+        Bd = Bw.to(dev) if b_kind == "contiguous" else _b_view(N, R, b_kind, b_dtype, torch.Generator().manual_seed(7))
+        if b_kind != "contiguous":   # the same values, as a strided view on the device
+            wide = torch.zeros(N, 2 * R, dtype=b_dtype, device=dev)
+            wide[:, 3:3 + R] = Bw.to(dev)
+            Bd = wide[:, 3:3 + R]
+        assert LA.applies(od, h.to(dev), Bd)
+        return LA.lora_add_(od, h.to(dev), Bd, 4.0).cpu()
+
+    out = run()
+    e, bnd = rel(out, ref), op_bound(ref, out_dtype)
+    assert out.dtype == out_dtype and e <= bnd, (e, bnd)
+    monkeypatch.setenv("OMK_LORA_ADD_NOVEC", "1")
+    assert torch.equal(run(), out)
+
+
+def test_lora_add_fp16_autograd(dev):
+    """fp16 result through the autograd node: forward by the kernel, gradients by the composition."""
+    from omnimamba_amd import lora_add as LA
+    from tolerances import op_bound
+    torch.manual_seed(2)
+    T, N, R = 70, 264, 16
+    res, h, Bw = torch.randn(T, N).half(), torch.randn(T, R).half(), torch.randn(N, R) * 0.1
+    resd = res.clone().to(dev).requires_grad_()
+    hd, Bd = h.clone().to(dev).requires_grad_(), Bw.clone().to(dev).requires_grad_()
+    work = resd * 1.0
+    assert LA.applies(work, hd, Bd)
+    out = LA.lora_add(work, hd, Bd, 4.0)
+    ref = res.double() + 4.0 * h.double() @ Bw.double().t()
+    assert out.dtype == torch.float16 and rel(out, ref) <= op_bound(ref, torch.float16)
+    g = torch.randn(T, N).half()
+    out.backward(g.to(dev))
+    assert rel(resd.grad, g.double()) < 1e-6
+    assert rel(hd.grad, 4.0 * g.double() @ Bw.double()) < 1e-2 and rel(Bd.grad, 4.0 * g.double().t() @ h.double()) < 1e-2
+
+
+@pytest.mark.parametrize("b_dtype,b_kind", [(torch.bfloat16, "contiguous"), (torch.float32, "strided")])
+def test_lora_up_bwd_b_operand_forms(dev, b_dtype, b_kind):
+    """omk_lora_up_bwd reads lora_b in its own dtype and row stride (bf16 MFMA fragments either way): a bf16 lora_b and a strided fp32
+    view give dh, dB within the bounds of test_lora_up_bwd.  fp16 dy is refused (up_bwd_applies) -- lora_ext takes two GEMMs."""
+    from omnimamba_amd import lora_add as LA
+    g = torch.Generator().manual_seed(9)
+    T, N = 1000, 520
+    dy, h = torch.randn(T, N, generator=g).bfloat16(), torch.randn(T, 8, generator=g).bfloat16()
+    Bw = _b_view(N, 8, b_kind, b_dtype, g)
+    if b_kind == "contiguous":
+        Bd = Bw.to(dev)
+    else:
+        wide = torch.zeros(N, 16, dtype=b_dtype, device=dev)
+        wide[:, 3:11] = Bw.to(dev)
+        Bd = wide[:, 3:11]
+    assert LA.up_bwd_applies(dy.to(dev), h.to(dev), Bd)
+    dh, db = LA.lora_up_bwd(dy.to(dev), h.to(dev), Bd)
+    Bq = Bw.bfloat16().double()
+    assert rel(dh, dy.double() @ Bq) < 1e-5 and rel(db, dy.double().t() @ h.double()) < 1e-5
+    assert not LA.up_bwd_applies(dy.half().to(dev), h.half().to(dev), Bd)
+
+
+@pytest.mark.parametrize("adt,rank", [(torch.float16, 8), (torch.bfloat16, 4)])
+def test_lora_ext_backward_when_the_kernels_refuse(dev, adt, rank):
+    """The A-branch backward of lora_ext falls back to the composition where the kernels refuse: fp16 (up_bwd_applies) keeps the masked
+    omk_lora_add for dx; rank 4 (applies and up_bwd_applies both refuse) takes the library GEMMs for everything.  Gradients vs fp64."""
+    import types
+    from omnimamba_amd import lora_add as LA
+    from omnimamba_amd.lora_ext import MIN_TOKENS, lora_ext_linear
+    torch.manual_seed(6)
+    T, in_f, out_f = MIN_TOKENS, 64, 96
+    x, W = torch.randn(T, in_f).to(adt), torch.randn(out_f, in_f) * 0.1
+    A, Bw = torch.randn(rank, in_f) * 0.1, torch.randn(out_f, rank) * 0.1
+    gy = torch.randn(T, out_f).to(adt)
+    xr, Ar, Br = (t.clone().to(dev).requires_grad_() for t in (x, A, Bw))
+    y = lora_ext_linear(types.SimpleNamespace(), xr, W.to(dev), Ar, Br, 2.0, adt, 0.0)
+    h_probe = torch.zeros(T, rank, dtype=adt, device=dev)
+    assert LA.up_bwd_applies(gy.to(dev), h_probe, Br) is False
+    assert LA.applies(torch.zeros(T, in_f, dtype=adt, device=dev), h_probe, Ar.t().contiguous()) == (rank == 8)
+    y.backward(gy.to(dev))
+    xd, Ad, Bd = x.double().requires_grad_(), A.double().requires_grad_(), Bw.double().requires_grad_()
+    yd = xd @ W.double().t() + 2.0 * (xd @ Ad.t()) @ Bd.t()
+    yd.backward(gy.double())
+    assert rel(y.detach().cpu(), yd.detach()) < 1e-2
+    for got, want in ((xr.grad, xd.grad), (Ar.grad, Ad.grad), (Br.grad, Bd.grad)):
+        assert rel(got.cpu(), want) < 1e-2

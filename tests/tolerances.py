@@ -25,7 +25,18 @@ Two more rules live here and nowhere else (round 6):
     operand, and the state that meets C) and ties with it on state-dominated heads: measured 0.94 .. 1.13 x the upstream-rounding
     oracle's own error on heads with A dt0 < 0.01, 0.2 .. 0.6 x elsewhere.  A tie cannot be asserted at 1.05 x of a quantity that
     is itself one draw of a rounding error, so its bound is TRAIN_FACTOR = 1.15 x; callers who need more take KHILO (+ 15 %) or
-    PRECISE (+ 37 %) per call (profiles/r06_precise.txt)."""
+    PRECISE (+ 37 %) per call (profiles/r06_precise.txt).
+
+The rule of the NON-SCAN streaming ops (norms, conv1d, LoRA add; op_bound below).  These kernels keep every intermediate in fp32
+and round once, at the store.  For an output o of dtype T and an fp64 reference r computed from exactly the tensors the kernel
+reads (a backward reference takes the forward's saved tensors -- residual_out, rstd, mean -- as its inputs, so that only the
+backward's own arithmetic is measured):
+
+    rel(o, r)  <=  1.1 * sqrt(q^2 + a^2),    q = rel(r.to(T), r) on the compared slice (0 for fp32 outputs)
+
+with a = OP_ARITH = 1e-4, the allowance of fp32 arithmetic with fast exp / rcp / rsqrt and long fp32 sums.  dw / db of the norms
+and the conv are fp32 sums: q = 0, so a dropped row (1 / sqrt(rows) of rel-L2) or a double-counted partial is far outside the
+bound, where the flat 1.5e-2 of rounds 1 - 6 hid it."""
 import math
 
 import torch
@@ -35,6 +46,7 @@ import oracle as O
 Q_BF16 = 1.65e-3
 ARITH_BUDGET = 1e-3
 TRAIN_FACTOR = 1.15
+OP_ARITH = 1e-4
 
 
 def training_budget(upstream_arith):
@@ -71,3 +83,10 @@ def direct_bound(own_arith_budget, upstream_arith, q=0.0):
     reference pipeline's own error is small (u << 1e-3) this IS the north-star 1e-3; where u ~ 1.7e-3 no kernel that does not
     reproduce upstream's rounding errors bit for bit can be closer to it than u."""
     return math.sqrt(q * q + 1.21 * (own_arith_budget ** 2 + upstream_arith ** 2))
+
+
+def op_bound(ref, dtype, arith=OP_ARITH):
+    """Bound of a non-scan op's output of dtype `dtype` against its fp64 reference `ref` (module docstring): one rounding of the
+    exact answer to `dtype`, measured on this slice, plus the fp32 arithmetic allowance, with 10 % slack."""
+    q = 0.0 if dtype in (torch.float32, torch.float64) else rel(ref.to(dtype), ref)
+    return 1.1 * math.sqrt(q * q + arith * arith)
