@@ -307,7 +307,7 @@ typedef struct {
   int32_t chunk_size;       /* API parity only: the result does not depend on it */
   int32_t force_generic;    /* 1 = use the shape-generic fp32 VALU kernel even when the MFMA kernel applies */
   int32_t flags;            /* ABI 6: OMK_SSD_* bits below, 0 = the default kernels.  Per call -- the library reads no environment
-                             * variable that changes which scan kernel runs or what it computes */
+                             * variable but the test hooks of INTEGRATION.md section 4, which only lower size thresholds */
   OmkTensor conv_weight;    /* ABI 6, optional (H * P, width <= 4): K2 fusion of the forward-only path (prefill / inference).  When present,
                              * x is the PRE-conv input of upstream's causal_conv1d_fn(..., activation="silu") for the x channels of xBC, and
                              * the scan applies out[t] = silu(bias + sum_k w[k] x[t - width + 1 + k]) (zeros in front of the sequence) while

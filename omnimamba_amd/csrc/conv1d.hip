@@ -864,40 +864,29 @@ extern "C" int omk_causal_conv1d_fwd(const OmkConv1dFwd* p, omk_stream stream) {
       if (a.W == 4) OMK_LAUNCH((conv1d_fwd_cl_kernel<T_, VEC_, TL_, 4, TG_>), grid, block, 0, stream, a); \
       else if (a.W == 3) OMK_LAUNCH((conv1d_fwd_cl_kernel<T_, VEC_, TL_, 3, TG_>), grid, block, 0, stream, a); \
       else OMK_LAUNCH((conv1d_fwd_cl_kernel<T_, VEC_, TL_, 2, TG_>), grid, block, 0, stream, a); } while (0)
-    const char* tle = getenv("OMK_CONV_FWD_TL");   // developer A/B of the tokens per thread (bf16)
-    const int tl = (tle && *tle) ? atoi(tle) : (a.L >= 1024 ? 64 : 32);   // 64: -4 % on the 1.3B slice (halo rows), 128: worse again
-    const bool cl8 = !(getenv("OMK_CONV_FWD_CL8") && getenv("OMK_CONV_FWD_CL8")[0] == '0');
+    const int tl = a.L >= 1024 ? 64 : 32;   // 64: -4 % on the 1.3B slice (halo rows), 128: worse again
     const int64_t farf = (int64_t)a.L * 2 * (a.xsl > a.osl ? a.xsl : a.osl);
-    const char* vce = getenv("OMK_CONV_FWD_VEC");   // developer A/B: "8" = 16 bytes per lane, 4 tokens in flight
-    if (p->x.dtype == OMK_BF16 && vce && vce[0] == '8' && a.C % 8 == 0) {
-      if (vce[1] == '8') CONV_FWD_V(bf16_t, 8, 64, 8); else if (vce[1] == '2') CONV_FWD_V(bf16_t, 8, 32, 4); else CONV_FWD_V(bf16_t, 8, 64, 4);
-    } else
-    if (cl8 && !(tle && *tle) && !(vce && *vce) && (p->x.dtype == OMK_BF16 || p->x.dtype == OMK_F16) && a.L >= 256 && a.C % 4 == 0 && farf < ((int64_t)1 << 31) &&
+    if ((p->x.dtype == OMK_BF16 || p->x.dtype == OMK_F16) && a.L >= 256 && a.C % 4 == 0 && farf < ((int64_t)1 << 31) &&
         a.xsc == 1 && a.osc == 1) {
-      // scalar token positions (conv1d_fwd_cl8_kernel); OMK_CONV_FWD_CL8=0: the per-thread tiles of rounds 1 - 4
+      // scalar token positions (conv1d_fwd_cl8_kernel); the per-thread tiles of rounds 1 - 4 below take the other layouts
       // strips of 16 tokens: the shorter a wave lives the better these streams run (tools/probe/conv_probe.hip: 128 / 64 / 32 / 16 tokens
       // per strip = 4.73 / 5.06 / 5.17 / 5.45 TB/s, three halo rows per strip included) -- once the prologue is a handful of 16-byte
       // requests (WF); the general prologue keeps 64
-      const char* wfe = getenv("OMK_CONV_CL8_WF");   // developer A/B: "0" = the general prologue
-      const bool wf = !(wfe && *wfe == '0') && p->weight.dtype == OMK_F32 && a.wsk == 1 && a.wsc == a.W && ((uintptr_t)p->weight.data & 15) == 0 &&
+      const bool wf = p->weight.dtype == OMK_F32 && a.wsk == 1 && a.wsc == a.W && ((uintptr_t)p->weight.data & 15) == 0 &&
                       (!present(p->bias) || (p->bias.dtype == OMK_F32 && ((uintptr_t)p->bias.data & 15) == 0));
-      int tlf = wf ? 16 : 64;
-      if (const char* e = getenv("OMK_CONV_CL8_TL")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64) tlf = v; }   // developer A/B
+      const int tlf = wf ? 16 : 64;
       const int CVB = (a.C / 4 + 63) / 64, NT4 = (a.L + 4 * tlf - 1) / (4 * tlf);
       dim3 grid((unsigned)((int64_t)a.B * NT4 * CVB)), block(256);
-#define CONV_FWD_8F(T_, TL_, W_) do { if (wf) OMK_LAUNCH((conv1d_fwd_cl8_kernel<T_, TL_, W_, TGF, true>), grid, block, 0, stream, a); \
-        else OMK_LAUNCH((conv1d_fwd_cl8_kernel<T_, TL_, W_, TGF, false>), grid, block, 0, stream, a); } while (0)
-#define CONV_FWD_8W(T_, TL_) do { if (a.W == 4) CONV_FWD_8F(T_, TL_, 4); else if (a.W == 3) CONV_FWD_8F(T_, TL_, 3); else CONV_FWD_8F(T_, TL_, 2); } while (0)
-#define CONV_FWD_8(T_) do { if (tlf == 64) CONV_FWD_8W(T_, 64); else if (tlf == 32) CONV_FWD_8W(T_, 32); else CONV_FWD_8W(T_, 16); } while (0)
+#define CONV_FWD_8W(T_, TL_, WF_) do { if (a.W == 4) OMK_LAUNCH((conv1d_fwd_cl8_kernel<T_, TL_, 4, TGF, WF_>), grid, block, 0, stream, a); \
+        else if (a.W == 3) OMK_LAUNCH((conv1d_fwd_cl8_kernel<T_, TL_, 3, TGF, WF_>), grid, block, 0, stream, a); \
+        else OMK_LAUNCH((conv1d_fwd_cl8_kernel<T_, TL_, 2, TGF, WF_>), grid, block, 0, stream, a); } while (0)
+#define CONV_FWD_8(T_) do { if (wf) CONV_FWD_8W(T_, 16, true); else CONV_FWD_8W(T_, 64, false); } while (0)
       if (p->x.dtype == OMK_BF16) CONV_FWD_8(bf16_t); else CONV_FWD_8(f16_t);
-#undef CONV_FWD_8F
 #undef CONV_FWD_8W
 #undef CONV_FWD_8
     } else
-    if (p->x.dtype == OMK_BF16) {
-      if (tl == 128) CONV_FWD_V(bf16_t, 4, 128, 8); else if (tl == 64) CONV_FWD_V(bf16_t, 4, 64, 8); else if (tl == 16) CONV_FWD_V(bf16_t, 4, 16, 8);
-      else CONV_FWD_V(bf16_t, 4, 32, 8);
-    } else if (p->x.dtype == OMK_F32) { if (tl == 64) CONV_FWD_V(float, 4, 64, 8); else CONV_FWD_V(float, 4, 32, 8); }
+    if (p->x.dtype == OMK_BF16) { if (tl == 64) CONV_FWD_V(bf16_t, 4, 64, 8); else CONV_FWD_V(bf16_t, 4, 32, 8); }
+    else if (p->x.dtype == OMK_F32) { if (tl == 64) CONV_FWD_V(float, 4, 64, 8); else CONV_FWD_V(float, 4, 32, 8); }
     else CONV_FWD_V(f16_t, 4, 32, 8);
 #undef CONV_FWD_V
   } else {
@@ -945,8 +934,8 @@ extern "C" int omk_causal_conv1d_bwd(const OmkConv1dBwd* p, omk_stream stream) {
   const bool fast = p->x.dtype != OMK_F32 && cl_fast_ok(p->x, a.C) && cl_fast_ok(p->dout, a.C) && cl_fast_ok(p->dx, a.C);
   dim3 block(256);
   if (fast) {
-    // strips of 64 tokens, 8 tokens in flight: 402 -> 373 us per call on the 1.3B slice against 32 / 4 (`OMK_CONV_BWD_VAR`: halo
-    // re-reads of W - 1 rows per strip and twice the loads in flight); 128-token strips gain nothing more
+    // strips of 64 tokens, 8 tokens in flight: 402 -> 373 us per call on the 1.3B slice against 32 / 4 (halo re-reads of W - 1 rows
+    // per strip and twice the loads in flight); 128-token strips gain nothing more
     constexpr int TL = 64;
 #define CONV_BWD_V(T_, VEC_, TG_) do { const int CVB = (a.C / VEC_ + 63) / 64, NT4 = (a.L + 4 * TL - 1) / (4 * TL); \
       dim3 grid((unsigned)((int64_t)a.B * NT4 * CVB)); \
@@ -955,47 +944,28 @@ extern "C" int omk_causal_conv1d_bwd(const OmkConv1dBwd* p, omk_stream stream) {
       else OMK_LAUNCH((conv1d_bwd_cl_kernel<T_, VEC_, TL, 2, TG_>), grid, block, 0, stream, a); } while (0)
     // 2 channels per lane: 86 VGPRs / 5 waves per SIMD; the silu' recompute makes this kernel VALU- and latency-heavy
     // (4 channels: 154 VGPRs, 383 us; 2 channels: ~290 us on the 1.3B shape)
-    const char* var = getenv("OMK_CONV_BWD_VAR");   // developer A/B (bf16, W = 4): "<VEC><TL><TG>" digits, e.g. 2648 = VEC 2, TL 64, TG 8
-    if (var && *var && p->x.dtype == OMK_BF16 && a.W == 4) {
-#define CONV_BWD_X(VEC_, TL_, TG_) do { const int CVB = (a.C / VEC_ + 63) / 64, NT4 = (a.L + 4 * TL_ - 1) / (4 * TL_); \
-        dim3 grid((unsigned)((int64_t)a.B * NT4 * CVB)); \
-        OMK_LAUNCH((conv1d_bwd_cl_kernel<bf16_t, VEC_, TL_, 4, TG_>), grid, block, 0, stream, a); } while (0)
-      const int v = atoi(var);
-      if (v == 2324) CONV_BWD_X(2, 32, 4);
-      else if (v == 2328) CONV_BWD_X(2, 32, 8);
-      else if (v == 2644) CONV_BWD_X(2, 64, 4);
-      else if (v == 2648) CONV_BWD_X(2, 64, 8);
-      else if (v == 21288) CONV_BWD_X(2, 128, 8);
-      else if (v == 4324) CONV_BWD_X(4, 32, 4);
-      else if (v == 4644) CONV_BWD_X(4, 64, 4);
-      else if (v == 1648) CONV_BWD_X(1, 64, 8);
-      else return fail(OMK_EINVAL, "OMK_CONV_BWD_VAR: unknown variant %d", v);
-#undef CONV_BWD_X
-    } else {
-      // the scalar-position kernel (conv1d_bwd_cl4_kernel) when every row offset fits 31 bits (OMK_CONV_BWD_CL4=0: the round-3 kernel)
-      const bool cl4 = !(getenv("OMK_CONV_BWD_CL4") && getenv("OMK_CONV_BWD_CL4")[0] == '0');
-      const int64_t far = (int64_t)a.L * 2 * (a.xsl > a.dosl ? (a.xsl > a.dxsl ? a.xsl : a.dxsl) : (a.dosl > a.dxsl ? a.dosl : a.dxsl));
-      if (cl4 && far < ((int64_t)1 << 31) && a.xsc == 1 && a.dosc == 1 && a.dxsc == 1) {
-        // (measured and not kept, profiles/r06_stream_kernels.txt: 8 / 16 strips per workgroup, 32- and 16-token strips, 8 / 16 tokens requested
-        // per group -- 189 ... 194 us all, 16 waves per workgroup 220 ... 262)
-        const bool wf = p->weight.dtype == OMK_F32 && a.wsk == 1 && a.wsc == a.W && ((uintptr_t)p->weight.data & 15) == 0 &&
-                        (!present(p->bias) || (p->bias.dtype == OMK_F32 && ((uintptr_t)p->bias.data & 7) == 0));
-        const int CVB = (a.C / 2 + 63) / 64, NTS = (a.L + 4 * TL - 1) / (4 * TL);
-        dim3 grid((unsigned)((int64_t)a.B * NTS * CVB)), blk(256);
-        const size_t pbytes = conv_bwd_part_bytes(a.B, a.C, a.L, a.W);
-        a.part = (p->workspace && p->workspace_bytes >= pbytes && !getenv("OMK_CONV_BWD_ATOMICS")) ? (float*)p->workspace : nullptr;
+    // the scalar-position kernel (conv1d_bwd_cl4_kernel) when every row offset fits 31 bits; the round-3 kernel otherwise
+    const int64_t far = (int64_t)a.L * 2 * (a.xsl > a.dosl ? (a.xsl > a.dxsl ? a.xsl : a.dxsl) : (a.dosl > a.dxsl ? a.dosl : a.dxsl));
+    if (far < ((int64_t)1 << 31) && a.xsc == 1 && a.dosc == 1 && a.dxsc == 1) {
+      // (measured and not kept, profiles/r06_stream_kernels.txt: 8 / 16 strips per workgroup, 32- and 16-token strips, 8 / 16 tokens requested
+      // per group -- 189 ... 194 us all, 16 waves per workgroup 220 ... 262)
+      const bool wf = p->weight.dtype == OMK_F32 && a.wsk == 1 && a.wsc == a.W && ((uintptr_t)p->weight.data & 15) == 0 &&
+                      (!present(p->bias) || (p->bias.dtype == OMK_F32 && ((uintptr_t)p->bias.data & 7) == 0));
+      const int CVB = (a.C / 2 + 63) / 64, NTS = (a.L + 4 * TL - 1) / (4 * TL);
+      dim3 grid((unsigned)((int64_t)a.B * NTS * CVB)), blk(256);
+      const size_t pbytes = conv_bwd_part_bytes(a.B, a.C, a.L, a.W);
+      a.part = (p->workspace && p->workspace_bytes >= pbytes) ? (float*)p->workspace : nullptr;   // (none: fp32 atomics into dw / db)
 #define CONV_BWD_4G(T_, W_) do { if (wf) OMK_LAUNCH((conv1d_bwd_cl4_kernel<T_, TL, W_, TGX, 4, true>), grid, blk, 0, stream, a); \
-          else OMK_LAUNCH((conv1d_bwd_cl4_kernel<T_, TL, W_, TGX, 4, false>), grid, blk, 0, stream, a); } while (0)
+        else OMK_LAUNCH((conv1d_bwd_cl4_kernel<T_, TL, W_, TGX, 4, false>), grid, blk, 0, stream, a); } while (0)
 #define CONV_BWD_4(T_) do { if (a.W == 4) CONV_BWD_4G(T_, 4); else if (a.W == 3) CONV_BWD_4G(T_, 3); else CONV_BWD_4G(T_, 2); } while (0)
-        if (p->x.dtype == OMK_BF16) CONV_BWD_4(bf16_t); else CONV_BWD_4(f16_t);
-        if (a.part) {
-          const int64_t ncol = (int64_t)a.C * (a.W + 1);
-          OMK_LAUNCH(conv1d_bwd_fold_kernel, dim3((unsigned)((ncol + 63) / 64)), dim3(1024), 0, stream, a.part, a.B * NTS, a.C, a.W, a.dw, a.db);
-        }
+      if (p->x.dtype == OMK_BF16) CONV_BWD_4(bf16_t); else CONV_BWD_4(f16_t);
+      if (a.part) {
+        const int64_t ncol = (int64_t)a.C * (a.W + 1);
+        OMK_LAUNCH(conv1d_bwd_fold_kernel, dim3((unsigned)((ncol + 63) / 64)), dim3(1024), 0, stream, a.part, a.B * NTS, a.C, a.W, a.dw, a.db);
+      }
 #undef CONV_BWD_4G
 #undef CONV_BWD_4
-      } else if (p->x.dtype == OMK_BF16) CONV_BWD_V(bf16_t, 2, 8); else CONV_BWD_V(f16_t, 2, 8);
-    }
+    } else if (p->x.dtype == OMK_BF16) CONV_BWD_V(bf16_t, 2, 8); else CONV_BWD_V(f16_t, 2, 8);
 #undef CONV_BWD_V
   } else {
     int64_t n = (int64_t)a.B * a.C;

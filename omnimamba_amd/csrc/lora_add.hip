@@ -103,12 +103,12 @@ __global__ __launch_bounds__(256) void lora_add_kernel(LoraAddArgs a) {
 // 4.5 M fp32 atomics of the first version (16 of its 89 us).
 // Both MFMAs are 16x16x32 with the rank in the N dimension (8 of 16 columns used): the kernel is a pure stream over dy.
 // 16 k tokens x 8512: 84 us (round 6: 60 us, see lora_up_plan) + 9 us for the two reductions of the partials, against 112 - 128 us for the two library GEMMs; the
-// load / stage / barrier skeleton alone is 68 us (4.1 TB/s), both MFMA parts together 3 us (OMK_LORA_UP_DBG).
+// load / stage / barrier skeleton alone is 68 us (4.1 TB/s), both MFMA parts together 3 us (measured by ablation, round 6).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int LU_TT = 64, LU_TN = 256, LU_LD = LU_TN + 8;
 struct LoraUpBwdArgs {
   const uint16_t* dy; int64_t dys; const void* B; int64_t bs; int bdt; const uint16_t* h; int64_t hs; float* dh; float* dB;
-  int T, N, R, tchunk, NB, dbg;   // dbg: developer ablation (OMK_LORA_UP_DBG): 1 no dh atomics, 2 no dB MFMAs, 4 no dh MFMAs
+  int T, N, R, tchunk, NB;
 };
 
 __global__ __launch_bounds__(256) void lora_up_bwd_kernel(LoraUpBwdArgs a) {
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void lora_up_bwd_kernel(LoraUpBwdArgs a) {
     // ---- dh: rows 16 w .. 16 w + 15 of the tile
     f32x4 acch = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int ks = 0; ks < ((a.dbg & 4) ? 0 : LU_TN / 32); ks++) {
+    for (int ks = 0; ks < LU_TN / 32; ks++) {
       const s16x8 fa = as_s16x8(ld16(&sY[(16 * w + t16) * LU_LD + 32 * ks + 8 * g16]));
       acch = mfma16x16x32_bf16(fa, bfr[ks], acch);              // D[token 4 g16 + i][r = t16]
     }
@@ -192,12 +192,12 @@ __global__ __launch_bounds__(256) void lora_up_bwd_kernel(LoraUpBwdArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         const int t = t0 + 16 * w + 4 * g16 + i;
-        if (t < te && !(a.dbg & 1)) a.dh[((int64_t)nb * a.T + t) * a.R + t16] = acch[i];
+        if (t < te) a.dh[((int64_t)nb * a.T + t) * a.R + t16] = acch[i];
       }
     }
     // ---- dB: columns 64 w .. 64 w + 63, contraction over the 64 tokens of the tile
 #pragma unroll
-    for (int ks = 0; ks < ((a.dbg & 2) ? 0 : LU_TT / 32); ks++) {
+    for (int ks = 0; ks < LU_TT / 32; ks++) {
       const s16x8 fh = as_s16x8(ld16(&sH[t16 * LU_TT + 32 * ks + 8 * g16]));      // B[k = token 8 g16 + j][r = t16]
 #pragma unroll
       for (int ct = 0; ct < 4; ct++) {
@@ -239,7 +239,7 @@ extern "C" int omk_lora_add(const OmkLoraAdd* p, omk_stream stream) {
     return fail(OMK_EUNSUPPORTED, "lora_add: rank must be 8 or 16 and rows 16-byte aligned (use addmm otherwise)");
   a.out = p->out.data; a.h = p->h.data; a.B = p->lora_b.data; a.os = p->out.stride[0]; a.hs = p->h.stride[0]; a.bs = p->lora_b.stride[0];
   a.bdt = p->lora_b.dtype; a.scale = p->scale;
-  a.bvec = (a.bs == a.R && ((uintptr_t)p->lora_b.data & 15) == 0 && !getenv("OMK_LORA_ADD_NOVEC")) ? 1 : 0;
+  a.bvec = (a.bs == a.R && ((uintptr_t)p->lora_b.data & 15) == 0) ? 1 : 0;
   if (present(p->mask)) {
     OMK_REQUIRE(p->mask.dtype == OMK_U8 && p->mask.ndim == 2 && p->mask.shape[0] == a.T && p->mask.shape[1] == a.N && p->mask.stride[1] == 1,
                 "lora_add: mask must be u8 (T, N) with contiguous rows");
@@ -248,7 +248,6 @@ extern "C" int omk_lora_add(const OmkLoraAdd* p, omk_stream stream) {
   const int nvec = a.N / vec, cvb = (nvec + 255) / 256;
   // few tokens (a 72-token prefill: 18 workgroups of 64 tokens took 19 us): cut the token blocks until the chip has work
   a.tokens_per_block = 32;   // (round 6, behind the 16-byte weight prologue: 128 / 64 / 32 / 16 / 8 tokens = 120 / 112 / 109.5 / 119 / 144 us at 16384 x 8512)
-  if (const char* e = getenv("OMK_LORA_ADD_TPB")) { const int v = atoi(e); if (v == 8 || v == 16 || v == 32 || v == 64 || v == 128) a.tokens_per_block = v; }   // developer A/B
   while (a.tokens_per_block > 8 && (int64_t)cvb * ((a.T + a.tokens_per_block - 1) / a.tokens_per_block) < 256) a.tokens_per_block >>= 1;
   const int tbs = (a.T + a.tokens_per_block - 1) / a.tokens_per_block;
   dim3 grid((unsigned)((int64_t)cvb * tbs)), block(256);
@@ -266,9 +265,7 @@ static void lora_up_plan(int64_t T, int64_t N, int* NB, int* tchunk, int* chunks
   // token chunks: ONE resident round -- 188 registers = two workgroups per CU, so as many workgroups as fit 512 slots and no more (round 6: 748
   // workgroups were 1.46 rounds, the second one half empty: 81.5 us; 510: 63.3, with the B block through LDS 59.8; 1020 / 1530 / 2040: 63 / 69 / 75 --
   // every further workgroup pays a prologue and a partial dB slab), at least four tiles each
-  int target = 512;
-  if (const char* e = getenv("OMK_LORA_UP_WGS")) { const int v = atoi(e); if (v >= 64 && v <= 16384) target = v; }   // developer A/B
-  int c = target / *NB;
+  int c = 512 / *NB;
   const int max_chunks = (int)((T + 4 * LU_TT - 1) / (4 * LU_TT));
   if (c > max_chunks) c = max_chunks;
   if (c < 1) c = 1;
@@ -301,7 +298,6 @@ extern "C" int omk_lora_up_bwd(const OmkLoraUpBwd* p, omk_stream stream) {
     return fail(OMK_EUNSUPPORTED, "lora_up_bwd: bf16 dy / h with 16-byte aligned rows, rank 8, out_features a multiple of 8 (use two GEMMs otherwise)");
   a.dy = (const uint16_t*)p->dy.data; a.dys = p->dy.stride[0]; a.B = p->lora_b.data; a.bs = p->lora_b.stride[0]; a.bdt = p->lora_b.dtype;
   a.h = (const uint16_t*)p->h.data; a.hs = p->h.stride[0]; a.dh = (float*)p->dh.data; a.dB = (float*)p->dlora_b.data;
-  if (const char* e = getenv("OMK_LORA_UP_DBG")) a.dbg = atoi(e);
   dim3 grid((unsigned)((int64_t)a.NB * chunks)), block(256);
   OMK_LAUNCH(lora_up_bwd_kernel, grid, block, 0, stream, a);
   return finish_launch("lora_up_bwd");

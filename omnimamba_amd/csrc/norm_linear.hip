@@ -1046,7 +1046,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
     const bool fast = (wdt == OMK_F32 || wdt == OMK_BF16) && xdt == wdt && same(p->z) && same(p->norm_weight) && same(p->lora_a) &&
                       same(p->bias) && p->out.dtype == wdt && present(p->norm_weight) && a.G == 1 && a.R <= 8 && resok &&
                       (trdt == OMK_F32 || trdt == wdt) && a.In == 1024 * nq && (nq == 1 || nq == 2 || nq == 4) &&
-                      (!present(p->lora_b) || p->lora_b.stride[1] == 1) && !getenv("OMK_NORM_LINEAR_GENERIC");
+                      (!present(p->lora_b) || p->lora_b.stride[1] == 1);
     if (present(p->conv_state)) {
       OMK_REQUIRE(present(p->conv_weight) && p->conv_state.ndim == 3 && p->conv_weight.ndim == 2, "norm_linear: conv_state (B, C, S) needs conv_weight (C, W)");
       const int64_t Cc = p->conv_state.shape[1];
@@ -1077,8 +1077,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       dim3 bgrid((unsigned)((nw_ + NL_THREADS / 64 - 1) / (NL_THREADS / 64))), bblock(NL_THREADS);
       const bool gate = present(p->z);
       if (gate && present(p->residual)) return fail(OMK_EUNSUPPORTED, "norm_linear: residual and gate together are served by the batch-1 kernel only");
-      // 16-bit weights: the matrix-pipe form, a workgroup per tile of 16 rows (OMK_NL_MFMA=0: the vector form, for the A/B)
-      const bool use_mfma = !(getenv("OMK_NL_MFMA") && atoi(getenv("OMK_NL_MFMA")) == 0);   // (developer switches are read per call, all of them)
+      // 16-bit weights: the matrix-pipe form, a workgroup per tile of 16 rows
       // B rows of the LoRA read as 16-byte loads
       // (both matrices: load_lora reads the A rows as 16-byte vectors too -- advisor finding, round 5)
       const bool lora_rows16 = a.R == 0 || (a.R == 8 && (a.lbs * (wdt == OMK_F32 ? 4 : 2)) % 16 == 0 && (reinterpret_cast<uintptr_t>(a.lb) & 15) == 0 &&
@@ -1086,15 +1085,12 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       // fp32 weights (four v_mfma_f32_16x16x4_f32 per 16-byte vector): only where it was measured ahead of the vector form -- eight sequences
       // with LoRA, rows of up to 2048 features: 29.7 against 31.5 us for the 1.3B in_proj; behind it at two sequences (28.8 / 19.5 us) and
       // without LoRA (23.9 / 19.7 us) -- profiles/r05_decode_projections.txt.  (4096 features: 32 loads per lane and tile, no room for two tiles.)
-      const bool mfma_f32 = !(getenv("OMK_NL_MFMA_F32") && atoi(getenv("OMK_NL_MFMA_F32")) == 0);
-      const bool f32_ok = wdt == OMK_F32 && nq <= 2 && mfma_f32 && ((nb == 8 && a.R > 0) || (getenv("OMK_NL_MFMA_F32") && atoi(getenv("OMK_NL_MFMA_F32")) == 2));
-      if (use_mfma && lora_rows16 && (wdt == OMK_BF16 || f32_ok)) {
+      const bool f32_ok = wdt == OMK_F32 && nq <= 2 && nb == 8 && a.R > 0;
+      if (lora_rows16 && (wdt == OMK_BF16 || f32_ok)) {
         // tiles of 8 rows when there are fewer 16-row tiles than workgroups (out_proj of the 1.3B model: 11.1 -> 10.1 us at eight sequences,
-        // 8.4 -> 7.3 us at two; with several tiles per workgroup 8 rows are behind: in_proj 16.2 -> 17.7 us).  OMK_NL_MFMA_ROWS = 8 / 16 for the A/B
-        int wgs = cu_count();
-        if (const char* e = getenv("OMK_NL_MFMA_WGS")) wgs = atoi(e) > 0 ? atoi(e) : wgs;   // tests: several tiles per workgroup on small matrices
-        int rows = (a.Out + 15) / 16 < wgs ? 8 : 16;
-        if (const char* e = getenv("OMK_NL_MFMA_ROWS")) rows = atoi(e) == 8 ? 8 : (atoi(e) == 16 ? 16 : rows);
+        // 8.4 -> 7.3 us at two; with several tiles per workgroup 8 rows are behind: in_proj 16.2 -> 17.7 us)
+        const int wgs = test_hook("OMK_NL_MFMA_WGS", cu_count());   // (tests: several tiles per workgroup on small matrices)
+        const int rows = (a.Out + 15) / 16 < wgs ? 8 : 16;
         const int nwv = nq == 1 ? 4 : 8, ntile = (a.Out + rows - 1) / rows, ub = wdt == OMK_F32 ? 4 : 2;
         const size_t msmem = (size_t)nb * (a.In + 16 / ub) * ub + (size_t)nwv * nb * (9 + 2 * 16) * 4 + (size_t)nb * 9 * 4;
         dim3 mgrid((unsigned)(ntile < wgs ? ntile : wgs));
@@ -1143,8 +1139,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       const int vecw = wdt == OMK_F32 ? 4 : 8;
       const int steps_row = a.In / (64 * vecw), rw = 16 / steps_row;   // rows per batch (16 loads of 16 bytes per lane)
       // waves: every wave takes k full batches of rw rows (k as small as two workgroups per CU allow)
-      const int wpc = getenv("OMK_NLF_WPC") ? atoi(getenv("OMK_NLF_WPC")) : 2;   // workgroups per CU the grid is sized for
-      const int maxw = (wpc > 0 ? wpc : 2) * cu_count() * (NL_THREADS / 64);
+      const int maxw = 2 * cu_count() * (NL_THREADS / 64);   // two workgroups per CU
       const int k = (a.Out + rw * maxw - 1) / (rw * maxw);
       const int nw_ = (a.Out + rw * k - 1) / (rw * k);
       a.nbatch = k;

@@ -420,14 +420,8 @@ __global__ __launch_bounds__(NORM_THREADS) void norm_gated_fwd_lean_kernel(NormA
     const int64_t row = rraw < a.rows ? rraw : a.rows - 1;
 #pragma unroll
     for (int c = 0; c < NCHUNK; c++) {
-      if (a.rms & 32) {
-        const u32x4 vx = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + row * a.xs + g0 + NORM_COL(c)));
-        const u32x4 vz = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(z + row * a.zs + g0 + NORM_COL(c)));
-        rx[c] = __builtin_bit_cast(vec_t<TX, VEC>, vx); rz[c] = __builtin_bit_cast(vec_t<TX, VEC>, vz);
-      } else {
       rx[c] = *reinterpret_cast<const vec_t<TX, VEC>*>(x + row * a.xs + g0 + NORM_COL(c));
       rz[c] = *reinterpret_cast<const vec_t<TX, VEC>*>(z + row * a.zs + g0 + NORM_COL(c));
-      }
     }
   };
   if (bi < niter) issue(bi);
@@ -440,24 +434,23 @@ __global__ __launch_bounds__(NORM_THREADS) void norm_gated_fwd_lean_kernel(NormA
     for (int c = 0; c < NCHUNK; c++)
 #pragma unroll
       for (int i = 0; i < VEC; i++) {
-        v[c][i] = (a.rms & 4) ? to_f32(rx[c].e[i]) * to_f32(rz[c].e[i]) : to_f32(rx[c].e[i]) * silu_fast(to_f32(rz[c].e[i]));
+        v[c][i] = to_f32(rx[c].e[i]) * silu_fast(to_f32(rz[c].e[i]));
+        OMK_OPAQUE(v[c][i]);   // (without it this kernel holds more registers: 82 instead of 66 VGPRs at 4096 columns, five waves per SIMD instead of seven)
         s2 += v[c][i] * v[c][i];
       }
     if (it + nbg < niter) issue(it + nbg);   // (the staging registers are free: the next row's loads fly during the reduction)
-    const float rstd = (a.rms & 2) ? s2 : rsqrtf(row_sum<WPR>(s2, red, wave, rpar) * inv_n + a.eps);   // (a.rms bits 1, 2: developer ablations, OMK_NORM_ABL)
-    if (lane == 0 && wsub == 0 && a.rstd && rlive && !(a.rms & 8)) a.rstd[rraw * a.ngroups + grp] = rstd;
+    const float rstd = rsqrtf(row_sum<WPR>(s2, red, wave, rpar) * inv_n + a.eps);
+    if (lane == 0 && wsub == 0 && a.rstd && rlive) a.rstd[rraw * a.ngroups + grp] = rstd;
     if (rlive) {
 #pragma unroll
       for (int c = 0; c < NCHUNK; c++) {
         float o[VEC];
 #pragma unroll
         for (int i = 0; i < VEC; i++) o[i] = v[c][i] * rstd * wreg[c][i];
-        if (!(a.rms & 16)) {   // (streamed once: non-temporal, - 3 %)
-          vec_t<TX, VEC> ov;
+        vec_t<TX, VEC> ov;   // (streamed once: non-temporal, - 3 %)
 #pragma unroll
-          for (int i = 0; i < VEC; i++) ov.e[i] = from_f32<TX>(o[i]);
-          __builtin_nontemporal_store(__builtin_bit_cast(u32x4, ov), reinterpret_cast<u32x4*>(y + rraw * a.ys + g0 + NORM_COL(c)));
-        } else st<TX, VEC>(y + rraw * a.ys + g0 + NORM_COL(c), o);
+        for (int i = 0; i < VEC; i++) ov.e[i] = from_f32<TX>(o[i]);
+        __builtin_nontemporal_store(__builtin_bit_cast(u32x4, ov), reinterpret_cast<u32x4*>(y + rraw * a.ys + g0 + NORM_COL(c)));
       }
     }
   }
@@ -756,11 +749,16 @@ static bool plan_vec(int64_t seglen, bool can8, VecPlan* out) {
   if (seglen <= 4 * 32 * 64) { *out = {1, 32, 4}; return true; }         // <= 8192, any alignment
   return false;
 }
+// test hook: the workgroups of a launch capped at OMK_NORM_BLOCKS (64 .. 2^20), so that small tests take several rows per workgroup; 0 = unset
+static int norm_blocks_hook() {
+  const int v = test_hook("OMK_NORM_BLOCKS", 0);
+  return v >= 64 && v <= (1 << 20) ? v : 0;
+}
 static int norm_blocks(int64_t rows, int ngroups, const VecPlan& pl) {
   const int rpb = NORM_WAVES / pl.wpr;
   int64_t per_group = (rows + rpb - 1) / rpb;
   int64_t cap = NORM_MAX_BLOCKS / ngroups;
-  if (const char* e = getenv("OMK_NORM_BLOCKS")) { const int v = atoi(e); if (v >= 64 && v <= (1 << 20)) cap = v / ngroups; }   // developer A/B
+  if (const int v = norm_blocks_hook()) cap = v / ngroups;
   if (cap < 1) cap = 1;
   if (per_group > cap) per_group = cap;
   if (per_group < 1) per_group = 1;
@@ -814,13 +812,13 @@ extern "C" int omk_add_norm_fwd(const OmkAddNormFwd* p, omk_stream stream) {
   // short-lived workgroups (see omk_norm_gated_fwd): two block rows each, behind a prologue of 16-byte requests -- when every lane's columns exist and
   // the weight / bias rows are aligned; otherwise the persistent grid of rounds 1 - 5
   a.wvec = plan.vec == 8 && cols == (int64_t)plan.wpr * plan.nchunk * 64 * 8 && ((uintptr_t)p->weight.data & 15) == 0 &&
-           (!present(p->bias) || ((uintptr_t)p->bias.data & 15) == 0) && !getenv("OMK_NORM_PERSISTENT");
+           (!present(p->bias) || ((uintptr_t)p->bias.data & 15) == 0);
   int nblk = norm_blocks(rows, 1, plan);
   if (a.wvec) {
     const int rpb = NORM_WAVES / plan.wpr;
     int64_t per = (rows + rpb - 1) / rpb;
     if (per > 2048) per = (per + 1) / 2;
-    if (const char* e = getenv("OMK_NORM_BLOCKS")) { const int v = atoi(e); if (v >= 64 && v <= (1 << 20) && v < per) per = v; }   // developer A/B
+    if (const int v = norm_blocks_hook()) per = v < per ? v : per;
     nblk = (int)per;
   }
   dim3 grid(nblk), block(NORM_THREADS);
@@ -906,9 +904,8 @@ extern "C" int omk_norm_gated_fwd(const OmkNormGatedFwd* p, omk_stream stream) {
   dim3 grid(norm_blocks(rows, a.ngroups, plan)), block(NORM_THREADS);
   // the reference's mode on full segments (every lane's columns exist): the software-pipelined kernel
   const bool lean = present(p->z) && !present(p->bias) && !p->norm_before_gate && plan.vec == 8 && gs == (int64_t)plan.wpr * plan.nchunk * 64 * 8 &&
-                    p->x.dtype == OMK_BF16 && !getenv("OMK_NORM_NO_LEAN");
+                    p->x.dtype == OMK_BF16;
   if (lean) {
-    if (const char* e = getenv("OMK_NORM_ABL")) a.rms |= atoi(e) & 62;
     // SHORT-LIVED workgroups: two block rows each.  tools/probe/stream3_probe.hip (profiles/r06_stream_kernels.txt): the same three streams run
     // at 5.7 TB/s from workgroups that live for one or two rows and at 5.1 - 5.3 from 1024 - 2048 persistent ones, whatever their row map
     // (strided, contiguous ranges, an atomic queue) -- the rate falls steadily with the rows a workgroup walks.  The weight row is requested
@@ -917,7 +914,7 @@ extern "C" int omk_norm_gated_fwd(const OmkNormGatedFwd* p, omk_stream stream) {
     const int rpb = NORM_WAVES / plan.wpr;
     int64_t per_group = (rows + rpb - 1) / rpb;
     if (per_group > 2048) per_group = (per_group + 1) / 2;
-    if (const char* e = getenv("OMK_NORM_BLOCKS")) { const int v = atoi(e); if (v >= 64 && v <= (1 << 20) && v / a.ngroups < per_group) per_group = v / a.ngroups; }   // developer A/B
+    if (const int v = norm_blocks_hook()) per_group = v / a.ngroups < per_group ? v / a.ngroups : per_group;
     const dim3 lgrid((unsigned)(per_group * a.ngroups));
 #define OMK_LEAN_FWD(NC_, WPR_) do { if (wvec) OMK_LAUNCH((norm_gated_fwd_lean_kernel<bf16_t, 8, NC_, WPR_, true>), lgrid, block, 0, stream, a); \
       else OMK_LAUNCH((norm_gated_fwd_lean_kernel<bf16_t, 8, NC_, WPR_, false>), lgrid, block, 0, stream, a); } while (0)
@@ -970,8 +967,8 @@ extern "C" int omk_norm_gated_bwd(const OmkNormGatedBwd* p, omk_stream stream) {
   dim3 grid(norm_blocks(rows, ng, plan)), block(NORM_THREADS);
   const int64_t gsz = cols / ng;
   const bool lean = present(p->z) && present(p->dz) && !p->norm_before_gate && plan.vec == 8 && gsz == (int64_t)plan.wpr * plan.nchunk * 64 * 8 &&
-                    p->x.dtype == OMK_BF16 && !getenv("OMK_NORM_NO_LEAN");
-  const bool w8 = lean && ng == 1 && cols == NORM_W8_COLS && !getenv("OMK_NORM_BWD_W8_OFF");
+                    p->x.dtype == OMK_BF16;
+  const bool w8 = lean && ng == 1 && cols == NORM_W8_COLS;
   if (w8) {
     int nb = rows < NORM_W8_BLOCKS ? (int)rows : NORM_W8_BLOCKS;
     OMK_LAUNCH(norm_gated_bwd_w8_kernel, dim3((unsigned)nb), dim3(512), 0, stream, a);

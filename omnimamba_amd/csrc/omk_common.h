@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 
 #include "../../include/omk.h"
 #include "omk_platform.h"
@@ -43,6 +44,15 @@ inline bool strides_multiple_of(const OmkTensor& t, int64_t elems) {
   return true;
 }
 int finish_launch(const char* what);
+
+// ---- test hooks -------------------------------------------------------------------------------------------
+// The only environment the library reads: a hook lowers a size threshold so that the tests reach a path at
+// test size.  It never picks a variant the inputs cannot pick.  Unset, empty or not positive: `dflt`.
+inline int test_hook(const char* name, int dflt) {
+  const char* e = getenv(name);
+  const int v = e ? atoi(e) : 0;
+  return v > 0 ? v : dflt;
+}
 
 // ---- storage types --------------------------------------------------------------------------------------
 struct bf16_t { uint16_t v; };

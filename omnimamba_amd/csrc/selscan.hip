@@ -825,7 +825,6 @@ struct SsBwdArgs {
   float* dA; float* dB; float* dC; float* dD; float* ddb;
   int64_t dBsb, dBsg, dBsn, dBsl, dCsb, dCsg, dCsn, dCsl;   // variable: (B, G, N, L); constant: dBsg = stride over d, dBsn over n
   int NB, nOct;   // chunked form: state indices per LDS block, channel tiles per workgroup
-  int dbg;        // developer ablation bits (OMK_SELSCAN_BWD_DBG): 2 no flush atomics, 4 no n loop
   uint32_t xg, xdu, xdd, xdz;   // lanes = channels form: bytes one batch element of dout / du / ddelta / dz spans (buffer ranges)
 };
 
@@ -1066,7 +1065,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
         // ROTATED order -- at step k wave w owns row (k + w) mod R -- and stay in step through one barrier: no two waves ever touch
         // the same accumulator row at the same time and a plain 16-byte read-add-write does the job.
         const int R = nbn > NW ? nbn : NW;
-        for (int k = 0; k < ((q.dbg & 4) ? 0 : R); k++) {
+        for (int k = 0; k < R; k++) {
           int nl = k + wv;
           nl = nl >= R ? nl - R : nl;
           if (nl < nbn) {
@@ -1186,7 +1185,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
         float* slot = sAcc + ((size_t)k * NB + nl) * TP + ((t % LC) / 4 * 64 + t / LC) * 4 + t % 4;
         const float v = *slot;
         *slot = 0.f;
-        if (tile0 + t < a.L && !(q.dbg & 2)) {
+        if (tile0 + t < a.L) {
           if (k == 0) atomic_add_f32(dBbase + (int64_t)(nb0 + nl) * q.dBsn + (int64_t)(tile0 + t) * q.dBsl, v);
           else atomic_add_f32(dCbase + (int64_t)(nb0 + nl) * q.dCsn + (int64_t)(tile0 + t) * q.dCsl, v);
         }
@@ -1510,13 +1509,13 @@ static int ss_lanes_form(SsArgs& a, int udt) {
   const int64_t su = span(a.usd, a.usl, a.Dm), sdl = span(a.dsd, a.dsl, a.Dm), sz = z ? span(a.zsd, a.zsl, a.Dm) : 0, so = span(a.osd, a.osl, a.Dm);
   const int64_t sb = span(a.Bsn, a.Bsl, 16), sc = span(a.Csn, a.Csl, 16);
   if (su >= lim || sdl >= lim || sz >= lim || so >= lim || sb >= lim || sc >= lim) return 0;
-  const char* e = getenv("OMK_SELSCAN_LANES");
-  if (e && atoi(e) == 0) return 0;
   const int dpg = a.Dm / a.G;
   const int64_t nw = (int64_t)a.B * a.G * ((dpg + 63) / 64);
   // few sequences: time has to be cut (the chunked scan).  Measured crossovers at L 1024, D 768 (tools/bench_selscan.py): channel-last
-  // storage from ~200 waves (the alternative pays L-contiguous copies), L-contiguous storage from one wave per SIMD
-  if (!(e && atoi(e) == 1) && nw < (cl ? 192 : 1024) && a.L >= 64) return 0;
+  // storage from ~200 waves (the alternative pays L-contiguous copies), L-contiguous storage from one wave per SIMD.
+  // Test hook OMK_SELSCAN_LANES=1: no minimum number of waves
+  const bool any_waves = test_hook("OMK_SELSCAN_LANES", 0) == 1;
+  if (!any_waves && nw < (cl ? 192 : 1024) && a.L >= 64) return 0;
   auto ext = [&](int64_t sd, int64_t sl, int64_t nd) -> uint32_t { return (uint32_t)(es * ((nd - 1) * sd + ((int64_t)a.L - 1) * sl + 1)); };
   a.xu = ext(a.usd, a.usl, a.Dm); a.xd = ext(a.dsd, a.dsl, a.Dm); a.xz = z ? ext(a.zsd, a.zsl, a.Dm) : 0u; a.xo = ext(a.osd, a.osl, a.Dm);
   a.xB = ext(a.Bsn, a.Bsl, a.N); a.xC = ext(a.Csn, a.Csl, a.N);
@@ -1534,31 +1533,28 @@ static int ss_launch_fwd(SsArgs& a, int udt, omk_stream stream, bool pass_ckpt =
   }
   // L-contiguous storage (upstream's layout): the chunked associative scan, one wave per (batch, channel)
   const bool lcontig = pass_ckpt || (a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.out && a.osl == 1 && (!a.Bvar || a.Bsl == 1) &&
-                                     (!a.Cvar || a.Csl == 1) && (!a.ckpt || a.TLB == SSR_TP) && a.L >= 64 && !getenv("OMK_SELSCAN_SEQ"));
+                                     (!a.Cvar || a.Csl == 1) && (!a.ckpt || a.TLB == SSR_TP) && a.L >= 64);
   if (lcontig) {
     const int64_t nseq = (int64_t)a.B * a.Dm;
-    const char* lce = getenv("OMK_SELSCAN_LC");
-    const bool lc16 = (pass_ckpt || a.ckpt) ? false : lce ? atoi(lce) == 16 : a.L >= 1024 && nseq < 4096;   // pass states: 512-token passes   // few sequences: fewer, longer passes; many: occupancy
+    // few sequences: fewer, longer passes; many: occupancy.  (Pass states: 512-token passes.)
+    const bool lc16 = !pass_ckpt && !a.ckpt && a.L >= 1024 && nseq < 4096;
     const int lc = lc16 ? 16 : 8;
     // shared B / C rows: 8 adjacent channels of one group per workgroup, rows of u's dtype, <= 64 KB of LDS
     const size_t es = dtype_size(udt);
     const size_t bc_bytes = (size_t)((a.Bvar ? a.N : 0) + (a.Cvar && !pass_ckpt ? a.N : 0)) * 64 * lc * es;
     const bool share = a.Bvar && a.Cvar && (a.Dm / a.G) % 8 == 0 && a.bdt == udt && a.cdt == udt && a.adt == OMK_F32 && a.N <= 64 &&
-                       bc_bytes <= 64 * 1024 && !getenv("OMK_SELSCAN_NOSHARE");
+                       bc_bytes <= 64 * 1024;
     if (share) {
       dim3 grid((unsigned)(nseq / 8)), block(512);
 #define SSC_SH(T, LC_, NU_) do { \
         if (OMK_SET_MAX_DYN_SMEM((selscan_fwd_shared_kernel<T, LC_, NU_>), bc_bytes)) return fail(OMK_ELAUNCH, "selective_scan_fwd: cannot raise dynamic LDS to %zu", bc_bytes); \
         OMK_LAUNCH((selscan_fwd_shared_kernel<T, LC_, NU_>), grid, block, bc_bytes, stream, a); } while (0)
-      const char* nue = getenv("OMK_SELSCAN_NU");
-      const bool nu2 = nue ? atoi(nue) == 2 : true;   // packed token pairs in the n loop (OMK_SELSCAN_NU=1: the scalar form)
 #define SSC_ST(T) do { \
         if (OMK_SET_MAX_DYN_SMEM((selscan_fwd_shared_kernel<T, 8, 1, true>), bc_bytes)) return fail(OMK_ELAUNCH, "selective_scan_bwd: cannot raise dynamic LDS to %zu", bc_bytes); \
         OMK_LAUNCH((selscan_fwd_shared_kernel<T, 8, 1, true>), grid, block, bc_bytes, stream, a); } while (0)
       if (pass_ckpt) OMK_DISPATCH_DTYPE(udt, T, SSC_ST(T));
       else if (lc16) OMK_DISPATCH_DTYPE(udt, T, SSC_SH(T, 16, 1));
-      else if (nu2) OMK_DISPATCH_DTYPE(udt, T, SSC_SH(T, 8, 2));
-      else OMK_DISPATCH_DTYPE(udt, T, SSC_SH(T, 8, 1));
+      else OMK_DISPATCH_DTYPE(udt, T, SSC_SH(T, 8, 2));   // packed token pairs in the n loop
 #undef SSC_SH
 #undef SSC_ST
     } else {
@@ -1598,8 +1594,7 @@ extern "C" int omk_selective_scan_fwd(const OmkSelScanFwd* p, omk_stream stream)
                 "selective_scan_fwd: pass_states must be contiguous f32 (B, D, ceil(L / 512), N)");
     a.ckpt = (float*)p->pass_states.data; a.TLB = SSR_TP; a.nTB = nP;
     if (!ss_lanes_form(a, p->u.dtype) &&
-        (!(a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.osl == 1 && (!a.Bvar || a.Bsl == 1) && (!a.Cvar || a.Csl == 1) && a.L >= 64) ||
-         getenv("OMK_SELSCAN_SEQ")))
+        !(a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.osl == 1 && (!a.Bvar || a.Bsl == 1) && (!a.Cvar || a.Csl == 1) && a.L >= 64))
       return fail(OMK_EUNSUPPORTED, "selective_scan_fwd: pass_states need L-contiguous u / delta / z / out / B / C and L >= 64");
   }
   if ((rc = ss_launch_fwd(a, p->u.dtype, stream))) return rc;
@@ -1615,7 +1610,7 @@ extern "C" int omk_selective_scan_fwd_form(const OmkSelScanFwd* p) {
   if (present(p->pass_states)) { a.ckpt = (float*)p->pass_states.data; a.TLB = SSR_TP; }
   if (ss_lanes_form(a, p->u.dtype)) return 2;
   const bool lcontig = a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.osl == 1 && (!a.Bvar || a.Bsl == 1) && (!a.Cvar || a.Csl == 1) &&
-                       a.L >= 64 && !getenv("OMK_SELSCAN_SEQ");
+                       a.L >= 64;
   return lcontig ? 1 : 0;
 }
 
@@ -1707,7 +1702,7 @@ extern "C" int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream)
   // ---- L-contiguous storage, input-dependent B and C of u's dtype: the chunked associative scan in both directions
   const bool chunked = a.Bvar && a.Cvar && a.usl == 1 && a.dsl == 1 && (!a.z || (a.zsl == 1 && q.dzsl == 1)) && q.gsl == 1 && q.dusl == 1 &&
                        q.ddsl == 1 && a.Bsl == 1 && a.Csl == 1 && a.bdt == udt && a.cdt == udt && a.adt == OMK_F32 && dpg % 8 == 0 &&
-                       a.L >= 64 && !getenv("OMK_SELSCAN_SEQ");
+                       a.L >= 64;
   OMK_REQUIRE(!present(p->pass_states) || chunked, "selective_scan_bwd: pass_states belong to the chunked form (L-contiguous rows, variable B / C, L >= 64) or, as tile states, to the lanes = channels form");
   if (chunked) {
     a.TLB = SSR_TP; a.nTB = (a.L + SSR_TP - 1) / SSR_TP;
@@ -1721,17 +1716,16 @@ extern "C" int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream)
       f.out = nullptr; f.last = nullptr; f.z = nullptr; f.D = nullptr;
       if ((rc = ss_launch_fwd(f, udt, stream, true))) return rc;
     }
-    int NW = dpg % 16 == 0 ? 16 : 8;
-    if (const char* e = getenv("OMK_SELSCAN_BWD_NW")) { if (atoi(e) == 8) NW = 8; }
+    const int NW = dpg % 16 == 0 ? 16 : 8;
     const size_t es = dtype_size(udt);
     q.NB = a.N < 16 ? a.N : 16;
-    if (const char* e = getenv("OMK_SELSCAN_BWD_NB")) { const int v = atoi(e); if (v >= 1 && v <= 16) q.NB = v < a.N ? v : a.N; }
     q.nOct = 1;
     if (a.N <= q.NB)
       for (int o = 4; o > 1; o >>= 1)
         if (dpg % (NW * o) == 0 && (int64_t)a.B * a.Dm / (NW * o) >= 512) { q.nOct = o; break; }
-    if (const char* e = getenv("OMK_SELSCAN_BWD_OCT")) { const int o = atoi(e); if ((o == 1 || o == 2 || o == 4) && a.N <= q.NB && dpg % (NW * o) == 0) q.nOct = o; }
-    if (const char* e = getenv("OMK_SELSCAN_BWD_DBG")) q.dbg = atoi(e);
+    // test hook OMK_SELSCAN_BWD_OCT = 1 / 2 / 4: that many channel tiles per workgroup at any number of workgroups
+    const int oct = test_hook("OMK_SELSCAN_BWD_OCT", 0);
+    if ((oct == 1 || oct == 2 || oct == 4) && a.N <= q.NB && dpg % (NW * oct) == 0) q.nOct = oct;
     const size_t smem = (size_t)q.NB * SSR_TP * (8 + 2 * es) + (size_t)(3 * q.nOct * NW * (q.nOct > 1 ? 16 : 64) + NW * 64) * 4;
     dim3 grid((unsigned)((int64_t)a.B * a.Dm / (NW * q.nOct))), block(NW * 64);
 #define SSR_GO(T) do { if (OMK_SET_MAX_DYN_SMEM((selscan_bwd_chunked_kernel<T>), smem)) return fail(OMK_ELAUNCH, "selective_scan_bwd: cannot raise dynamic LDS to %zu", smem); \

@@ -544,16 +544,9 @@ static void launch_dt_prep(const OmkTensor& dt, const OmkTensor& dtb, const SsdD
                    (d.H % 2) == 0 && (d.L % 4) == 0 && ((uintptr_t)dtp & 15) == 0 && (!dsoft || ((uintptr_t)dsoft & 15) == 0);
   if (vec) {
     // 32-token tiles: 7.6 us per launch against 9.7 us with 64 (twice the blocks in flight; the (B, H, L) rows still leave as full 128-byte lines)
-    const int tok = getenv("OMK_DT_PREP_TOK") ? atoi(getenv("OMK_DT_PREP_TOK")) : 32;
-    if (tok == 32) {
-      dim3 grid((unsigned)((int64_t)d.B * ((d.L + 31) / 32) * ((d.H + 63) / 64)));
-      if (dt.dtype == OMK_BF16) OMK_LAUNCH((ssd_dt_prep_vec_kernel<bf16_t, 32>), grid, block, 0, stream, a);
-      else OMK_LAUNCH((ssd_dt_prep_vec_kernel<f16_t, 32>), grid, block, 0, stream, a);
-    } else {
-      dim3 grid((unsigned)((int64_t)d.B * ((d.L + 63) / 64) * ((d.H + 63) / 64)));
-      if (dt.dtype == OMK_BF16) OMK_LAUNCH((ssd_dt_prep_vec_kernel<bf16_t, 64>), grid, block, 0, stream, a);
-      else OMK_LAUNCH((ssd_dt_prep_vec_kernel<f16_t, 64>), grid, block, 0, stream, a);
-    }
+    dim3 grid((unsigned)((int64_t)d.B * ((d.L + 31) / 32) * ((d.H + 63) / 64)));
+    if (dt.dtype == OMK_BF16) OMK_LAUNCH((ssd_dt_prep_vec_kernel<bf16_t, 32>), grid, block, 0, stream, a);
+    else OMK_LAUNCH((ssd_dt_prep_vec_kernel<f16_t, 32>), grid, block, 0, stream, a);
     return;
   }
   dim3 grid((unsigned)((int64_t)d.B * ((d.L + 31) / 32) * ((d.H + 31) / 32)));
@@ -652,9 +645,9 @@ extern "C" int omk_ssd_scan_fwd(const OmkSsdFwd* p, omk_stream stream) {
   }
   g.out = p->out.data; g.osb = p->out.stride[0]; g.osl = p->out.stride[1]; g.osh = p->out.stride[2]; g.out_dt = p->out.dtype; g.outx = p->out_x.data;
   if (present(p->D)) { g.D = p->D.data; g.D_dt = p->D.dtype; g.Dsh = p->D.stride[0]; g.Dsp = p->D.ndim == 2 ? p->D.stride[1] : 0; }
-  if (getenv("OMK_PROF") && p->workspace_bytes >= omk_ssd_scan_fwd_workspace_bytes(p)) g.prof = (unsigned long long*)((char*)p->workspace + align256((size_t)d.B * d.H * d.L * 4));
 #ifdef OMK_PHASE_PROF
-  if (const char* e = getenv("OMK_ABLATE")) g.ablate = atoi(e);
+  if (getenv("OMK_PROF") && p->workspace_bytes >= omk_ssd_scan_fwd_workspace_bytes(p)) g.prof = (unsigned long long*)((char*)p->workspace + align256((size_t)d.B * d.H * d.L * 4));
+  if (const char* e = getenv("OMK_ABLATE")) g.ablate = atoi(e);   // (skips phases: wrong results)
   if (getenv("OMK_PROF_WG") && p->workspace_bytes >= omk_ssd_scan_fwd_workspace_bytes(p))   // the per-workgroup clocks instead of the phase sums: slots behind everything else
     { g.prof = (unsigned long long*)((char*)p->workspace + omk_ssd_scan_fwd_workspace_bytes(p) - 64 * 1024); g.ablate |= 1 << 20; }
 #endif

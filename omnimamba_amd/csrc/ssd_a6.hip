@@ -558,10 +558,9 @@ __global__ __launch_bounds__(512) void ssd_a6_kernel(GScan a) {
   }
 }
 
-// The column-slice kernel takes the class A scans of head PAIRS that share a group (OMK_SSD_A6=0: the row-strip kernel), split
+// The column-slice kernel takes the class A scans of head PAIRS that share a group (the row-strip kernel the others), split
 // sequences included (the zero-start state pass + fold of ssd_mfma_prepare_segments provides the segment start states).
 bool ssd_a6_applies(const GScan& g) {
-  if (const char* e = getenv("OMK_SSD_A6")) if (e[0] == '0') return false;
   if (g.mode != GS_Y && g.mode != GS_DX) return false;
   if (g.H % 2 != 0 || (g.H / g.G) % 2 != 0) return false;
   if (g.state_only) return false;

@@ -782,7 +782,6 @@ bool ssd_a8_applies(const GScan& g) {
 }
 
 int ssd_a8_launch(const GScan& g, omk_stream stream) {
-  if (getenv("OMK_SSD_TRACE")) fprintf(stderr, "[omk] ssd_a8 mode %d B %d L %d H %d dump %d fin %d seg %d flags %d\n", g.mode, g.B, g.L, g.H, g.dump != nullptr, g.fin != nullptr, g.seg != nullptr, g.flags);
   GScan a = g;
   const SegPlan sp = a.seg ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QA8 - 1) / QA8};
   a.nseg = sp.nseg; a.cps = sp.cps;

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(512) void ssd_cp_kernel(CpArgs a) {
     }
   };
   auto issue_sg = [&](int h) {   // the two state images: issued behind Phase B (the register peak), in flight during Phase A
-    const int64_t slot = (a.ablate & 4) ? 0 : ((((int64_t)b * a.nW + win) * a.H + h) << 13);
+    const int64_t slot = (((int64_t)b * a.nW + win) * a.H + h) << 13;
     const BufRes Fr = make_buf(a.Sf + slot, 16384u), Gr = make_buf(a.Sg + slot, 16384u);
     int tq = tid;
     OMK_OPAQUE(tq);
@@ -211,7 +211,6 @@ __global__ __launch_bounds__(512) void ssd_cp_kernel(CpArgs a) {
   // token scalars, restart values and dD of a finished head from the slots its waves filled (buffer sb): runs while the NEXT head
   // is being computed (waves 3 and 5: tokens; lane 0 of the scalar wave, ahead of its own next write of c_end / dec: the restart values), so nothing of it sits between the two barriers of a head
   auto readout = [&](int h, int sb, int ring) {
-    if (a.ablate & 64) return;
     const int64_t bh = (int64_t)b * a.H + h;
     if (w == RW0 || w == RW1) {
       int m = (w == RW0 ? 0 : 64) + lane;
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(512) void ssd_cp_kernel(CpArgs a) {
   for (int hi = 0; hi < hps; hi++) {
     const int h = hbeg + hi, sb = hi & 1;
     const bool more = hi + 1 < hps;
-    if (more && !(a.ablate & 8) && !(a.ablate & 512)) issue_xy(h + 1);   // next head's rows: in flight during both phases
+    if (more) issue_xy(h + 1);   // next head's rows: in flight during both phases
     if (hi > 0) readout(h - 1, sb ^ 1, r_prev);
     PTC(0);
     // (lane bases of the swizzled tiles; tile row blocks, k steps and column blocks enter as uniform adds / XORs on top of them)
@@ -270,9 +269,13 @@ __global__ __launch_bounds__(512) void ssd_cp_kernel(CpArgs a) {
     const float ecm_m = sm.ecm[sb][mrow], wsc_s = sm.wsc[sb][mrow], wsc0_s = sm.wsc0[sb][mrow], dts_s = sm.dts[sb][mrow];
     // (the k step of the row operands is an XOR on the swizzled segment index: four lane addresses shared by dy and x, both tiles)
     const int oB0 = oB, oB1 = oB ^ 16, oB2 = oB ^ 32, oB3 = oB ^ 48;
+    // (the two column blocks stay apart behind a branch the compiler cannot fold: as one basic block they need 136 VGPRs more than
+    // the kernel has -- scratch spills)
+    int split = 1;
+    OMK_OPAQUE_S(split);
 #pragma unroll
     for (int j = 0; j < 2; j++) {
-      if (a.ablate & 2) continue;
+      if (!split) continue;
       const int nbx = 32 * (2 * nh + j);   // column block of the state images: an XOR on the swizzled segment index
       // oT0, oT1 < 2048 (rows 0 .. 15 of a 128-column tile): the k step (16 rows = 2048 elements) stays an immediate offset
       const int t0 = oT0 ^ nbx, t1 = oT1 ^ nbx, cb = oC ^ nbx;
@@ -311,7 +314,7 @@ __global__ __launch_bounds__(512) void ssd_cp_kernel(CpArgs a) {
       }
     }
     // the two state images of the next head behind Phase B: sixteen 1 KB requests per wave in one burst stall on the address path
-    if (more && !(a.ablate & 8) && !(a.ablate & 256)) issue_sg(h + 1);
+    if (more) issue_sg(h + 1);
     PTC(1);
     // ---- Phase A: intra-window terms
     float qm = 0.f;
@@ -360,51 +363,45 @@ __global__ __launch_bounds__(512) void ssd_cp_kernel(CpArgs a) {
       OMK_CP_TILE(0); OMK_CP_TILE(1); OMK_SCHED_FENCE(); OMK_CP_TILE(2); OMK_CP_TILE(3); OMK_SCHED_FENCE(); OMK_CP_TILE(4);   // (pairs: five interleaved tiles do not fit the registers)
 #undef OMK_CP_TILE
     };
-    if (!(a.ablate & 1)) {
-      switch (rl) {
-        case 0: phaseA(std::integral_constant<int, 0>{}); break;
-        case 1: phaseA(std::integral_constant<int, 1>{}); break;
-        case 2: phaseA(std::integral_constant<int, 2>{}); break;
-        case 3: phaseA(std::integral_constant<int, 3>{}); break;
-        case 4: phaseA(std::integral_constant<int, 4>{}); break;
-        case 5: phaseA(std::integral_constant<int, 5>{}); break;
-        case 6: phaseA(std::integral_constant<int, 6>{}); break;
-        default: phaseA(std::integral_constant<int, 7>{}); break;
-      }
+    switch (rl) {
+      case 0: phaseA(std::integral_constant<int, 0>{}); break;
+      case 1: phaseA(std::integral_constant<int, 1>{}); break;
+      case 2: phaseA(std::integral_constant<int, 2>{}); break;
+      case 3: phaseA(std::integral_constant<int, 3>{}); break;
+      case 4: phaseA(std::integral_constant<int, 4>{}); break;
+      case 5: phaseA(std::integral_constant<int, 5>{}); break;
+      case 6: phaseA(std::integral_constant<int, 6>{}); break;
+      default: phaseA(std::integral_constant<int, 7>{}); break;
     }
-    if (!(a.ablate & 1)) {
-      // column sums: the other twelve rows of a tile sit in the lanes 16, 32, 48 further on
+    // column sums: the other twelve rows of a tile sit in the lanes 16, 32, 48 further on
 #pragma unroll
-      for (int t = 0; t < 5; t++) colv[t] += shfl_xor(colv[t], 16);
+    for (int t = 0; t < 5; t++) colv[t] += shfl_xor(colv[t], 16);
 #pragma unroll
-      for (int t = 0; t < 5; t++) colv[t] += shfl_xor(colv[t], 32);
+    for (int t = 0; t < 5; t++) colv[t] += shfl_xor(colv[t], 32);
 #pragma unroll
-      for (int t = 0; t < 5; t++)
-        if (tmb[t] >= 0 && g16 == 0) sm.colA[sb][tmb[t] * (tmb[t] + 1) / 2 + tsb[t]][t16] = colv[t];
-      // row sums of the two strips (zeros where the wave has no tile of a strip: every slot is rewritten for every head)
-      row16_sum4(ra0);
-      row16_sum4(ra1);
-      const float v0 = t16 == 0 ? ra0[0] : (t16 == 1 ? ra0[1] : (t16 == 2 ? ra0[2] : ra0[3]));
-      const float v1 = t16 == 0 ? ra1[0] : (t16 == 1 ? ra1[1] : (t16 == 2 ? ra1[2] : ra1[3]));
-      if (t16 < 4) { sm.rowA[sb][rl][0][4 * g16 + t16] = v0; sm.rowA[sb][rl][1][4 * g16 + t16] = v1; }
-    }
+    for (int t = 0; t < 5; t++)
+      if (tmb[t] >= 0 && g16 == 0) sm.colA[sb][tmb[t] * (tmb[t] + 1) / 2 + tsb[t]][t16] = colv[t];
+    // row sums of the two strips (zeros where the wave has no tile of a strip: every slot is rewritten for every head)
+    row16_sum4(ra0);
+    row16_sum4(ra1);
+    const float v0 = t16 == 0 ? ra0[0] : (t16 == 1 ? ra0[1] : (t16 == 2 ? ra0[2] : ra0[3]));
+    const float v1 = t16 == 0 ? ra1[0] : (t16 == 1 ? ra1[1] : (t16 == 2 ? ra1[2] : ra1[3]));
+    if (t16 < 4) { sm.rowA[sb][rl][0][4 * g16 + t16] = v0; sm.rowA[sb][rl][1][4 * g16 + t16] = v1; }
     PTC(2);
     ep += shfl_xor(ep, 32);
     wp += shfl_xor(wp, 32);
-    if (!(a.ablate & 128)) {
-      const float ei = h32 == 0 ? ecm_m * ep : 0.f, wi = h32 == 0 ? wsc0_s * wp : 0.f;   // this wave's n half
-      if (h32 == 0) { sm.eI[sb][nh][mrow] = ei; sm.wI[sb][nh][mrow] = wi; }
-      const float dtw = dts_s * wi;
-      const float s_all = wave_sum(dtw), s_eh = wave_sum(ei), s_qm = wave_sum(qm);
-      if (lane == 0) *reinterpret_cast<f32x4*>(&sm.mw[sb][w][0]) = f32x4{s_all, mbB < 2 ? s_all : 0.f, mbB < 2 ? 0.f : s_eh, s_qm};
-    }
-    if (more && !(a.ablate & 16)) stage_sums(r_next);
+    const float ei = h32 == 0 ? ecm_m * ep : 0.f, wi = h32 == 0 ? wsc0_s * wp : 0.f;   // this wave's n half
+    if (h32 == 0) { sm.eI[sb][nh][mrow] = ei; sm.wI[sb][nh][mrow] = wi; }
+    const float dtw = dts_s * wi;
+    const float s_all = wave_sum(dtw), s_eh = wave_sum(ei), s_qm = wave_sum(qm);
+    if (lane == 0) *reinterpret_cast<f32x4*>(&sm.mw[sb][w][0]) = f32x4{s_all, mbB < 2 ? s_all : 0.f, mbB < 2 ? 0.f : s_eh, s_qm};
+    if (more) stage_sums(r_next);
     PTC(3);
-    if (w == SW && more && !(a.ablate & 32)) scalars(h + 1, sb ^ 1, r_next);
+    if (w == SW && more) scalars(h + 1, sb ^ 1, r_next);
     PTC(4);
     block_sync();   // every read of this head's tiles is done, its token-scalar slots are complete
     PTC(5);
-    if (more && !(a.ablate & 16)) commit(sb ^ 1);
+    if (more) commit(sb ^ 1);
     PTC(6);
     block_sync();   // next head staged
     PTC(7);
@@ -543,14 +540,12 @@ int ssd_cp_heads_split(int B, int L, int H, int G) {
 // one head subset, bf16 gradients on 8-byte aligned rows: the kernel stores dB / dC itself (no fp32 partials, no fold launch)
 bool ssd_cp_direct(const CpArgs& a) {
   const bool al = (((uintptr_t)a.dB | (uintptr_t)a.dC) & 7) == 0 && ((a.dbsb | a.dbsl | a.dbsg | a.dcsb | a.dcsl | a.dcsg) & 3) == 0;
-  const char* de = getenv("OMK_CP_DIRECT");
-  return a.nhs == 1 && a.dB_dt == OMK_BF16 && a.dC_dt == OMK_BF16 && al && !(de && de[0] == '0');
+  return a.nhs == 1 && a.dB_dt == OMK_BF16 && a.dC_dt == OMK_BF16 && al;
 }
 
 int ssd_cp_launch(const CpArgs& a0, omk_stream stream) {
   CpArgs a = a0;
-  if (const char* e = getenv("OMK_CP_ABLATE")) a.ablate = atoi(e);
-  // 8-byte stores of four bf16: rows and group blocks of dB / dC 8-byte aligned (OMK_CP_DIRECT=0: the partial buffers + fold launch)
+  // 8-byte stores of four bf16: rows and group blocks of dB / dC 8-byte aligned (otherwise: the partial buffers + fold launch)
   a.direct = ssd_cp_direct(a) ? 1 : 0;
   kernels_note("ssd_cp<direct=%d,nhs=%d>", a.direct, a.nhs);
   const size_t smem = sizeof(SmemCp);

@@ -69,7 +69,7 @@ struct GScan {
   // weight element (channel c = h * DU + u, tap k) at cw[c * cwsc + k * cwsk], optional bias cb[c]
   const void* cw; int64_t cwsc, cwsk; int cw_dt, cW; const void* cb; int cb_dt;
   int state_only;                                                // class A (MFMA): no output, only the state pass from the initial state to `fin` (context-parallel shards)
-  unsigned long long* prof;                                      // developer only: per-wave phase cycle sums of workgroup 0 (OMK_PROF env)
+  unsigned long long* prof;                                      // developer only (OMK_PHASE_PROF builds, OMK_PROF=1): per-wave phase cycle sums of workgroup 0
   int ablate;                                                    // developer only (OMK_PHASE_PROF builds): phases to skip, wrong results
 };
 
@@ -82,16 +82,12 @@ struct SegPlan { int nseg, cps; };
 // restart interval of the decay-gradient prefix in chunks.  Every checkpoint is 16 KB per head and boundary (537 MB written
 // and read back per backward at B 8, L 4096 with an interval of 1), but thinning them costs accuracy: measured on the
 // emulator, L = 1024, d(dt) / dA rel-L2 2.1e-3 / 4.4e-2 at 1, 2.2e-3 / 4.6e-2 at 2, 2.8e-3 / 9.0e-2 at 4, 3.8e-3 / 2.0e-1 at 8,
-// and at L = 130 an interval of 2 already breaks the 6e-3 bound on d(dt).  Default 1; OMK_SSD_CKPT is an experiment knob.
-inline int ssd_ckpt_every() {
-  if (const char* e = getenv("OMK_SSD_CKPT")) { const int v = atoi(e); if (v >= 1 && v <= 64) return v; }
-  return 1;
-}
+// and at L = 130 an interval of 2 already breaks the 6e-3 bound on d(dt).  So: every boundary.
+constexpr int ssd_ckpt_every() { return 1; }
 inline SegPlan ssd_segments(int BH, int L) {
   const int nC = (L + 63) / 64;
   SegPlan p = {1, nC};
-  int minc = 8;   // chunks per segment at least (OMK_SSD_SEG_CHUNKS: test hook, lets short sequences split)
-  if (const char* e = getenv("OMK_SSD_SEG_CHUNKS")) minc = atoi(e) > 0 ? atoi(e) : minc;
+  const int minc = test_hook("OMK_SSD_SEG_CHUNKS", 8);   // chunks per segment at least (the test hook lets short sequences split)
   if (BH <= 0 || BH > 128) return p;
   int n = 512 / BH;
   if (n > nC / minc) n = nC / minc;
@@ -119,7 +115,7 @@ bool ssd_a6_applies(const GScan& g);
 int ssd_a6_launch(const GScan& g, omk_stream stream);
 int ssd_a6_state_only(const GScan& g, omk_stream stream);
 // the specialised-wave class A kernel (ssd_a8.hip): four compute waves of 32 state columns + four helper waves per head pair
-bool ssd_a8_applies(const GScan& g);   // OMK_SSD_A8=0: ssd_a6.hip takes its shapes
+bool ssd_a8_applies(const GScan& g);   // (no: ssd_a6.hip takes the shape)
 int ssd_a8_launch(const GScan& g, omk_stream stream);
 int ssd_a6_state_dump(const GScan& g, omk_stream stream);   // OMK_EUNSUPPORTED when the column-slice kernel does not take the shape
 // state-only pass over the whole sequence that leaves the window-boundary states in g.dump (class A descriptor, no output)
@@ -139,7 +135,6 @@ struct CpArgs {
   void *dB, *dC; int64_t dbsb, dbsl, dbsg, dcsb, dcsl, dcsg; int dB_dt, dC_dt;
   int B, L, H, G, nW, nhs;
   int direct;   // set by ssd_cp_launch: one head subset and bf16 gradients -- the kernel writes dB / dC itself
-  int ablate;   // developer only (OMK_CP_ABLATE): phases to skip, wrong results
   unsigned long long* prof;   // developer only (OMK_PHASE_PROF builds, OMK_CP_PROF=1): per-wave phase cycle sums of workgroup 0
 };
 int ssd_cp_heads_split(int B, int L, int H, int G);

@@ -202,7 +202,7 @@ extern "C" int omk_selective_state_update(const OmkStateUpdate* p, omk_stream st
                       (!present(p->z) || p->z.dtype == p->x.dtype) && p->out.dtype == p->x.dtype &&   // (an ABSENT gate has dtype 0 = fp32: the bf16 decode at batch 8 fell to the row kernel)
                       (int64_t)a.B * a.H * a.P * a.N >= ((int64_t)1 << 21);
     const int rpb = tied ? (64 / lpr) * 4 : 1;
-    if (tied && a.P % (rpb * 4) == 0 && !getenv("OMK_STATE_UPDATE_GENERIC")) {
+    if (tied && a.P % (rpb * 4) == 0) {
       dim3 grid((unsigned)((int64_t)a.B * a.H * (a.P / (rpb * 4))));
 #define SU_TIED(TS, TX) do { if (lpr == 32) OMK_LAUNCH((state_update_tied_kernel<TS, TX, 32, 4>), grid, block, 0, stream, a); \
                              else OMK_LAUNCH((state_update_tied_kernel<TS, TX, 16, 4>), grid, block, 0, stream, a); } while (0)

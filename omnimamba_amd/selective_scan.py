@@ -62,7 +62,7 @@ class SelectiveScanFn(torch.autograd.Function):
             ps = torch.empty(Bsz, (L + 15) // 16, A.shape[1], Dm, dtype=torch.float32, device=u.device)
         if (ps is None and not lanes_fwd and L >= 64 and any(ctx.needs_input_grad) and B4.dim() == 4 and C4.dim() == 4 and B4.dtype == u.dtype and C4.dtype == u.dtype and
                 (Dm // B4.shape[1]) % 8 == 0 and (out.stride(1) == 1 or all(t is None or t.stride(-1) == 1 for t in (u, delta, z, B4, C4))) and
-                not os.environ.get("OMK_SELSCAN_SEQ") and not os.environ.get("OMK_SELSCAN_NO_PASS_STATES")):
+                not os.environ.get("OMK_SELSCAN_NO_PASS_STATES")):
             # = the conditions of the chunked backward (selscan.hip); without the tensor the backward runs a state-only forward pass first
             ps = torch.empty(Bsz, Dm, (L + 511) // 512, A.shape[1], dtype=torch.float32, device=u.device)
         if u.numel() > 0:
@@ -87,7 +87,7 @@ class SelectiveScanFn(torch.autograd.Function):
         dout = dout.to(u.dtype)
         lanes = False
         tile_ps = ps is not None and ps.shape[-1] == u.shape[1] and ps.shape[1] == (u.shape[2] + 15) // 16
-        if u.stride(1) == 1 and u.shape[1] > 1 and u.numel() > 0 and (ps is None or tile_ps) and os.environ.get("OMK_SELSCAN_BWD_LANES", "1") != "0":   # (=0: developer A/B against the copies + chunked scan)
+        if u.stride(1) == 1 and u.shape[1] > 1 and u.numel() > 0 and (ps is None or tile_ps):
             # channel-last views (what the Mamba-1 module holds): with enough sequences the lanes-are-channels reverse sweep reads and
             # writes them as they lie (omk_selective_scan_bwd_form == 2, selscan.hip: selscan_bwd_lanes_kernel) -- no L-contiguous copies
             Bsz, Dm, L = u.shape

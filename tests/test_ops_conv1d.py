@@ -5,6 +5,12 @@ import torch
 import oracle as O
 
 
+def without_workspace(monkeypatch):
+    """The raw backward without the workspace the autograd node passes: dweight / dbias through fp32 atomics (rounds 1 - 5)."""
+    from omnimamba_amd import causal_conv1d as CC
+    monkeypatch.setattr(CC.K, "workspace", lambda *args: None)
+
+
 def rel(a, b):
     return ((a.double().cpu() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
 
@@ -83,7 +89,7 @@ def test_conv1d_long_strips_both_prologues_agree(dev, W):
 
 def test_conv1d_bwd_partial_rows_are_deterministic_and_equal_the_atomics(dev, monkeypatch):
     """Long channel-last 16-bit rows: with the workspace of omk_causal_conv1d_bwd_workspace_bytes (what the autograd nodes pass) dweight / dbias come
-    from per-tile partial rows added up in a fixed order -- the same bits on every run; OMK_CONV_BWD_ATOMICS=1 takes the fp32 atomics of rounds 1 - 5."""
+    from per-tile partial rows added up in a fixed order -- the same bits on every run; without a workspace the fp32 atomics of rounds 1 - 5."""
     from omnimamba_amd.causal_conv1d import causal_conv1d_fn
     torch.manual_seed(3)
     B, C, L, W = 3, 24, 700, 4
@@ -99,7 +105,7 @@ def test_conv1d_bwd_partial_rows_are_deterministic_and_equal_the_atomics(dev, mo
 
     a1, a2 = grads(), grads()
     assert all(torch.equal(u, v) for u, v in zip(a1, a2))
-    monkeypatch.setenv("OMK_CONV_BWD_ATOMICS", "1")
+    without_workspace(monkeypatch)
     a3 = grads()
     assert torch.equal(a1[0], a3[0]) and rel(a1[1], a3[1].double()) < 1e-5 and rel(a1[2], a3[2].double()) < 1e-5
 
@@ -133,7 +139,7 @@ def test_conv1d_update(dev, dtype):
 def test_conv1d_channel_blocks_and_bwd_folds(dev, monkeypatch, C, W, dtype):
     """Channel-last 16-bit rows wide enough for several channel blocks of 128 (the grid's ceil(C / 2 / 64)): C 136 / 264 leave a partial
     last block.  L 300 >= 256 takes conv1d_fwd_cl8_kernel and conv1d_bwd_cl4_kernel (f16_t instantiations for fp16) with two 256-token
-    strips, the second ragged.  dweight / dbias through the partial-row fold (B x ceil(L / 256) rows) and through OMK_CONV_BWD_ATOMICS=1;
+    strips, the second ragged.  dweight / dbias through the partial-row fold (B x ceil(L / 256) rows) and, without a workspace, atomics;
     with and without initial states.  Bounds: tolerances.op_bound against fp64 of the tensors the kernels read."""
     from omnimamba_amd.causal_conv1d import causal_conv1d_fn
     from tolerances import op_bound
@@ -152,7 +158,7 @@ def test_conv1d_channel_blocks_and_bwd_folds(dev, monkeypatch, C, W, dtype):
 
     for fold in ("parts", "atomics"):
         if fold == "atomics":
-            monkeypatch.setenv("OMK_CONV_BWD_ATOMICS", "1")
+            without_workspace(monkeypatch)
         for use_init in (False, True):
             xr = xdev.detach().requires_grad_()
             wr, br = w.clone().to(dev).requires_grad_(), b.clone().to(dev).requires_grad_()

@@ -77,10 +77,10 @@ def _b_view(N, R, kind, dtype, g):
 @pytest.mark.parametrize("out_dtype", [torch.bfloat16, torch.float16, torch.float32])
 @pytest.mark.parametrize("b_dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("b_kind", ["contiguous", "strided"])
-def test_lora_add_b_operand_paths(dev, monkeypatch, out_dtype, b_dtype, b_kind):
+def test_lora_add_b_operand_paths(dev, out_dtype, b_dtype, b_kind):
     """omk_lora_add for every lora_b form and output dtype the entry accepts: a.bvec (contiguous, aligned B rows) against the per-element
-    loads of a strided view or OMK_LORA_ADD_NOVEC -- the same bits -- and both against fp64 (tolerances.op_bound).  T 70 x N 264: a ragged
-    token block and a partial column block."""
+    loads of a strided view -- the same bits -- and both against fp64 (tolerances.op_bound).  T 70 x N 264: a ragged token block and a
+    partial column block."""
     from omnimamba_amd import lora_add as LA
     from tolerances import op_bound
     g = torch.Generator().manual_seed(7)
@@ -89,21 +89,20 @@ def test_lora_add_b_operand_paths(dev, monkeypatch, out_dtype, b_dtype, b_kind):
     Bw = _b_view(N, R, b_kind, b_dtype, g)
     ref = res.double() + 4.0 * h.double() @ Bw.double().t()
 
-    def run():
+    def run(kind):
         od = res.clone().to(dev)
-        Bd = Bw.to(dev) if b_kind == "contiguous" else _b_view(N, R, b_kind, b_dtype, torch.Generator().manual_seed(7))
-        if b_kind != "contiguous":   # the same values, as a strided view on the device
+        Bd = Bw.to(dev).contiguous()
+        if kind != "contiguous":   # the same values, as a strided view on the device
             wide = torch.zeros(N, 2 * R, dtype=b_dtype, device=dev)
-            wide[:, 3:3 + R] = Bw.to(dev)
+            wide[:, 3:3 + R] = Bd
             Bd = wide[:, 3:3 + R]
         assert LA.applies(od, h.to(dev), Bd)
         return LA.lora_add_(od, h.to(dev), Bd, 4.0).cpu()
 
-    out = run()
+    out = run(b_kind)
     e, bnd = rel(out, ref), op_bound(ref, out_dtype)
     assert out.dtype == out_dtype and e <= bnd, (e, bnd)
-    monkeypatch.setenv("OMK_LORA_ADD_NOVEC", "1")
-    assert torch.equal(run(), out)
+    assert torch.equal(run("strided" if b_kind == "contiguous" else "contiguous"), out)   # the other B operand path
 
 
 def test_lora_add_fp16_autograd(dev):

@@ -44,12 +44,13 @@ def test_gated_norm_linear(dev, B, In, Out, G, nbg):
     (2048, 333, torch.float32, torch.float32, True, False), (4096, 77, torch.float32, torch.float32, False, True),
     (2048, 517, torch.bfloat16, torch.float32, True, False), (2048, 64, torch.bfloat16, torch.bfloat16, True, False),
     (4096, 130, torch.bfloat16, torch.float32, False, True), (1024, 1000, torch.bfloat16, torch.float32, True, True)])
-def test_uniform_dtype_variant(dev, monkeypatch, In, Out, dtype, rdtype, with_lora, with_z):
+def test_uniform_dtype_variant(dev, In, Out, dtype, rdtype, with_lora, with_z):
     """The templated kernel the 1.3B decode takes (one dtype for activations, weights, norm weight and LoRA; fp32 or that
-    dtype for the residual): against the fp64 composition, and against the generic kernel on the same inputs."""
+    dtype for the residual): against the fp64 composition, and against the generic kernel on the same inputs (the norm weight's
+    values in the other dtype: a mix the templated kernel does not take)."""
     from omnimamba_amd.norm_linear import norm_linear
     x, res, z = torch.randn(1, In).to(dtype), torch.randn(1, In).to(rdtype), torch.randn(1, In).to(dtype)
-    nw, W, bias = (torch.rand(In) + 0.5).to(dtype), (torch.randn(Out, In) * 0.05).to(dtype), torch.randn(Out).to(dtype)
+    nw, W, bias = (torch.rand(In) + 0.5).bfloat16().to(dtype), (torch.randn(Out, In) * 0.05).to(dtype), torch.randn(Out).to(dtype)
     la, lb = (torch.randn(8, In) * 0.05).to(dtype), (torch.randn(Out, 8) * 0.05).to(dtype)
     kw = dict(norm_weight=nw.to(dev), eps=1e-5)
     if with_z:
@@ -59,8 +60,8 @@ def test_uniform_dtype_variant(dev, monkeypatch, In, Out, dtype, rdtype, with_lo
     if with_lora:
         kw.update(lora_a=la.to(dev), lora_b=lb.to(dev), lora_scale=4.0)
     r = norm_linear(x.to(dev), W.to(dev), bias.to(dev), **kw)
-    monkeypatch.setenv("OMK_NORM_LINEAR_GENERIC", "1")
-    g = norm_linear(x.to(dev), W.to(dev), bias.to(dev), **kw)
+    other = torch.bfloat16 if dtype == torch.float32 else torch.float32
+    g = norm_linear(x.to(dev), W.to(dev), bias.to(dev), **dict(kw, norm_weight=nw.to(other).to(dev)))
     out, outg = (r, g) if with_z else (r[0], g[0])
     xd = x.double()
     if with_z:
@@ -149,13 +150,12 @@ def test_batched_variant(dev, B, In, Out, dtype, rdtype, mode):
 
 @pytest.mark.parametrize("wgs,dtype", [(1, torch.bfloat16), (3, torch.bfloat16), (4, torch.bfloat16), (3, torch.float32), (4, torch.float32)])
 def test_batched_matrix_form_walks_several_tiles_per_workgroup(dev, wgs, dtype, monkeypatch):
-    """Two to eight sequences (bf16 weights; fp32 weights with rows of up to 2048 features): a workgroup of norm_linear_mfma_kernel walks the tiles blockIdx.x, + gridDim.x, ... with two
-    register sets of weights and finish operands in flight (the 1.3B in_proj: 532 tiles on 256 workgroups).  Forced here on a small matrix
-    (OMK_NL_MFMA_WGS): 13 tiles on 1 / 3 / 4 workgroups -- odd and even tile counts per workgroup, a ragged last tile, LoRA, conv tail over
-    two steps; and the same call through the vector form (OMK_NL_MFMA=0 is read once per process, so the comparison is with the composition)."""
+    """Two to eight sequences (bf16 weights; fp32 weights with rows of up to 2048 features, five to eight sequences and LoRA): a workgroup of
+    norm_linear_mfma_kernel walks the tiles blockIdx.x, + gridDim.x, ... with two register sets of weights and finish operands in flight (the
+    1.3B in_proj: 532 tiles on 256 workgroups).  Forced here on a small matrix (OMK_NL_MFMA_WGS): 13 tiles on 1 / 3 / 4 workgroups -- odd and
+    even tile counts per workgroup, a ragged last tile, LoRA, conv tail over two steps; against the composition."""
     from omnimamba_amd.norm_linear import norm_linear
     monkeypatch.setenv("OMK_NL_MFMA_WGS", str(wgs))
-    monkeypatch.setenv("OMK_NL_MFMA_F32", "2")        # fp32 weights: the matrix form at any batch (by default only where it is ahead: 8 sequences + LoRA)
     torch.manual_seed(3)
     B, In, Out, C, off, W, S = 5, 2048, 200, 100, 60, 4, 3
     f32 = dtype == torch.float32

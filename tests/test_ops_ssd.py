@@ -42,11 +42,11 @@ def test_ssd_generic_fwd(dev, dtype, L, H, P, N, G):
 
 @pytest.mark.parametrize("L,H,P,G,with_z,with_init,dhp", [(150, 2, 64, 1, True, True, False), (16, 4, 64, 2, False, False, False),
                                                           (37, 2, 32, 1, True, False, True), (1, 2, 64, 1, False, True, False)])
-def test_ssd_f32_mfma_fwd(dev, monkeypatch, L, H, P, G, with_z, with_init, dhp):
+def test_ssd_f32_mfma_fwd_against_generic(dev, L, H, P, G, with_z, with_init, dhp):
     """fp32 activations (the reference's inference default) take the fp32 matrix-instruction kernel (csrc/ssd_f32.hip: chunks of 16
     tokens, a head cut into 16-column workgroups, no operand rounding): same accuracy class as the token-by-token generic kernel --
     y, the pre-gate copy and the final state against the fp64 recurrence at 3e-5; ragged lengths, one token, gate, initial state,
-    D per head and per (head, column), two groups.  OMK_SSD_F32_MFMA=0 gives the generic kernel: the two agree to 2e-5."""
+    D per head and per (head, column), two groups.  force_generic=True gives the generic kernel: the two agree to 2e-5."""
     from omnimamba_amd.ssd_combined import ssd_scan_fwd
     N = 128
     x, dt, A, Bm, Cm, D, z, dtb, init = make(2, L, H, P, N, G, torch.float32, seed=9)
@@ -65,8 +65,7 @@ def test_ssd_f32_mfma_fwd(dev, monkeypatch, L, H, P, G, with_z, with_init, dhp):
     if with_z:
         ox0 = O.ssd_ref_sequential(x, dt, A, Bm, Cm, D=D, dt_bias=dtb, initial_states=init, dt_softplus=True, dt_limit=(0.0, 3.0), compute_dtype=torch.float64)
         assert rel(out_x, ox0) < 3e-5
-    monkeypatch.setenv("OMK_SSD_F32_MFMA", "0")
-    out_g, _, fin_g = ssd_scan_fwd(d(x), d(dt), d(A), d(Bm), d(Cm), **kw)
+    out_g, _, fin_g = ssd_scan_fwd(d(x), d(dt), d(A), d(Bm), d(Cm), force_generic=True, **kw)
     assert rel(out, out_g.cpu()) < 2e-5 and rel(fin, fin_g.cpu()) < 2e-5 and not torch.equal(out.cpu(), out_g.cpu())
 
 

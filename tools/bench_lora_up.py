@@ -13,4 +13,4 @@ dy, h = torch.randn(T, N, device=dev).bfloat16(), torch.randn(T, 8, device=dev).
 B = torch.randn(N, 8, device=dev) * 0.1
 t_f = min(timeit(lambda: LA.lora_up_bwd(dy, h, B), 20, 3) for _ in range(3))
 t_g = min(timeit(lambda: (dy @ B.bfloat16(), weight_grad(dy, h, torch.float32)), 20, 3) for _ in range(3))
-print(f"fused {t_f * 1e3:7.1f} us ({T * N * 2 / t_f / 1e6:6.0f} GB/s)   two GEMMs {t_g * 1e3:7.1f} us   (OMK_LORA_UP_DBG={os.environ.get('OMK_LORA_UP_DBG', '0')})")
+print(f"fused {t_f * 1e3:7.1f} us ({T * N * 2 / t_f / 1e6:6.0f} GB/s)   two GEMMs {t_g * 1e3:7.1f} us")

@@ -1,5 +1,5 @@
 """Developer tool: forward of the Mamba-1 mixer module (d_model 384 -> d_inner 768, d_state 16) at L 1024 over a few batch sizes.
-OMK_SELSCAN_LANES=0 keeps the lanes-are-channels scan out (L-contiguous copies of x, z, dt, B, C + chunked scan)."""
+OMK_SELSCAN_LANES=1 (a test hook of the library) takes the lanes-are-channels scan at every batch size."""
 import os
 import sys
 import torch

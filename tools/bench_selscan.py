@@ -1,6 +1,6 @@
 """Developer tool: Mamba-1 selective_scan forward (and, with --bwd, forward + backward) at BASELINE configs[0] (B 2, L 1024, D 768,
 N 16 fp32) and scaled batches; --bld: channel-last (B, L, D) views as the Mamba-1 module holds them; --batches 2,16,64.
-OMK_SELSCAN_LANES=0 keeps the lanes-are-channels sweep out (chunked scan, copies for channel-last views)."""
+OMK_SELSCAN_LANES=1 (a test hook of the library) takes the lanes-are-channels sweep at every batch size."""
 import os
 import sys
 import torch

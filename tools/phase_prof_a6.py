@@ -2,7 +2,6 @@
 import os, sys
 os.environ["OMK_PROF"] = "1"
 os.environ["OMK_SSD_NO_SPLIT"] = "1"
-os.environ.setdefault("OMK_SSD_A6", "1")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from omnimamba_amd import _capi as K
