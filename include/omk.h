@@ -24,11 +24,11 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 7
+#define OMK_ABI_VERSION 8
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
-typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */ } omk_dtype;
+typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices only */ } omk_dtype;
 typedef void* omk_stream; /* hipStream_t */
 
 typedef struct {
@@ -151,6 +151,11 @@ typedef struct {
   OmkTensor weight, bias;
   OmkTensor out;        /* (B, C, T) */
   int32_t silu;
+  /* ABI 8, optional int32 (B): row b of x / out reads and writes conv_state row conv_state_indices[b] of a pool whose batch
+   * dimension may exceed B.  A negative index (or one >= the pool's rows) marks a padding row: no state is read or written
+   * and the row's out is zeros.  Two rows with the same non-negative index: undefined result.  Indices are read on the
+   * device only (graph-capturable).  Absent: conv_state is (B, C, S) and row b is state row b. */
+  OmkTensor conv_state_indices;
 } OmkConv1dUpdate;
 int omk_causal_conv1d_update(const OmkConv1dUpdate* p, omk_stream stream);
 
@@ -168,6 +173,11 @@ typedef struct {
   OmkTensor dt_bias; /* optional (H, P) */
   OmkTensor out;     /* (B, H, P) */
   int32_t dt_softplus;
+  /* ABI 8, optional int32 (B): row b of x / dt / B / C / z / out reads and writes state row state_batch_indices[b] of a pool
+   * whose batch dimension may exceed B.  A negative index (or one >= the pool's rows) marks a padding row: no state is read
+   * or written and the row's out is zeros.  Two rows with the same non-negative index: undefined result.  Indices are read
+   * on the device only (graph-capturable).  Absent: state is (B, H, P, N) and row b is state row b. */
+  OmkTensor state_batch_indices;
 } OmkStateUpdate;
 int omk_selective_state_update(const OmkStateUpdate* p, omk_stream stream);
 
@@ -246,6 +256,11 @@ typedef struct {
   float lora_scale;
   int32_t norm_before_gate;
   int32_t conv_silu;
+  /* ABI 8, optional int32 (B), only with conv_state: sequence b rolls conv_state row conv_state_indices[b] of a pool whose
+   * batch dimension may exceed B.  A negative index (or one >= the pool's rows) marks a padding row: its conv state is not
+   * read or written and its conv columns [conv_offset, conv_offset + C) of out are zeros (the other columns are computed as
+   * usual).  Two rows with the same non-negative index: undefined result.  Indices are read on the device only. */
+  OmkTensor conv_state_indices;
 } OmkNormLinear;
 int omk_norm_linear(const OmkNormLinear* p, omk_stream stream);
 

@@ -11,9 +11,9 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 7
+OMK_ABI_VERSION = 8
 OMK_MAX_DIMS = 5
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3}   # 3 = OMK_U8: masks only
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices only
 
 
 class OmkTensor(C.Structure):
@@ -27,7 +27,7 @@ def T(t: Optional[torch.Tensor]) -> OmkTensor:
         return o
     dt = _DT.get(t.dtype)
     if dt is None:
-        raise TypeError(f"unsupported dtype {t.dtype} (f32/bf16/f16, u8/bool masks only)")
+        raise TypeError(f"unsupported dtype {t.dtype} (f32/bf16/f16, u8/bool masks, int32 indices only)")
     n = t.dim()
     if n > OMK_MAX_DIMS:
         raise ValueError("too many dims")
@@ -59,9 +59,9 @@ Conv1dFwd = _S("OmkConv1dFwd", [(n, _t) for n in ("x", "weight", "bias", "initia
                + [("silu", _i)])
 Conv1dBwd = _S("OmkConv1dBwd", [(n, _t) for n in ("x", "weight", "bias", "initial_states", "dout", "dx", "dweight",
                                                   "dbias", "dinitial_states")] + [("silu", _i), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)])
-Conv1dUpdate = _S("OmkConv1dUpdate", [(n, _t) for n in ("x", "conv_state", "weight", "bias", "out")] + [("silu", _i)])
+Conv1dUpdate = _S("OmkConv1dUpdate", [(n, _t) for n in ("x", "conv_state", "weight", "bias", "out")] + [("silu", _i), ("conv_state_indices", _t)])
 StateUpdate = _S("OmkStateUpdate", [(n, _t) for n in ("state", "x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "out")]
-                 + [("dt_softplus", _i)])
+                 + [("dt_softplus", _i), ("state_batch_indices", _t)])
 SelScanFwd = _S("OmkSelScanFwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm", "D", "z", "delta_bias", "out",
                                                     "last_state", "pass_states")] + [("delta_softplus", _i)])
 SelScanBwd = _S("OmkSelScanBwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm", "D", "z", "delta_bias", "dout", "du",
@@ -70,7 +70,7 @@ SelScanBwd = _S("OmkSelScanBwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm
 NormLinear = _S("OmkNormLinear", [(n, _t) for n in ("x", "residual", "z", "norm_weight", "weight", "bias", "lora_a", "lora_b",
                                                     "residual_out", "out", "conv_state", "conv_weight", "conv_bias")]
                 + [("group_size", C.c_int64), ("conv_offset", C.c_int64), ("eps", _f), ("lora_scale", _f),
-                   ("norm_before_gate", _i), ("conv_silu", _i)])
+                   ("norm_before_gate", _i), ("conv_silu", _i), ("conv_state_indices", _t)])
 LoraAdd = _S("OmkLoraAdd", [(n, _t) for n in ("out", "h", "lora_b", "mask")] + [("scale", _f)])
 LoraUpBwd = _S("OmkLoraUpBwd", [(n, _t) for n in ("dy", "lora_b", "h", "dh", "dlora_b")])
 SsdFwd = _S("OmkSsdFwd", [(n, _t) for n in ("x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "initial_states", "out",

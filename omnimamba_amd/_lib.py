@@ -46,3 +46,19 @@ def require_device(lib, *tensors):
             dev = t.device
         elif t.device != dev:
             raise RuntimeError(f"tensors on different devices: {dev} vs {t.device}")
+
+
+def slot_indices(idx, batch, device, name):
+    """Host checks of a slot-index tensor (state_batch_indices / conv_state_indices): 1-D, `batch` long, on `device`, int32 -- or
+    int64, cast here with one extra launch.  The values are never read on the host: a step that carries them stays capturable."""
+    if idx is None:
+        return None
+    if idx.dim() != 1 or idx.shape[0] != batch:
+        raise ValueError(f"{name} must be 1-D of length {batch}, got shape {tuple(idx.shape)}")
+    if idx.device != device:
+        raise ValueError(f"{name} is on {idx.device}, the batch on {device}")
+    if idx.dtype == torch.int64:
+        idx = idx.to(torch.int32)
+    elif idx.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32 (or int64), got {idx.dtype}")
+    return idx if idx.is_contiguous() else idx.contiguous()

@@ -1,0 +1,198 @@
+"""Continuous batching of decode requests of different prompt and answer lengths (MMU questions: 4 + 729 image positions + a question of
+any length, answers that end at EOS).
+
+The states live in a pool of ``max_batch`` slots.  A request is admitted FIFO into a free slot: a batch-1 prefill at its exact length
+writes the slot (views of the pool: no padding ever reaches a recurrent state), its first id is sampled from the prefill logits, and it
+joins the step.  The step runs the live rows in the smallest bucket of {1, 2, 4, ..., max_batch} that holds them; every row carries its
+own position and its slot (``InferenceParams.state_indices``), empty rows of the bucket carry slot -1 and leave every state alone.  A row
+retires on EOS or at its own ``max_length``; its slot goes to the next request.  Retiring and admitting rewrite the small row buffers
+(ids, positions, slots) and never move a state.  With ``cg=True`` one step graph is captured per bucket.
+"""
+from __future__ import annotations
+
+from collections import deque
+
+import torch
+
+from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
+
+
+def _buckets(max_batch):
+    b, out = 1, []
+    while b < max_batch:
+        out.append(b)
+        b *= 2
+    return out + [max_batch]
+
+
+class _Bucket:
+    """Static row buffers of one bucket size and the InferenceParams that point the step at the pool through them; with cg the
+    captured step (empty rows only while it is warmed up and captured: no state is touched)."""
+
+    def __init__(self, model, pool, nb, max_seqlen, task, cg, mempool):
+        dev = next(iter(model.parameters())).device
+        self.nb = nb
+        self.input_ids = torch.zeros(nb, 1, dtype=torch.long, device=dev)
+        self.position_ids = torch.zeros(nb, 1, dtype=torch.long, device=dev)
+        self.slots = torch.full((nb,), -1, dtype=torch.int32, device=dev)
+        # seqlen_offset > 0 selects the step branch everywhere; its value is not read by the step itself
+        self.ip = InferenceParams(max_seqlen=max_seqlen, max_batch_size=nb, seqlen_offset=1, key_value_memory_dict=pool,
+                                  state_indices=self.slots)
+        self.task = task
+        self.model = model
+        self.graph = None
+        if cg:
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    self._fwd()
+                s.synchronize()
+            torch.cuda.current_stream().wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, pool=mempool):
+                self.logits = self._fwd()
+
+    def _fwd(self):
+        out = self.model(self.input_ids, None, position_ids=self.position_ids, task=self.task, inference_params=self.ip,
+                         num_last_tokens=1)
+        return (out.t2i_logits if self.task == "t2i" else out.mmu_logits).squeeze(1)
+
+    def run(self):
+        if self.graph is None:
+            return self._fwd()
+        self.graph.replay()
+        return self.logits
+
+
+def _pool_cache(model, max_batch, max_seqlen, task, cg):
+    """The slot pool and the per-bucket steps, kept on the model under the rule of generation.decode's `_decoding_cache`: a new device,
+    dtype or task, or a larger max_batch / max_length, drops them."""
+    p0 = next(iter(model.parameters()))
+    c = getattr(model, "_ragged_cache", None)
+    if (c is None or (c["device"], c["dtype"], c["task"], c["cg"]) != (p0.device, p0.dtype, task, cg)
+            or max_batch > c["max_batch"] or max_seqlen > c["max_seqlen"]):
+        c = {"device": p0.device, "dtype": p0.dtype, "task": task, "cg": cg, "max_batch": max_batch, "max_seqlen": max_seqlen,
+             "pool": model.allocate_inference_cache(max_batch, max_seqlen, p0.dtype), "buckets": {}, "prefill": {},
+             "mempool": torch.cuda.graphs.graph_pool_handle() if cg else None}
+        model._ragged_cache = None       # (the old pool and graphs go before the new ones are captured)
+        model._ragged_cache = c
+    return c
+
+
+def _prefill(model, c, slot, emb, task, cg):
+    """Batch-1 prefill of one prompt into pool slot `slot` -> logits (1, vocab).  Eager: straight into views of the slot.  Captured
+    (prompts of <= 512 positions, as generation.decode): a PrefillGraph per prompt length on a batch-1 cache of its own, whose states
+    are then copied into the slot."""
+    seqlen = emb.shape[1]
+    if cg and _prefill_graph_ok(seqlen):
+        key = (seqlen, emb.dtype)
+        pg = c["prefill"].get(key)
+        if pg is None:
+            if len(c["prefill"]) >= MAX_PREFILL_GRAPHS:
+                del c["prefill"][next(iter(c["prefill"]))]
+            ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=1,
+                                 key_value_memory_dict=model.allocate_inference_cache(1, c["max_seqlen"], c["dtype"]))
+            pg = PrefillGraph(model, ip, 1, seqlen, emb.shape[-1], task, emb.dtype, mempool=c["mempool"])
+        c["prefill"][key] = c["prefill"].pop(key, pg)          # most recently used last
+        lg = pg.run(emb)
+        src = [t for k in sorted(pg.ip.key_value_memory_dict) for t in pg.ip.key_value_memory_dict[k]]
+        dst = [t[slot:slot + 1] for k in sorted(c["pool"]) for t in c["pool"][k]]
+        torch._foreach_copy_(dst, src)
+        return lg
+    ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=1,
+                         key_value_memory_dict={k: tuple(t[slot:slot + 1] for t in v) for k, v in c["pool"].items()})
+    out = model(None, emb, position_ids=None, task=task, inference_params=ip, num_last_tokens=1)
+    return (out.t2i_logits if task == "t2i" else out.mmu_logits).squeeze(1)
+
+
+@torch.inference_mode()
+def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
+                  min_p=0.0, cg=True):
+    """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
+    generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
+    model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
+    past the position table (raised before that step is launched)."""
+    n = len(requests)
+    if n == 0:
+        return []
+    lens = [int(max_length)] * n if isinstance(max_length, int) else [int(m) for m in max_length]
+    if len(lens) != n:
+        raise ValueError(f"decode_ragged: {len(lens)} max_length values for {n} requests")
+    if max_batch < 1:
+        raise ValueError("decode_ragged: max_batch must be >= 1")
+    for ids, emb in requests:
+        if ids.dim() != 2 or ids.shape[0] != 1 or emb.dim() != 3 or emb.shape[0] != 1:
+            raise ValueError("decode_ragged: every request is (input_ids (1, L), input_embeddings (1, P, d))")
+    dev = requests[0][1].device
+    if hasattr(model, "prepare_decode"):
+        model.prepare_decode(task)
+    cfg_ = getattr(model, "cfg", None)
+    n_pos = None if cfg_ is None else getattr(cfg_, "t2i_positions" if task == "t2i" else "mmu_positions", None)
+    c = _pool_cache(model, max_batch, max(lens), task, cg)
+    buckets = _buckets(max_batch)
+
+    def bucket(nb):
+        if nb not in c["buckets"]:
+            c["buckets"][nb] = _Bucket(model, c["pool"], nb, c["max_seqlen"], task, cg, c["mempool"])
+        return c["buckets"][nb]
+
+    draw = lambda lg: sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+    last = torch.zeros(c["max_batch"], dtype=torch.long, device=dev)   # last sampled id of every slot: the next step's input
+    drawn, n_drawn = [], 0               # every sampled id tensor in order, and how many ids they hold
+    pieces = [[] for _ in range(n)]      # per request: the positions of its ids in cat(drawn), in sampling order
+    queue, free = deque(range(n)), list(range(max_batch))
+    live = []                            # rows of the step: [request, slot, offset]
+    check_eos = eos_token_id is not None
+
+    def finished(i, tok, off):
+        return (check_eos and tok == eos_token_id) or off >= lens[i] - 1
+
+    while queue or live:
+        while queue and free:                                  # admit FIFO into free slots
+            i = queue.popleft()
+            s = free.pop(0)
+            ids, emb = requests[i]
+            tok = draw(_prefill(model, c, s, emb, task, cg))   # (1,)
+            last[s:s + 1].copy_(tok)
+            drawn.append(tok)
+            pieces[i].append(n_drawn)
+            n_drawn += 1
+            off = emb.shape[1]
+            if finished(i, int(tok[0]) if check_eos else None, off):
+                free.append(s)
+            else:
+                live.append([i, s, off])
+        if not live:
+            continue
+        if n_pos is not None:
+            for i, _, off in live:
+                if off >= n_pos:
+                    raise IndexError(f"decode_ragged: position {off} of request {i} is outside the {task} position table of "
+                                     f"{n_pos} rows (StackConfig.{{t2i,mmu}}_positions)")
+        nb = next(b for b in buckets if b >= len(live))
+        bk = bucket(nb)
+        pad = nb - len(live)
+        slots_h = [s for _, s, _ in live]
+        rows = torch.tensor(slots_h + [0] * pad, dtype=torch.long).to(dev, non_blocking=True)
+        bk.input_ids[:, 0] = last.index_select(0, rows)
+        bk.position_ids.copy_(torch.tensor([[off] for _, _, off in live] + [[0]] * pad, dtype=torch.long), non_blocking=True)
+        bk.slots.copy_(torch.tensor(slots_h + [-1] * pad, dtype=torch.int32), non_blocking=True)
+        toks = draw(bk.run()[: len(live)])
+        last.index_copy_(0, rows[: len(live)], toks)
+        toks_h = toks.tolist() if check_eos else None
+        still = []
+        for r, row in enumerate(live):
+            i, s, off = row
+            row[2] = off = off + 1
+            pieces[i].append(n_drawn + r)
+            if finished(i, toks_h[r] if check_eos else None, off):
+                free.append(s)
+            else:
+                still.append(row)
+        drawn.append(toks)
+        n_drawn += len(live)
+        live = still
+    flat = torch.cat(drawn)
+    return [torch.cat([ids, flat[torch.tensor(pieces[i], device=dev)].view(1, -1).to(ids.device)], dim=1)
+            for i, (ids, _) in enumerate(requests)]

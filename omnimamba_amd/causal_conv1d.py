@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi as K
-from ._lib import get_lib, require_device
+from ._lib import get_lib, require_device, slot_indices
 
 
 def _act_flag(activation):
@@ -86,16 +86,20 @@ def causal_conv1d_fn(x, weight, bias=None, seq_idx=None, initial_states=None, re
 
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, cache_seqlens=None,
                          conv_state_indices=None):
-    """x: (batch, dim) or (batch, dim, seqlen); conv_state: (batch, dim, state_len >= width-1), updated in place."""
-    if cache_seqlens is not None or conv_state_indices is not None:
-        raise NotImplementedError("cache_seqlens / conv_state_indices are not on the OmniMamba path")
+    """x: (batch, dim) or (batch, dim, seqlen); conv_state: (batch, dim, state_len >= width-1), updated in place.
+    conv_state_indices: optional (batch,) int32 (int64 is cast: one extra launch): row b rolls conv_state row
+    conv_state_indices[b] of a pool with any number of rows; a negative index marks a padding row -- its state is neither read
+    nor written and its output is zeros.  The values are never read on the host (graph-capturable)."""
+    if cache_seqlens is not None:
+        raise NotImplementedError("cache_seqlens is not on the OmniMamba path")
     lib = get_lib()
-    require_device(lib, x, conv_state, weight, bias)
+    require_device(lib, x, conv_state, weight, bias, conv_state_indices)
+    idx = slot_indices(conv_state_indices, x.shape[0], x.device, "conv_state_indices")
     squeeze = x.dim() == 2
     x3 = x.unsqueeze(-1) if squeeze else x
     out = torch.empty_like(x3)
     if x3.numel() > 0:
         p = K.Conv1dUpdate(x=K.T(x3), conv_state=K.T(conv_state), weight=K.T(weight), bias=K.T(bias), out=K.T(out),
-                           silu=_act_flag(activation))
+                           silu=_act_flag(activation), conv_state_indices=K.T(idx))
         K.run(lib, "omk_causal_conv1d_update", p, x3)
     return out.squeeze(-1) if squeeze else out

@@ -784,17 +784,26 @@ __global__ void conv1d_dinit_kernel(ConvArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 struct ConvUpdArgs {
   const void* x; void* state; const void* w; const void* bias; void* out;
+  const int* csi;                        // ABI 8: slot of row b in the state pool (null: row b)
   int64_t xsb, xsc, xsl, ssb, ssc, ssl, osb, osc, osl, wsc, wsk;
-  int B, C, T, S, W, silu, xdt, sdt, wdt, bdt;
+  int B, C, T, S, W, silu, xdt, sdt, wdt, bdt, pool;
 };
 __global__ void conv1d_update_kernel(ConvUpdArgs a) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (int64_t)a.B * a.C) return;
   const int c = (int)(g % a.C), b = (int)(g / a.C);
+  int sb = b;
+  if (a.csi) {                           // slot of this row; negative or outside the pool: a padding row, no state traffic, zeros out
+    sb = a.csi[b];
+    if (sb < 0 || sb >= a.pool) {
+      for (int t = 0; t < a.T; t++) store_rt(a.out, (int64_t)b * a.osb + (int64_t)c * a.osc + (int64_t)t * a.osl, a.xdt, 0.f);
+      return;
+    }
+  }
   float w[CONV_MAXW], win[CONV_MAXW];
   for (int k = 0; k < CONV_MAXW; k++) w[k] = k < a.W ? load_rt(a.w, (int64_t)c * a.wsc + k * a.wsk, a.wdt) : 0.f;
   const float bias = a.bias ? load_rt(a.bias, c, a.bdt) : 0.f;
-  const int64_t sbase = (int64_t)b * a.ssb + (int64_t)c * a.ssc;
+  const int64_t sbase = (int64_t)sb * a.ssb + (int64_t)c * a.ssc;
   // window = last W-1 state entries
   for (int k = 0; k < CONV_MAXW; k++) win[k] = 0.f;
   for (int k = 0; k + 1 < a.W; k++) win[k] = load_rt(a.state, sbase + (int64_t)(a.S - (a.W - 1) + k) * a.ssl, a.sdt);
@@ -986,7 +995,11 @@ extern "C" int omk_causal_conv1d_update(const OmkConv1dUpdate* p, omk_stream str
   ConvUpdArgs a = {};
   a.B = (int)p->x.shape[0]; a.C = (int)p->x.shape[1]; a.T = (int)p->x.shape[2]; a.S = (int)p->conv_state.shape[2]; a.W = (int)p->weight.shape[1];
   OMK_REQUIRE(a.W >= 2 && a.W <= CONV_MAXW && a.S >= a.W - 1, "causal_conv1d_update: W in 2..4 and state_len >= W-1");
-  OMK_REQUIRE(p->conv_state.shape[0] == a.B && p->conv_state.shape[1] == a.C && p->weight.shape[0] == a.C, "causal_conv1d_update: shape mismatch");
+  // with slot indices conv_state is a pool of any number of rows
+  const bool indexed = present(p->conv_state_indices);
+  OMK_REQUIRE((indexed || p->conv_state.shape[0] == a.B) && p->conv_state.shape[1] == a.C && p->weight.shape[0] == a.C, "causal_conv1d_update: shape mismatch");
+  OMK_REQUIRE(indices_ok(p->conv_state_indices, a.B), "causal_conv1d_update: conv_state_indices must be contiguous int32 (B)");
+  a.csi = (const int*)p->conv_state_indices.data; a.pool = (int)p->conv_state.shape[0];
   OMK_REQUIRE(p->out.dtype == p->x.dtype, "causal_conv1d_update: out dtype");
   a.x = p->x.data; a.state = p->conv_state.data; a.w = p->weight.data; a.bias = p->bias.data; a.out = p->out.data;
   a.xsb = p->x.stride[0]; a.xsc = p->x.stride[1]; a.xsl = p->x.stride[2];

@@ -41,8 +41,17 @@ struct NlArgs {
   int B, In, Out, R, G, xdt, rdt, rodt, nwdt, bdt, odt, ldt, nbg;   // G = norm groups, nbg = norm_before_gate
   int nbatch;                                                        // templated variant: row batches per wave
   void* cst; const void* ccw; const void* ccb; int64_t csb, csc, csl, ccws; int cc0, cc1, cS, cW, csilu;   // conv tail (see omk.h)
+  const int* csi; int cpool;                                         // ABI 8: conv-state slot of sequence b (null: b), pool rows
   float eps, scale;
 };
+
+// conv-state row of sequence b: its slot in the pool, or -1 for a padding row (negative or out-of-pool index; no state traffic, zeros
+// in the conv columns).  Without slot indices: b.
+__device__ __forceinline__ int nl_slot(const NlArgs& a, int b) {
+  if (!a.csi) return b;
+  const int s = a.csi[b];
+  return (s >= 0 && s < a.cpool) ? s : -1;
+}
 
 // four consecutive elements of a runtime-typed array as floats (8- or 16-byte load)
 __device__ __forceinline__ void ld4_rt(const void* p, int64_t idx, int dt, float (&o)[4]) {
@@ -359,6 +368,8 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
   };
   const int frow_ = wg + lane * nwaves, frow = frow_ < a.Out ? frow_ : a.Out - 1;
   const bool conv_on = a.cst != nullptr;
+  const int cslot = conv_on ? nl_slot(a, 0) : 0;      // (one sequence: a uniform scalar load)
+  TW* const cst = conv_on ? (TW*)a.cst + (int64_t)(cslot >= 0 ? cslot : 0) * a.csb : nullptr;   // (padding: row 0, read and not used)
   uint32_t q_lb[RMAX > 0 ? RMAX : 1], q_wt[4], q_hist[3], q_cb, q_bias = 0u;
   {
     if constexpr (RMAX > 0) {
@@ -371,7 +382,7 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
     if (a.bias) q_bias = rawld((const TW*)a.bias + frow);                           // (uniform; the projections of the model have none)
     const int convC = a.cc1 - a.cc0, c_ = frow - a.cc0, ch = c_ < 0 ? 0 : (c_ < convC ? c_ : convC - 1);
     const TW* wr_ = conv_on ? (const TW*)a.ccw + (int64_t)ch * a.ccws : W;
-    const TW* cs = conv_on ? (const TW*)a.cst + (int64_t)ch * a.csc : W;
+    const TW* cs = conv_on ? cst + (int64_t)ch * a.csc : W;
     const int64_t csl = conv_on ? a.csl : 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int col = k - (4 - a.cW); q_wt[k] = rawld(wr_ + (col >= 0 ? col : 0)); }
@@ -418,10 +429,12 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
     }
     vv *= rstd;
     if (a.bias) vv += rawf(q_bias);
-    if (conv_on && row >= a.cc0 && row < a.cc1) {
+    if (conv_on && row >= a.cc0 && row < a.cc1 && cslot < 0) {
+      vv = 0.f;                                               // padding sequence: its conv columns are zeros, its state is not touched
+    } else if (conv_on && row >= a.cc0 && row < a.cc1) {
       // this row is a new xBC input: causal_conv1d_update for its channel, right here (no other lane touches it)
       const int ch = row - a.cc0;
-      TW* cs = (TW*)a.cst + (int64_t)ch * a.csc;
+      TW* cs = cst + (int64_t)ch * a.csc;
       float hist[3], wt[4];
 #pragma unroll
       for (int k = 0; k < 3; k++) hist[k] = rawf(q_hist[k]);
@@ -653,10 +666,13 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
     // every load of the tail first (sequences past B clamp to the last one), then the arithmetic, stores last: with the
     // loads inside a per-sequence branch each sequence costs its own round trip
     float hist[NB][3], vout[NB], xin[NB];
+    int cslot[NB];                                              // conv-state slots: uniform scalar loads (-1: padding sequence)
+#pragma unroll
+    for (int b = 0; b < NB; b++) cslot[b] = a.cst ? nl_slot(a, b < a.B ? b : a.B - 1) : 0;
     if (isconv) {
 #pragma unroll
       for (int b = 0; b < NB; b++) {
-        const TW* cs = (const TW*)a.cst + (int64_t)(b < a.B ? b : a.B - 1) * a.csb + (int64_t)ch * a.csc;
+        const TW* cs = (const TW*)a.cst + (int64_t)(cslot[b] >= 0 ? cslot[b] : 0) * a.csb + (int64_t)ch * a.csc;
 #pragma unroll
         for (int k = 0; k < 3; k++) { const int sl = a.cS - 3 + k; hist[b][k] = to_f32(cs[(int64_t)(sl >= 0 ? sl : 0) * a.csl]); }
       }
@@ -682,15 +698,15 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
       xin[b] = to_f32(from_f32<TW>(vv));
       if (isconv) {
         const float cv = cbias + wt[0] * hist[b][0] + wt[1] * hist[b][1] + wt[2] * hist[b][2] + wt[3] * xin[b];
-        vv = a.csilu ? silu_f(cv) : cv;
+        vv = cslot[b] < 0 ? 0.f : (a.csilu ? silu_f(cv) : cv);
       }
       vout[b] = vv;
     }
 #pragma unroll
     for (int b = 0; b < NB; b++) {
       if (b < a.B) {
-        if (isconv) {
-          TW* cs = (TW*)a.cst + (int64_t)b * a.csb + (int64_t)ch * a.csc;
+        if (isconv && cslot[b] >= 0) {
+          TW* cs = (TW*)a.cst + (int64_t)cslot[b] * a.csb + (int64_t)ch * a.csc;
           for (int sl = 0; sl + 1 < a.cS; sl++) {
             const int k = sl + 1 - (a.cS - 3);
             cs[(int64_t)sl * a.csl] = from_f32<TW>(k == 0 ? hist[b][0] : (k == 1 ? hist[b][1] : hist[b][2]));
@@ -780,6 +796,8 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   struct Fin { uint32_t lbq[LBR]; uint32_t hist[3], wt[4], cbias, bias; };   // (one register per value: 16-bit members get packed -- a wait)
   const bool conv_on = a.cst != nullptr;
   const int convC = a.cc1 - a.cc0;
+  // conv-state slot of the sequence this thread finishes, loaded once (-1: padding sequence -- row 0 is read and not used)
+  const int fslot = conv_on ? nl_slot(a, fb < a.B ? fb : a.B - 1) : 0;
   auto load_w = [&](u32x4 (&w)[NLD], int t) {
     const int rt = ROWS * t + (t16 & (ROWS - 1));
     const TW* wp = (const TW*)a.W + (int64_t)(rt < a.Out ? rt : a.Out - 1) * a.Ws + wave * KPW + VEC * g16;
@@ -802,7 +820,7 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
     f.bias = a.bias ? raw16((const TW*)a.bias + frow) : 0u;   // (the projections of the model have none: a uniform branch)
     const int c_ = frow - a.cc0, ch = c_ < 0 ? 0 : (c_ < convC ? c_ : convC - 1);
     const TW* wr_ = conv_on ? (const TW*)a.ccw + (int64_t)ch * a.ccws : (const TW*)a.W;
-    const TW* cs = conv_on ? (const TW*)a.cst + (int64_t)fbc * a.csb + (int64_t)ch * a.csc : (const TW*)a.W;
+    const TW* cs = conv_on ? (const TW*)a.cst + (int64_t)(fslot >= 0 ? fslot : 0) * a.csb + (int64_t)ch * a.csc : (const TW*)a.W;
     const int64_t csl = conv_on ? a.csl : 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int col = k - (4 - a.cW); f.wt[k] = raw16(wr_ + (col >= 0 ? col : 0)); }
@@ -952,14 +970,18 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
         for (int k = 0; k < 4; k++) wt[k] = k - (4 - a.cW) >= 0 ? f16(fc.wt[k]) : 0.f;
         const float cv = (a.ccb ? f16(fc.cbias) : 0.f) + wt[0] * f16(fc.hist[0]) + wt[1] * f16(fc.hist[1]) + wt[2] * f16(fc.hist[2]) + wt[3] * xin;
         vv = a.csilu ? silu_f(cv) : cv;
-        TW* cs = (TW*)a.cst + (int64_t)fb * a.csb + (int64_t)(frow - a.cc0) * a.csc;
-        for (int sl = 0; sl + 1 < a.cS; sl++) {      // roll: the stored values move as they are
-          const int k = sl + 1 - (a.cS - 3);
-          const uint32_t hq = k == 0 ? fc.hist[0] : (k == 1 ? fc.hist[1] : fc.hist[2]);
-          if constexpr (W32) cs[(int64_t)sl * a.csl] = __builtin_bit_cast(TW, hq);
-          else cs[(int64_t)sl * a.csl] = __builtin_bit_cast(TW, (uint16_t)hq);
+        if (fslot < 0) {
+          vv = 0.f;                                  // padding sequence: zeros in its conv columns, its state is not touched
+        } else {
+          TW* cs = (TW*)a.cst + (int64_t)fslot * a.csb + (int64_t)(frow - a.cc0) * a.csc;
+          for (int sl = 0; sl + 1 < a.cS; sl++) {    // roll: the stored values move as they are
+            const int k = sl + 1 - (a.cS - 3);
+            const uint32_t hq = k == 0 ? fc.hist[0] : (k == 1 ? fc.hist[1] : fc.hist[2]);
+            if constexpr (W32) cs[(int64_t)sl * a.csl] = __builtin_bit_cast(TW, hq);
+            else cs[(int64_t)sl * a.csl] = __builtin_bit_cast(TW, (uint16_t)hq);
+          }
+          cs[(int64_t)(a.cS - 1) * a.csl] = xr;
         }
-        cs[(int64_t)(a.cS - 1) * a.csl] = xr;
       }
       ((TW*)a.out)[(int64_t)fb * a.os + frow] = from_f32<TW>(vv);
     }
@@ -996,6 +1018,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
   a.B = (int)p->x.shape[0]; a.In = (int)p->x.shape[1]; a.Out = (int)p->weight.shape[0];
   OMK_REQUIRE(p->weight.shape[1] == a.In && p->out.shape[0] == a.B && p->out.shape[1] == a.Out, "norm_linear: shape mismatch");
   OMK_REQUIRE(p->x.stride[1] == 1 && p->out.stride[1] == 1 && p->weight.stride[1] == 1, "norm_linear: last dims must be contiguous");
+  OMK_REQUIRE(!present(p->conv_state_indices) || present(p->conv_state), "norm_linear: conv_state_indices need conv_state");
   if (a.B == 0 || a.Out == 0) return OMK_OK;
   // up to eight sequences per call (norm_linear_batched_kernel); more than that goes to the separate ops
   if (a.B > 8) return fail(OMK_EUNSUPPORTED, "norm_linear: batch %d > 8 is served by the unfused ops", a.B);
@@ -1051,7 +1074,11 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       OMK_REQUIRE(present(p->conv_weight) && p->conv_state.ndim == 3 && p->conv_weight.ndim == 2, "norm_linear: conv_state (B, C, S) needs conv_weight (C, W)");
       const int64_t Cc = p->conv_state.shape[1];
       a.cS = (int)p->conv_state.shape[2]; a.cW = (int)p->conv_weight.shape[1];
-      OMK_REQUIRE(p->conv_state.shape[0] == a.B, "norm_linear: conv_state batch");
+      // with slot indices conv_state is a pool of any (non-zero) number of rows
+      const bool indexed = present(p->conv_state_indices);
+      OMK_REQUIRE(indexed ? p->conv_state.shape[0] > 0 : p->conv_state.shape[0] == a.B, "norm_linear: conv_state batch");
+      OMK_REQUIRE(indices_ok(p->conv_state_indices, a.B), "norm_linear: conv_state_indices must be contiguous int32 (B)");
+      a.csi = (const int*)p->conv_state_indices.data; a.cpool = (int)p->conv_state.shape[0];
       OMK_REQUIRE(p->conv_weight.shape[0] == Cc && p->conv_offset >= 0 && p->conv_offset + Cc <= a.Out, "norm_linear: conv channels must be rows [conv_offset, conv_offset + C) of the output");
       const bool cok = fast && a.cW >= 2 && a.cW <= 4 && a.cS >= a.cW - 1 && a.cS <= 4 && p->conv_state.dtype == wdt && p->conv_weight.dtype == wdt &&
                        p->conv_weight.stride[1] == 1 && (!present(p->conv_bias) || (p->conv_bias.dtype == wdt && is_contig_last(p->conv_bias) && numel(p->conv_bias) == Cc));

@@ -35,8 +35,12 @@ inline bool is_dense(const OmkTensor& t) {
   }
   return true;
 }
-inline size_t dtype_size(int dt) { return dt == OMK_F32 ? 4 : dt == OMK_U8 ? 1 : 2; }
+inline size_t dtype_size(int dt) { return (dt == OMK_F32 || dt == OMK_I32) ? 4 : dt == OMK_U8 ? 1 : 2; }
 inline bool aligned16(const OmkTensor& t) { return ((uintptr_t)t.data & 15) == 0; }
+// ABI 8 slot indices (state_batch_indices / conv_state_indices): absent, or contiguous int32 (B).  The values are never read on the host.
+inline bool indices_ok(const OmkTensor& t, int64_t B) {
+  return !present(t) || (t.dtype == OMK_I32 && t.ndim == 1 && t.shape[0] == B && (B == 1 || t.stride[0] == 1));
+}
 // every stride except the last is a multiple of `elems` (so 16-byte vector rows stay aligned)
 inline bool strides_multiple_of(const OmkTensor& t, int64_t elems) {
   for (int i = 0; i + 1 < t.ndim; i++)

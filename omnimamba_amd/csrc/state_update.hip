@@ -12,10 +12,19 @@ namespace omk {
 struct SuArgs {
   void* state; const void* x; const void* dt; const void* A; const void* Bm; const void* Cm; const void* D; const void* z;
   const void* dtb; void* out;
+  const int* sbi;                                     // ABI 8: slot of row b in the state pool (null: row b), pool rows
   int64_t ssb, ssh, ssp, ssn, xsb, xsh, xsp, dsb, dsh, dsp, ash, asp, asn, bsb, bsg, bsn, csb, csg, csn;
   int64_t Dsh, Dsp, zsb, zsh, zsp, tsh, tsp, osb, osh, osp;
-  int B, H, P, N, G, softplus, xdt, dtdt, adt, ddt, tbdt;
+  int B, H, P, N, G, softplus, xdt, dtdt, adt, ddt, tbdt, pool;
 };
+
+// the state row of batch row b: its slot in the pool, or -1 for a padding row (negative or out-of-pool index).  b is
+// workgroup-uniform, so this is one scalar load in front of the state address, and a padding row leaves the workgroup as a whole.
+__device__ __forceinline__ int su_slot(const SuArgs& a, int b) {
+  if (!a.sbi) return b;
+  const int s = a.sbi[b];
+  return (s >= 0 && s < a.pool) ? s : -1;
+}
 
 template <class TS, class TX, int VEC, int LPR>
 __global__ __launch_bounds__(256) void state_update_kernel(SuArgs a) {
@@ -29,6 +38,11 @@ __global__ __launch_bounds__(256) void state_update_kernel(SuArgs a) {
   const bool live = p < a.P;
   const int pp = live ? p : a.P - 1;                 // keep every lane in the shuffles
   const int g = h / (a.H / a.G);
+  const int sb = su_slot(a, b);
+  if (sb < 0) {                                      // padding row: no state traffic, zeros out
+    if (live && lr == 0) store_rt(a.out, (int64_t)b * a.osb + (int64_t)h * a.osh + (int64_t)p * a.osp, a.xdt, 0.f);
+    return;
+  }
   // every independent load first: the scalars of the row and (vector path, N <= LPR * VEC: one step) its state / B / C
   // (requests first, conversions behind the last request: raw_rt_flat / cvt_rt_flat in omk_common.h; D and the gate of the row ride along
   // from clamped / dummy addresses instead of sitting under branches behind the reduction)
@@ -39,7 +53,7 @@ __global__ __launch_bounds__(256) void state_update_kernel(SuArgs a) {
   const RawElem q_A = raw_rt_flat(a.A, (int64_t)h * a.ash + (int64_t)pp * a.asp, a.adt);
   const RawElem q_D = raw_rt_flat(a.D ? a.D : a.A, a.D ? (int64_t)h * a.Dsh + (int64_t)pp * a.Dsp : 0, a.D ? a.ddt : a.adt);
   const RawElem q_z = raw_rt_flat(a.z ? a.z : a.x, a.z ? (int64_t)b * a.zsb + (int64_t)h * a.zsh + (int64_t)pp * a.zsp : 0, a.xdt);
-  TS* s = (TS*)a.state + (int64_t)b * a.ssb + (int64_t)h * a.ssh + (int64_t)pp * a.ssp;
+  TS* s = (TS*)a.state + (int64_t)sb * a.ssb + (int64_t)h * a.ssh + (int64_t)pp * a.ssp;
   const TX* Bp = (const TX*)a.Bm + (int64_t)b * a.bsb + (int64_t)g * a.bsg;
   const TX* Cp = (const TX*)a.Cm + (int64_t)b * a.csb + (int64_t)g * a.csg;
   float sv0[VEC], bv0[VEC], cv0[VEC];
@@ -102,7 +116,15 @@ __global__ __launch_bounds__(256) void state_update_tied_kernel(SuArgs a) {
   const int pb = blockIdx.x % pblocks, h = (blockIdx.x / pblocks) % a.H, b = blockIdx.x / (pblocks * a.H);
   const int g = h / (a.H / a.G);
   const int p0 = pb * RPB * RPT + wave * RPW + rw, n0 = lr * VEC;
-  TS* s = (TS*)a.state + (int64_t)b * a.ssb + (int64_t)h * a.ssh + n0;
+  const int sb = su_slot(a, b);
+  if (sb < 0) {                                                // padding row: no state traffic, zeros out
+    if (lr == 0) {
+#pragma unroll
+      for (int k = 0; k < RPT; k++) ((TX*)a.out)[(int64_t)b * a.osb + (int64_t)h * a.osh + (int64_t)(p0 + k * RPB) * a.osp] = from_f32<TX>(0.f);
+    }
+    return;
+  }
+  TS* s = (TS*)a.state + (int64_t)sb * a.ssb + (int64_t)h * a.ssh + n0;
   float sv[RPT][VEC], xv[RPT], bv[VEC], cv[VEC];
 #pragma unroll
   for (int k = 0; k < RPT; k++) load_vec<TS, VEC>(s + (int64_t)(p0 + k * RPB) * a.ssp, sv[k]);
@@ -169,7 +191,12 @@ extern "C" int omk_selective_state_update(const OmkStateUpdate* p, omk_stream st
   OMK_REQUIRE(p->state.ndim == 4 && p->x.ndim == 3 && p->dt.ndim == 3 && p->A.ndim == 3 && p->Bm.ndim == 3 && p->Cm.ndim == 3 && p->out.ndim == 3,
               "selective_state_update: state (B,H,P,N), x/dt/out (B,H,P), A (H,P,N), B/C (B,G,N)");
   SuArgs a = {};
-  a.B = (int)p->state.shape[0]; a.H = (int)p->state.shape[1]; a.P = (int)p->state.shape[2]; a.N = (int)p->state.shape[3]; a.G = (int)p->Bm.shape[1];
+  // with slot indices the state is a pool of any number of rows and the batch is x's; without, they are one and the same
+  const bool indexed = present(p->state_batch_indices);
+  a.B = (int)(indexed ? p->x.shape[0] : p->state.shape[0]); a.pool = (int)p->state.shape[0];
+  a.H = (int)p->state.shape[1]; a.P = (int)p->state.shape[2]; a.N = (int)p->state.shape[3]; a.G = (int)p->Bm.shape[1];
+  OMK_REQUIRE(indices_ok(p->state_batch_indices, a.B), "selective_state_update: state_batch_indices must be contiguous int32 (B)");
+  a.sbi = (const int*)p->state_batch_indices.data;
   OMK_REQUIRE(a.G > 0 && a.H % a.G == 0, "selective_state_update: H must be a multiple of ngroups");
   OMK_REQUIRE(p->x.shape[0] == a.B && p->x.shape[1] == a.H && p->x.shape[2] == a.P, "selective_state_update: x shape");
   OMK_REQUIRE(p->Bm.shape[0] == a.B && p->Bm.shape[2] == a.N && p->Cm.shape[1] == a.G && p->Cm.shape[2] == a.N, "selective_state_update: B/C shape");

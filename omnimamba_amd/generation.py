@@ -23,6 +23,9 @@ class InferenceParams:
     batch_size_offset: int = 0
     key_value_memory_dict: dict = field(default_factory=dict)
     lengths_per_sample: Optional[torch.Tensor] = None
+    # continuous batching (omnimamba_amd/batch_decode.py): int32 (batch,) slot of each step row in the cache's state pool, -1 = an empty
+    # row.  Set, the decode step reads and writes pool rows through it; None, row b is cache row b as before.
+    state_indices: Optional[torch.Tensor] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen

@@ -115,7 +115,7 @@ class Mamba2(nn.Module):
         if inference_params is not None:
             conv_state, ssm_state = self._get_states_from_cache(inference_params, batch)
             if inference_params.seqlen_offset > 0:
-                out, _, _ = self.step(u, conv_state, ssm_state)
+                out, _, _ = self.step(u, conv_state, ssm_state, state_indices=getattr(inference_params, "state_indices", None))
                 return out
             if not torch.is_grad_enabled():
                 self._A_inference()   # prefill: bring the step's persistent -exp(A_log) buffer up to date (graph replays read it)
@@ -228,21 +228,23 @@ class Mamba2(nn.Module):
         self._A_ver = self.A_log._version
         return buf
 
-    def step(self, hidden_states, conv_state, ssm_state):
-        """hidden_states: (batch, 1, d_model); both states updated in place. -> (out (batch, 1, d_model), conv, ssm)"""
+    def step(self, hidden_states, conv_state, ssm_state, state_indices=None):
+        """hidden_states: (batch, 1, d_model); both states updated in place. -> (out (batch, 1, d_model), conv, ssm)
+        state_indices: optional int32 (batch,): row b steps pool row state_indices[b] of conv_state / ssm_state (-1: empty row)."""
         assert hidden_states.shape[1] == 1, "Only support decoding with 1 token at a time for now"
         zxbcdt = self.in_proj(hidden_states.squeeze(1))
-        return self.step_from_zxbcdt(zxbcdt, conv_state, ssm_state).unsqueeze(1), conv_state, ssm_state
+        return self.step_from_zxbcdt(zxbcdt, conv_state, ssm_state, state_indices=state_indices).unsqueeze(1), conv_state, ssm_state
 
-    def step_from_zxbcdt(self, zxbcdt, conv_state, ssm_state, conv_done=False):
+    def step_from_zxbcdt(self, zxbcdt, conv_state, ssm_state, conv_done=False, state_indices=None):
         """The decode step after in_proj: zxbcdt (batch, d_in_proj) -> out (batch, d_model).  Split out so that callers
         which fuse the block's pre-norm into the in_proj GEMV (stack.ResidualBlock) can enter here; conv_done: the xBC
-        columns already went through the convolution update (norm_linear's conv tail)."""
+        columns already went through the convolution update (norm_linear's conv tail).  state_indices: see step."""
         d_mlp = (zxbcdt.shape[-1] - 2 * self.d_ssm - 2 * self.ngroups * self.d_state - self.nheads) // 2
         z0, x0, z, xBC, dt = torch.split(
             zxbcdt, [d_mlp, d_mlp, self.d_ssm, self.d_ssm + 2 * self.ngroups * self.d_state, self.nheads], dim=-1)
         if not conv_done:
-            xBC = causal_conv1d_update(xBC, conv_state, self.conv1d.weight.squeeze(1), self.conv1d.bias, self.activation)
+            xBC = causal_conv1d_update(xBC, conv_state, self.conv1d.weight.squeeze(1), self.conv1d.bias, self.activation,
+                                       conv_state_indices=state_indices)
         x, B, C = torch.split(xBC, [self.d_ssm, self.ngroups * self.d_state, self.ngroups * self.d_state], dim=-1)
         A = self._A_inference()
         H, P, N = self.nheads, self.headdim, self.d_state
@@ -254,7 +256,7 @@ class Mamba2(nn.Module):
         D_e = self.D.view(H, P) if self.D_has_hdim else self.D[:, None].expand(H, P)
         y = selective_state_update(ssm_state, x.view(batch, H, P), dt_e, A_e, B.view(batch, self.ngroups, N),
                                    C.view(batch, self.ngroups, N), D_e, z=z.view(batch, H, P) if not self.rmsnorm else None,
-                                   dt_bias=dt_bias_e, dt_softplus=True)
+                                   dt_bias=dt_bias_e, dt_softplus=True, state_batch_indices=state_indices)
         y = y.reshape(batch, H * P)
         if (self.rmsnorm and d_mlp == 0 and type(self.out_proj) is nn.Linear and self.norm.bias is None
                 and NL.applies(y, self.out_proj.weight, self.norm.weight, z, self.out_proj.bias)):
@@ -278,6 +280,7 @@ class Mamba2(nn.Module):
         return conv_state, ssm_state
 
     def _get_states_from_cache(self, inference_params, batch_size, initialize_states=False):
+        """(conv_state, ssm_state) of this layer; with ``inference_params.state_indices`` set they are the whole slot pool."""
         assert self.layer_idx is not None
         if self.layer_idx not in inference_params.key_value_memory_dict:
             conv_state, ssm_state = self.allocate_inference_cache(batch_size, 0)

@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi as K
-from ._lib import get_lib, require_device
+from ._lib import get_lib, require_device, slot_indices
 
 MAX_BATCH = 8     # sequences per call; larger decode batches take the separate ops
 
@@ -39,7 +39,8 @@ def applies(x: torch.Tensor, weight: torch.Tensor, norm_weight=None, *same_dtype
 
 
 def conv_tail_applies(x, weight, norm_weight, conv_state, conv_weight, conv_bias, lora_a=None, bias=None, residual=None) -> bool:
-    """Whether `norm_linear(..., conv_state=...)` is served (the uniform-dtype kernel: fp32 or bf16 everywhere)."""
+    """Whether `norm_linear(..., conv_state=...)` is served (the uniform-dtype kernel: fp32 or bf16 everywhere).  conv_state may be
+    a pool with more rows than x has sequences (addressed through `conv_state_indices`)."""
     dt = weight.dtype
     same = lambda t: t is None or t.dtype == dt
     W, S = conv_weight.shape[-1], conv_state.shape[-1]
@@ -51,13 +52,19 @@ def conv_tail_applies(x, weight, norm_weight, conv_state, conv_weight, conv_bias
 
 def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=None, residual_out_dtype=None, z=None,
                 group_size=None, norm_before_gate=False, lora_a=None, lora_b=None, lora_scale=0.0, out_dtype=None,
-                conv_state=None, conv_weight=None, conv_bias=None, conv_offset=0, conv_silu=True):
+                conv_state=None, conv_weight=None, conv_bias=None, conv_offset=0, conv_silu=True, conv_state_indices=None):
     """out = norm(x [+ residual] | gated by z) @ weight^T [+ bias] [+ lora_scale * (n @ lora_a^T) @ lora_b^T].
     x: (B, in).  Returns out, or (out, residual_out) when `residual_out_dtype` is given (residual_out = x + residual).
     conv_state (B, C, S) + conv_weight (C, W): output columns [conv_offset, conv_offset + C) additionally go through
-    causal_conv1d_update (+ SiLU): out holds the convolved values and conv_state is rolled in place."""
+    causal_conv1d_update (+ SiLU): out holds the convolved values and conv_state is rolled in place.
+    conv_state_indices (B,) int32 (int64 is cast: one extra launch): sequence b rolls conv_state row conv_state_indices[b] of a pool
+    with any number of rows; a negative index marks a padding sequence -- its conv state is neither read nor written and its conv
+    columns of out are zeros.  The values are never read on the host."""
     lib = get_lib()
-    require_device(lib, x, weight, bias, norm_weight, residual, z, lora_a, lora_b, conv_state, conv_weight, conv_bias)
+    require_device(lib, x, weight, bias, norm_weight, residual, z, lora_a, lora_b, conv_state, conv_weight, conv_bias, conv_state_indices)
+    if conv_state_indices is not None and conv_state is None:
+        raise ValueError("conv_state_indices need conv_state")
+    idx = slot_indices(conv_state_indices, x.shape[0], x.device, "conv_state_indices")
     if x.stride(-1) != 1:
         x = x.contiguous()
     if z is not None and (z.dtype != x.dtype or z.stride(-1) != 1):
@@ -69,6 +76,7 @@ def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=No
                      lora_a=K.T(lora_a), lora_b=K.T(lora_b), residual_out=K.T(ro), out=K.T(out),
                      conv_state=K.T(conv_state), conv_weight=K.T(conv_weight), conv_bias=K.T(conv_bias),
                      group_size=0 if group_size is None else int(group_size), conv_offset=int(conv_offset), eps=float(eps),
-                     lora_scale=float(lora_scale), norm_before_gate=int(bool(norm_before_gate)), conv_silu=int(bool(conv_silu)))
+                     lora_scale=float(lora_scale), norm_before_gate=int(bool(norm_before_gate)), conv_silu=int(bool(conv_silu)),
+                     conv_state_indices=K.T(idx))
     K.run(lib, "omk_norm_linear", p, x)
     return out if ro is None else (out, ro)

@@ -185,18 +185,36 @@ class OmniMambaPath(nn.Module):
         return zq.reshape(shape[0], shape[2], shape[3], shape[1]).permute(0, 3, 1, 2).contiguous()
 
     # ---- MMU generation (scripts/inference_mmu.py:55-95: the prompt the script assembles by hand, then mamba.generate)
+    def _mmu_prompt(self, images_feat, input_ids):
+        """(prompt ids (B, 4 + T), prompt embeddings (B, 4 + n_img + T, d)) of <|mmu|> <|soi|> [projector(images_feat)] <|eoi|> <|sot|>
+        question ids."""
+        ids = torch.cat([self._sp("<|mmu|>", input_ids), self._sp("<|soi|>", input_ids), self._sp("<|eoi|>", input_ids),
+                         self._sp("<|sot|>", input_ids), input_ids], dim=1)
+        txt = self.llm_backbone.embed_input_ids(ids)
+        img = self.projector(images_feat).to(txt.dtype)
+        return ids, torch.cat((txt[:, :2], img, txt[:, 2:]), dim=1)
+
     @torch.no_grad()
     def mmu_generate(self, images_feat, input_ids, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1, top_p=0.0, cg=True):
         """<|mmu|> <|soi|> [projector(images_feat)] <|eoi|> <|sot|> question ids -> the reference's greedy continuation.  Returns the
         token matrix the script decodes: the 4 + len(question) prompt ids followed by the generated ids (the image positions carry no
         ids, as in the script)."""
-        ids = torch.cat([self._sp("<|mmu|>", input_ids), self._sp("<|soi|>", input_ids), self._sp("<|eoi|>", input_ids),
-                         self._sp("<|sot|>", input_ids), input_ids], dim=1)
-        txt = self.llm_backbone.embed_input_ids(ids)
-        img = self.projector(images_feat).to(txt.dtype)
-        emb = torch.cat((txt[:, :2], img, txt[:, 2:]), dim=1)
+        ids, emb = self._mmu_prompt(images_feat, input_ids)
         return self.llm_backbone.mamba.generate(input_ids=ids, input_embeddings=emb, cond=None, eos_token_id=eos_token_id, max_length=max_length,
                                                 temperature=temperature, top_p=top_p, top_k=top_k, cg=cg, task="mmu")
+
+    @torch.no_grad()
+    def mmu_generate_batch(self, images_feat_list, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1,
+                           top_p=0.0, max_batch=8, cg=True):
+        """Many MMU requests at once (continuous batching, omnimamba_amd/batch_decode.py): request i is images_feat_list[i] (1, n_img,
+        fused_vision_dim) with the question input_ids_list[i] (1, T_i), its prompt built as in mmu_generate.  max_length: an int or one
+        per request.  Returns one id tensor per request, each equal to what mmu_generate returns for that request alone."""
+        from .batch_decode import decode_ragged
+        if len(images_feat_list) != len(input_ids_list):
+            raise ValueError("mmu_generate_batch: one images_feat per question")
+        reqs = [self._mmu_prompt(f, q) for f, q in zip(images_feat_list, input_ids_list)]
+        return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
+                             top_k=top_k, top_p=top_p, temperature=temperature, cg=cg)
 
     # ---- T2I generation (omnimamba.py:311-337 minus the VQ decoder network)
     @torch.no_grad()

@@ -9,18 +9,20 @@ from __future__ import annotations
 import torch
 
 from . import _capi as K
-from ._lib import get_lib, require_device
+from ._lib import get_lib, require_device, slot_indices
 
 
 def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False,
                            state_batch_indices=None):
     """state: (batch, dim, dstate) or (batch, nheads, dim, dstate), updated IN PLACE.
     x, dt, z: (batch, dim) or (batch, nheads, dim); A: (dim, dstate) or (nheads, dim, dstate);
-    B, C: (batch, dstate) or (batch, ngroups, dstate); D, dt_bias: (dim) or (nheads, dim).  Returns out like x."""
-    if state_batch_indices is not None:
-        raise NotImplementedError("state_batch_indices is not on the OmniMamba path")
+    B, C: (batch, dstate) or (batch, ngroups, dstate); D, dt_bias: (dim) or (nheads, dim).  Returns out like x.
+    state_batch_indices: optional (batch,) int32 (int64 is cast: one extra launch): row b uses state row
+    state_batch_indices[b] of a pool with any number of rows; a negative index marks a padding row -- its state is neither
+    read nor written and its output is zeros.  The values are never read on the host (graph-capturable)."""
     lib = get_lib()
-    require_device(lib, state, x, dt, A, B, C, D, z, dt_bias)
+    require_device(lib, state, x, dt, A, B, C, D, z, dt_bias, state_batch_indices)
+    idx = slot_indices(state_batch_indices, x.shape[0], x.device, "state_batch_indices")
     has_heads = state.dim() > 3
     if not has_heads:
         state_v, x_v, dt_v, A_v = state.unsqueeze(1), x.unsqueeze(1), dt.unsqueeze(1), A.unsqueeze(0)
@@ -39,6 +41,6 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     out = torch.empty_like(x_v)
     if x_v.numel() > 0:
         p = K.StateUpdate(state=K.T(state_v), x=K.T(x_v), dt=K.T(dt_v), A=K.T(A_v), Bm=K.T(B_v), Cm=K.T(C_v), D=K.T(D_v),
-                          z=K.T(z_v), dt_bias=K.T(tb_v), out=K.T(out), dt_softplus=int(dt_softplus))
+                          z=K.T(z_v), dt_bias=K.T(tb_v), out=K.T(out), dt_softplus=int(dt_softplus), state_batch_indices=K.T(idx))
         K.run(lib, "omk_selective_state_update", p, x_v)
     return out if has_heads else out.squeeze(1)

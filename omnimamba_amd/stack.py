@@ -240,6 +240,7 @@ class ResidualBlock(nn.Module):
             return None
         ro_dtype = torch.float32 if (self.residual_in_fp32 or (residual is not None and residual.dtype == torch.float32)) else x2.dtype
         conv_state, ssm_state = self.mixer._get_states_from_cache(inference_params, x2.shape[0])
+        slots = getattr(inference_params, "state_indices", None)
         res2 = None if residual is None else residual.squeeze(1)
         m, conv = self.mixer, {}
         cw = m.conv1d.weight.squeeze(1)
@@ -247,10 +248,11 @@ class ResidualBlock(nn.Module):
         if (m.activation in ("silu", "swish") and os.environ.get("OMK_DECODE_CONV_SEPARATE") != "1"
                 and NL.conv_tail_applies(x2, ip.weight, self.norm.weight, conv_state, cw, m.conv1d.bias, lora.get("lora_a"), ip.bias, res2)):
             # the convolution of the new xBC inputs rides on the in_proj launch (one launch less per layer-step)
-            conv = dict(conv_state=conv_state, conv_weight=cw, conv_bias=m.conv1d.bias, conv_offset=2 * d_mlp + m.d_ssm)
+            conv = dict(conv_state=conv_state, conv_weight=cw, conv_bias=m.conv1d.bias, conv_offset=2 * d_mlp + m.d_ssm,
+                        conv_state_indices=slots)
         zxbcdt, new_res = NL.norm_linear(x2, ip.weight, ip.bias, norm_weight=self.norm.weight, eps=self.norm.eps,
                                          residual=res2, residual_out_dtype=ro_dtype, **lora, **conv)
-        out = self.mixer.step_from_zxbcdt(zxbcdt, conv_state, ssm_state, conv_done=bool(conv))
+        out = self.mixer.step_from_zxbcdt(zxbcdt, conv_state, ssm_state, conv_done=bool(conv), state_indices=slots)
         return out.unsqueeze(1), new_res.unsqueeze(1)
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):

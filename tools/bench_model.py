@@ -1,5 +1,5 @@
 """BASELINE.json configs[2..4] on the synthetic OmniMamba-1.3B stack (random init, synthetic data), 1 GPU or N GPUs via
-torch.distributed.run:   python tools/bench_model.py [decode|train] [--batch B] [--seqlen L] [--steps K]
+torch.distributed.run:   python tools/bench_model.py [decode|train|decode_mmu_batch|step_index_cost] [--batch B] [--seqlen L] [--steps K]
 Prints one JSON line per workload (rank 0)."""
 import argparse
 import json
@@ -108,9 +108,118 @@ def bench_train(args, dev, rank, world):
                           "losses": [round(float(x["loss"] if isinstance(x, dict) else x), 4) for x in losses]}), flush=True)
 
 
+def _mmu_batch_workload(cfg, dev, n_req=32):
+    """32 MMU requests: 729 image positions, questions of 8 - 120 ids, answers of 16 - 256 ids set by per-request max_length (random
+    weights give no usable EOS)."""
+    g = torch.Generator().manual_seed(1)
+    qlen = torch.randint(8, 121, (n_req,), generator=g).tolist()
+    new = [int(x) for x in torch.linspace(16, 256, n_req)]
+    new = [new[i] for i in torch.randperm(n_req, generator=g).tolist()]
+    qs = [torch.randint(0, 50000, (1, L), generator=g).to(dev) for L in qlen]
+    feats = [torch.randn(1, 729, cfg.fused_vision_dim, generator=g).to(dev) for _ in range(n_req)]
+    lens = [4 + 729 + L + n for L, n in zip(qlen, new)]         # decode samples max_length - prompt positions ids (no EOS)
+    return feats, qs, lens, new
+
+
+def bench_decode_mmu_batch(args, dev):
+    """Continuous batching of MMU requests (omnimamba_amd/batch_decode.py): generated tokens / s of mmu_generate_batch (max_batch 8) against
+    the same requests through sequential mmu_generate calls, OmniMamba-1.3B with fp32 weights (as the reference runs it) and with bf16
+    weights; every bucket / graph is warmed up first, prefills are part of both timings."""
+    cfg = StackConfig.omnimamba_1_3b()
+    for wdt in (torch.float32, torch.bfloat16):
+        torch.manual_seed(0)
+        model = OmniMambaPath(cfg, stage="inference", device=dev, dtype=wdt)
+        feats, qs, lens, new = _mmu_batch_workload(cfg, dev)
+        feats = [f.to(wdt) for f in feats]
+        n_tok = sum(new)
+        # warm-ups: the sequential step graph at the largest max_length (later calls reuse it), every bucket of the ragged step
+        model.mmu_generate(feats[0], qs[0], max_length=max(lens), cg=True)
+        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        seq = [model.mmu_generate(f, q, max_length=L, cg=True) for f, q, L in zip(feats, qs, lens)]
+        torch.cuda.synchronize()
+        t_seq = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        rag = model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True)
+        torch.cuda.synchronize()
+        t_rag = time.perf_counter() - t0
+        got, want = [r.shape[1] for r in rag], [s_.shape[1] for s_ in seq]
+        assert got == want == [4 + q.shape[1] + n for q, n in zip(qs, new)], (got, want)
+        same = sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
+        print(json.dumps({"workload": "OmniMamba-1.3B MMU continuous batching", "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
+                          "requests": len(qs), "generated_tokens": n_tok, "max_batch": args.max_batch,
+                          "sequential_s": round(t_seq, 3), "ragged_s": round(t_rag, 3),
+                          "sequential_tokens_per_s": round(n_tok / t_seq, 1), "ragged_tokens_per_s": round(n_tok / t_rag, 1),
+                          "speedup": round(t_seq / t_rag, 2), "requests_with_identical_ids": same}), flush=True)
+        del model
+        torch.cuda.empty_cache()
+
+
+def bench_step_index_cost(args, dev):
+    """The cost of state_indices on the decode step: the captured bf16 batch-B step of OmniMamba-1.3B with identity slot indices against
+    today's captured step without them, replays alternating in blocks of 20 (``--steps`` replays each).  ``--only plain|indexed`` captures
+    and replays one of the two (for a kernel-trace run of each)."""
+    from omnimamba_amd.batch_decode import _Bucket
+    from omnimamba_amd.generation import InferenceParams
+    torch.manual_seed(0)
+    cfg = StackConfig.omnimamba_1_3b()
+    model = OmniMambaLM(cfg, device=dev, dtype=torch.bfloat16).eval()
+    B = args.batch
+    pool = model.allocate_inference_cache(B, 4096, torch.bfloat16)
+    for c, s_ in pool.values():
+        c.normal_(std=0.1), s_.normal_(std=0.1)
+    model.prepare_decode("mmu")
+    graphs = {}
+    with torch.inference_mode():
+        if args.only in (None, "indexed"):
+            bk = _Bucket(model, pool, B, 4096, "mmu", True, None)
+            bk.slots.copy_(torch.arange(B, dtype=torch.int32))
+            bk.position_ids.fill_(800)
+            graphs["indexed"] = bk.graph
+        if args.only in (None, "plain"):
+            ip = InferenceParams(max_seqlen=4096, max_batch_size=B, seqlen_offset=1, key_value_memory_dict=pool)
+            ids, pos = torch.zeros(B, 1, dtype=torch.long, device=dev), torch.full((B, 1), 800, dtype=torch.long, device=dev)
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                for _ in range(2):
+                    model(ids, None, position_ids=pos, task="mmu", inference_params=ip, num_last_tokens=1)
+                s.synchronize()
+            torch.cuda.current_stream().wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                model(ids, None, position_ids=pos, task="mmu", inference_params=ip, num_last_tokens=1)
+            graphs["plain"] = g
+    for g in graphs.values():
+        for _ in range(20):
+            g.replay()
+    torch.cuda.synchronize()
+    times = {k: [] for k in graphs}
+    blk = 20
+    for _ in range((args.steps + blk - 1) // blk):
+        for k, g in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(blk):
+                g.replay()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / blk)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    out = {"workload": "OmniMamba-1.3B captured decode step, bf16 weights", "batch": B, "replays_each": len(next(iter(times.values()))) * blk}
+    out.update({f"{k}_ms_median": round(v, 4) for k, v in med.items()})
+    out.update({f"{k}_ms_min": round(min(times[k]), 4) for k in times})
+    if len(med) == 2:
+        out["indexed_over_plain_pct"] = round((med["indexed"] / med["plain"] - 1) * 100, 2)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["decode", "train"])
+    ap.add_argument("what", choices=["decode", "train", "decode_mmu_batch", "step_index_cost"])
+    ap.add_argument("--max-batch", type=int, default=8, help="decode_mmu_batch: slots of the ragged decoder")
+    ap.add_argument("--only", choices=["plain", "indexed"], default=None, help="step_index_cost: capture and replay one step only")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--seqlen", type=int, default=2048)
     ap.add_argument("--steps", type=int, default=3)
@@ -126,6 +235,10 @@ def main():
     torch.cuda.set_device(dev)
     if args.what == "decode":
         (bench_decode_mmu if args.task == "mmu" else bench_decode)(args, dev)
+    elif args.what == "decode_mmu_batch":
+        bench_decode_mmu_batch(args, dev)
+    elif args.what == "step_index_cost":
+        bench_step_index_cost(args, dev)
     else:
         bench_train(args, dev, rank, world)
 
