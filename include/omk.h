@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 8
+#define OMK_ABI_VERSION 9
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
@@ -180,6 +180,32 @@ typedef struct {
   OmkTensor state_batch_indices;
 } OmkStateUpdate;
 int omk_selective_state_update(const OmkStateUpdate* p, omk_stream stream);
+
+/* ---- multi-token SSM state extend (ABI 9) ----------------------------------------------------------------
+ * T tokens of ONE turn applied to a cached state in one pass: a follow-up turn of a conversation continues the state the previous
+ * turn left instead of re-running the whole conversation (Mamba2.forward with a cache at seqlen_offset > 0 and L > 1).  Per token
+ * t in order:  s <- s * exp(dt_t A) + dt_t x_t (x) B_t ;  y_t = s . C_t + D x_t ;  y_t *= silu(z_t)  (dt_t: + dt_bias, softplus as
+ * in OmkStateUpdate).  The fields mean what they mean in OmkStateUpdate with a token dimension after the batch; the state is
+ * read once, kept in fp32 for all T tokens and stored once (one rounding for a 16-bit state).  An fp32 state ends bit-identical
+ * to T omk_selective_state_update calls.  Layouts: N in {16, 32, 64, 128} with unit stride on n and 4-element aligned rows of
+ * state / B / C, any T >= 0; anything else returns OMK_EUNSUPPORTED (step such a state token by token).  Graph-capturable. */
+typedef struct {
+  OmkTensor state;   /* (B, H, P, N) in place */
+  OmkTensor x;       /* (B, T, H, P) */
+  OmkTensor dt;      /* (B, T, H, P) stride 0 on P allowed */
+  OmkTensor A;       /* (H, P, N) stride 0 on P,N allowed */
+  OmkTensor Bm, Cm;  /* (B, T, G, N) */
+  OmkTensor D;       /* optional (H, P) */
+  OmkTensor z;       /* optional (B, T, H, P) */
+  OmkTensor dt_bias; /* optional (H, P) */
+  OmkTensor out;     /* (B, T, H, P): y_t of every token */
+  int32_t dt_softplus;
+  /* optional int32 (B), ABI 8's meaning: row b extends state row state_batch_indices[b] of a pool whose batch dimension may
+   * exceed B; a negative index (or one >= the pool's rows) marks a padding row: no state is read or written and its T outputs
+   * are zeros.  Absent: state is (B, H, P, N) and row b is state row b. */
+  OmkTensor state_batch_indices;
+} OmkStateExtend;
+int omk_selective_state_extend(const OmkStateExtend* p, omk_stream stream);
 
 /* ---- Mamba-1 selective scan ----------------------------------------------------------------------------
  * upstream mamba_ssm.ops.selective_scan_interface.selective_scan_fn (BASELINE.json configs[0] signature)

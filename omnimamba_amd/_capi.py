@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 8
+OMK_ABI_VERSION = 9
 OMK_MAX_DIMS = 5
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices only
 
@@ -62,6 +62,8 @@ Conv1dBwd = _S("OmkConv1dBwd", [(n, _t) for n in ("x", "weight", "bias", "initia
 Conv1dUpdate = _S("OmkConv1dUpdate", [(n, _t) for n in ("x", "conv_state", "weight", "bias", "out")] + [("silu", _i), ("conv_state_indices", _t)])
 StateUpdate = _S("OmkStateUpdate", [(n, _t) for n in ("state", "x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "out")]
                  + [("dt_softplus", _i), ("state_batch_indices", _t)])
+StateExtend = _S("OmkStateExtend", [(n, _t) for n in ("state", "x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "out")]
+                 + [("dt_softplus", _i), ("state_batch_indices", _t)])   # ABI 9: OmkStateUpdate with a token dimension
 SelScanFwd = _S("OmkSelScanFwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm", "D", "z", "delta_bias", "out",
                                                     "last_state", "pass_states")] + [("delta_softplus", _i)])
 SelScanBwd = _S("OmkSelScanBwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm", "D", "z", "delta_bias", "dout", "du",
@@ -91,7 +93,7 @@ Sample = _S("OmkSample", [("logits", _t), ("out_ids", _t), ("step_counter", C.c_
                           ("top_k", _i), ("top_p", _f), ("temperature", _f), ("min_p", _f)])
 
 STRUCTS = {s.__name__: s for s in (Sample, CrossEntropy, OmkTensor, AddNormFwd, AddNormBwd, NormGatedFwd, NormGatedBwd, Conv1dFwd, Conv1dBwd,
-                                   Conv1dUpdate, StateUpdate, SelScanFwd, SelScanBwd, NormLinear, LoraAdd, LoraUpBwd, SsdFwd, SsdBwd)}
+                                   Conv1dUpdate, StateUpdate, StateExtend, SelScanFwd, SelScanBwd, NormLinear, LoraAdd, LoraUpBwd, SsdFwd, SsdBwd)}
 
 # every symbol include/omk.h declares
 SYMBOLS = [
@@ -99,7 +101,7 @@ SYMBOLS = [
     "omk_add_norm_fwd", "omk_add_norm_bwd_workspace_bytes", "omk_add_norm_bwd",
     "omk_norm_gated_fwd", "omk_norm_gated_bwd_workspace_bytes", "omk_norm_gated_bwd",
     "omk_causal_conv1d_fwd", "omk_causal_conv1d_bwd_workspace_bytes", "omk_causal_conv1d_bwd", "omk_causal_conv1d_update",
-    "omk_selective_state_update", "omk_norm_linear", "omk_lora_add", "omk_lora_up_bwd",
+    "omk_selective_state_update", "omk_selective_state_extend", "omk_norm_linear", "omk_lora_add", "omk_lora_up_bwd",
     "omk_selective_scan_fwd", "omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_selective_scan_bwd_workspace_bytes", "omk_selective_scan_bwd",
     "omk_ssd_scan_fwd_workspace_bytes", "omk_ssd_scan_fwd_window_states_bytes", "omk_ssd_scan_fwd", "omk_ssd_scan_bwd_workspace_bytes", "omk_ssd_scan_bwd",
     "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample",

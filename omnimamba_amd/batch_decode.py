@@ -7,14 +7,32 @@ joins the step.  The step runs the live rows in the smallest bucket of {1, 2, 4,
 own position and its slot (``InferenceParams.state_indices``), empty rows of the bucket carry slot -1 and leave every state alone.  A row
 retires on EOS or at its own ``max_length``; its slot goes to the next request.  Retiring and admitting rewrite the small row buffers
 (ids, positions, slots) and never move a state.  With ``cg=True`` one step graph is captured per bucket.
+
+Multi-turn (MMU follow-ups): a request may carry the ``DecodeState`` its previous turn left (``return_states=True``).  Admission copies it
+into the free slot and extends the slot by the pending id and the new turn's tokens (Mamba2's extend path: the conversation is never
+re-prefilled), then the request decodes like any other.
 """
 from __future__ import annotations
 
 from collections import deque
+from dataclasses import dataclass
+from typing import List, Tuple
 
 import torch
 
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
+
+
+@dataclass
+class DecodeState:
+    """What a finished request leaves for its next turn: the recurrent state of one sequence after `seqlen` positions.
+    layers: per layer (in layer order) the batch-1 (conv_state, ssm_state) copies; pending_id: the last sampled id, which the model
+    has not consumed yet (the next turn starts with it, at position seqlen); task and dtype: of the cache it was copied from."""
+    layers: List[Tuple[torch.Tensor, torch.Tensor]]
+    seqlen: int
+    pending_id: int
+    task: str
+    dtype: torch.dtype
 
 
 def _buckets(max_batch):
@@ -106,24 +124,59 @@ def _prefill(model, c, slot, emb, task, cg):
     return (out.t2i_logits if task == "t2i" else out.mmu_logits).squeeze(1)
 
 
+def _extend(model, c, slot, state, emb, task):
+    """Continue a conversation in pool slot `slot`: copy `state` in, then extend the slot by [state.pending_id] + the turn's embeddings
+    `emb` (1, P, d) at positions state.seqlen ... (eager, straight into views of the slot) -> logits (1, vocab) of the last position."""
+    if state.task != task or state.dtype != c["dtype"]:
+        raise ValueError(f"decode_ragged: a {state.task} / {state.dtype} state cannot continue in a {task} / {c['dtype']} cache")
+    dst = [t[slot:slot + 1] for k in sorted(c["pool"]) for t in c["pool"][k]]
+    torch._foreach_copy_(dst, [t for pair in state.layers for t in pair])
+    dev = emb.device
+    pend = model.get_input_embeddings()(torch.tensor([[state.pending_id]], dtype=torch.long, device=dev))
+    h = torch.cat([pend.to(emb.dtype), emb], dim=1)
+    pos = torch.arange(state.seqlen, state.seqlen + h.shape[1], dtype=torch.long, device=dev)[None]
+    # the stack adds no position rows to embeddings it is handed with position_ids: they are added here, at the conversation's positions
+    h = h + model.backbone.mmu_pos_embed[:, state.seqlen: state.seqlen + h.shape[1]].to(h.dtype)
+    ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=1, seqlen_offset=state.seqlen,
+                         key_value_memory_dict={k: tuple(t[slot:slot + 1] for t in v) for k, v in c["pool"].items()})
+    out = model(None, h, position_ids=pos, task=task, inference_params=ip, num_last_tokens=1)
+    return out.mmu_logits.squeeze(1)
+
+
+def _save(c, slot, seqlen, pending_id, task):
+    return DecodeState(layers=[tuple(t[slot:slot + 1].clone() for t in c["pool"][k]) for k in sorted(c["pool"])], seqlen=seqlen,
+                       pending_id=pending_id, task=task, dtype=c["dtype"])
+
+
 @torch.inference_mode()
 def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
-                  min_p=0.0, cg=True):
+                  min_p=0.0, cg=True, return_states=False):
     """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
     generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
     model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
-    past the position table (raised before that step is launched)."""
+    past the position table (raised before that step is launched).
+
+    A request may also be (input_ids (1, Li), input_embeddings (1, Pi, d), state): the next turn of a conversation whose previous turn
+    left `state` (a DecodeState; 'mmu' only).  Its embeddings are the new turn's only; the slot continues from the state at position
+    state.seqlen with [state.pending_id] + the new turn, and max_length counts the whole conversation's positions.  Its ids are
+    input_ids followed by the sampled ids.  return_states=True: returns (ids_list, states_list), states_list[i] the DecodeState of
+    request i when it finished."""
     n = len(requests)
     if n == 0:
-        return []
+        return ([], []) if return_states else []
     lens = [int(max_length)] * n if isinstance(max_length, int) else [int(m) for m in max_length]
     if len(lens) != n:
         raise ValueError(f"decode_ragged: {len(lens)} max_length values for {n} requests")
     if max_batch < 1:
         raise ValueError("decode_ragged: max_batch must be >= 1")
-    for ids, emb in requests:
+    for r in requests:
+        if len(r) not in (2, 3):
+            raise ValueError("decode_ragged: every request is (input_ids, input_embeddings) or (input_ids, input_embeddings, state)")
+        ids, emb = r[0], r[1]
         if ids.dim() != 2 or ids.shape[0] != 1 or emb.dim() != 3 or emb.shape[0] != 1:
             raise ValueError("decode_ragged: every request is (input_ids (1, L), input_embeddings (1, P, d))")
+        if len(r) == 3 and (task != "mmu" or not isinstance(r[2], DecodeState)):
+            raise ValueError("decode_ragged: a continued request carries a DecodeState and is an mmu request")
     dev = requests[0][1].device
     if hasattr(model, "prepare_decode"):
         model.prepare_decode(task)
@@ -143,24 +196,39 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     pieces = [[] for _ in range(n)]      # per request: the positions of its ids in cat(drawn), in sampling order
     queue, free = deque(range(n)), list(range(max_batch))
     live = []                            # rows of the step: [request, slot, offset]
-    check_eos = eos_token_id is not None
+    check_eos = eos_token_id is not None or return_states
+    states = [None] * n
+
+    def retire(i, s, off, tok):
+        free.append(s)
+        if return_states:
+            states[i] = _save(c, s, off, tok, task)
 
     def finished(i, tok, off):
-        return (check_eos and tok == eos_token_id) or off >= lens[i] - 1
+        return (eos_token_id is not None and tok == eos_token_id) or off >= lens[i] - 1
 
     while queue or live:
         while queue and free:                                  # admit FIFO into free slots
             i = queue.popleft()
             s = free.pop(0)
-            ids, emb = requests[i]
-            tok = draw(_prefill(model, c, s, emb, task, cg))   # (1,)
+            ids, emb = requests[i][:2]
+            if len(requests[i]) == 3:
+                st = requests[i][2]
+                off = st.seqlen + 1 + emb.shape[1]
+                if n_pos is not None and off > n_pos:
+                    raise IndexError(f"decode_ragged: request {i} continues to position {off - 1}, outside the {task} position table of "
+                                     f"{n_pos} rows (StackConfig.{{t2i,mmu}}_positions)")
+                tok = draw(_extend(model, c, s, st, emb, task))
+            else:
+                tok = draw(_prefill(model, c, s, emb, task, cg))   # (1,)
+                off = emb.shape[1]
             last[s:s + 1].copy_(tok)
             drawn.append(tok)
             pieces[i].append(n_drawn)
             n_drawn += 1
-            off = emb.shape[1]
-            if finished(i, int(tok[0]) if check_eos else None, off):
-                free.append(s)
+            tok_h = int(tok[0]) if check_eos else None
+            if finished(i, tok_h, off):
+                retire(i, s, off, tok_h)
             else:
                 live.append([i, s, off])
         if not live:
@@ -187,12 +255,13 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             row[2] = off = off + 1
             pieces[i].append(n_drawn + r)
             if finished(i, toks_h[r] if check_eos else None, off):
-                free.append(s)
+                retire(i, s, off, toks_h[r] if check_eos else None)
             else:
                 still.append(row)
         drawn.append(toks)
         n_drawn += len(live)
         live = still
     flat = torch.cat(drawn)
-    return [torch.cat([ids, flat[torch.tensor(pieces[i], device=dev)].view(1, -1).to(ids.device)], dim=1)
-            for i, (ids, _) in enumerate(requests)]
+    out = [torch.cat([r[0], flat[torch.tensor(pieces[i], device=dev)].view(1, -1).to(r[0].device)], dim=1)
+           for i, r in enumerate(requests)]
+    return (out, states) if return_states else out

@@ -5,6 +5,7 @@ models/stage2/config_mamba.py:16; called at models/stage2/block.py:117,149-150).
 
   forward(u)            training / no cache : in_proj (hipBLASLt) -> fused conv1d+SSD+gated-norm+out_proj node
   forward(u, ip, off=0) prefill with cache  : conv_state / ssm_state are fully overwritten
+  forward(u, ip, off>0) L > 1: extend       : the cached sequence continues by L tokens (a follow-up turn), states in place
   step(u, conv, ssm)    decode              : causal_conv1d_update + selective_state_update, in place
 ``in_proj`` stays an nn.Linear attribute invoked through __call__ because the reference swaps it for its task-switched
 LoRA Linear (models/stage2/lora.py:90-106) and sets ``.task_types`` on it (mixer_seq_simple.py:368-371).
@@ -22,8 +23,14 @@ from .causal_conv1d import causal_conv1d_fn, causal_conv1d_update
 from .layernorm_gated import RMSNorm as RMSNormGated
 from . import norm_linear as NL
 from .linear import linear
-from .selective_state_update import selective_state_update
+from .selective_state_update import selective_state_extend, selective_state_update
 from .ssd_combined import mamba_chunk_scan_combined, mamba_split_conv1d_scan_combined
+
+# Extend (forward with a cache at seqlen_offset > 0, L > 1): turns of up to this many tokens go through omk_selective_state_extend (the
+# state read once, T tokens applied serially per row), longer ones through the chunked scan with the cached state as initial_states.
+# Set from tools/bench_model.py mmu_followup (per layer, 1.3B shapes, batch 1, MI355X, eager): the extend kernel takes 37 / 39 / 65 us at
+# T 1 / 8 / 32 in fp32 (24 / 33 / 60 in bf16), the chunked scan 49 - 51 us at all three: the two meet between 8 and 32.
+EXTEND_SCAN_MAX_T = 16
 
 
 class Mamba2(nn.Module):
@@ -114,6 +121,8 @@ class Mamba2(nn.Module):
         conv_state, ssm_state = None, None
         if inference_params is not None:
             conv_state, ssm_state = self._get_states_from_cache(inference_params, batch)
+            if inference_params.seqlen_offset > 0 and seqlen > 1:
+                return self._extend(u, batch, seqlen, seqlen_og, conv_state, ssm_state, inference_params)
             if inference_params.seqlen_offset > 0:
                 out, _, _ = self.step(u, conv_state, ssm_state, state_indices=getattr(inference_params, "state_indices", None))
                 return out
@@ -173,6 +182,48 @@ class Mamba2(nn.Module):
             dt_softplus=True, return_final_states=ssm_state is not None, **dt_limit_kwargs)
         if ssm_state is not None:
             y, last_state = y
+            ssm_state.copy_(last_state)
+        y = y.flatten(-2)
+        if self.rmsnorm:
+            y = self.norm(y, z)
+        if d_mlp > 0:
+            y = torch.cat([F.silu(z0) * x0, y], dim=-1)
+        if seqlen_og is not None:
+            y = y.reshape(batch * seqlen, -1)
+        return self.out_proj(y)
+
+    def _extend(self, u, batch, seqlen, seqlen_og, conv_state, ssm_state, inference_params):
+        """Continue the cached sequence by `seqlen` tokens: afterwards out, conv_state and ssm_state are what a prefill of the whole
+        concatenated sequence gives.  conv1d from the cached inputs (initial_states) -> scan from the cached state (the extend kernel or
+        the chunked scan, EXTEND_SCAN_MAX_T) -> gated norm -> out_proj, as the prefill's unfused branch."""
+        if getattr(inference_params, "state_indices", None) is not None:
+            raise NotImplementedError("Mamba2 extend runs one cache row per sequence (a view of its slot), not state_indices")
+        if torch.is_grad_enabled():
+            raise NotImplementedError("Mamba2 extend is an inference path (no autograd through the cached states)")
+        zxbcdt = linear(u, self.in_proj.weight, self.in_proj.bias) if type(self.in_proj) is nn.Linear else self.in_proj(u)
+        if seqlen_og is not None:
+            zxbcdt = zxbcdt.view(batch, seqlen, -1)
+        A = self._A_inference()
+        d_mlp = (zxbcdt.shape[-1] - 2 * self.d_ssm - 2 * self.ngroups * self.d_state - self.nheads) // 2
+        z0, x0, z, xBC, dt = torch.split(
+            zxbcdt, [d_mlp, d_mlp, self.d_ssm, self.d_ssm + 2 * self.ngroups * self.d_state, self.nheads], dim=-1)
+        # conv: the cached last d_conv inputs stand before the new ones; the state keeps the last d_conv inputs of the concatenation
+        xBC_t = xBC.contiguous().transpose(1, 2)      # channel-last: the conv output keeps it, B / C rows stay unit-stride
+        new_conv = torch.cat([conv_state, xBC_t.to(conv_state.dtype)], dim=-1)[..., -self.d_conv:]
+        xBC = causal_conv1d_fn(xBC_t, self.conv1d.weight.squeeze(1), self.conv1d.bias, initial_states=conv_state[..., 1:],
+                               activation=self.activation).transpose(1, 2)
+        conv_state.copy_(new_conv)
+        x, B, C = torch.split(xBC, [self.d_ssm, self.ngroups * self.d_state, self.ngroups * self.d_state], dim=-1)
+        x = x.unflatten(-1, (self.nheads, self.headdim))
+        B, C = B.unflatten(-1, (self.ngroups, self.d_state)), C.unflatten(-1, (self.ngroups, self.d_state))
+        zh = z.unflatten(-1, (self.nheads, self.headdim)) if not self.rmsnorm else None
+        if seqlen <= EXTEND_SCAN_MAX_T and self.dt_limit == (0.0, float("inf")) and self.d_state in (16, 32, 64, 128):
+            y = selective_state_extend(ssm_state, x, dt, A, B, C, D=self._D(), z=zh, dt_bias=self.dt_bias, dt_softplus=True)
+        else:
+            dt_limit_kwargs = {} if self.dt_limit == (0.0, float("inf")) else dict(dt_limit=self.dt_limit)
+            y, last_state = mamba_chunk_scan_combined(x, dt, A, B, C, chunk_size=self.chunk_size, D=self._D(), z=zh, dt_bias=self.dt_bias,
+                                                      initial_states=ssm_state, dt_softplus=True, return_final_states=True,
+                                                      **dt_limit_kwargs)
             ssm_state.copy_(last_state)
         y = y.flatten(-2)
         if self.rmsnorm:

@@ -1,8 +1,9 @@
-"""Single-token SSM state update on the MI355X (decode step of Mamba2.step).
+"""Single-token SSM state update and its multi-token extend on the MI355X (decode step of Mamba2.step).
 
 Mirrors ``mamba_ssm.ops.triton.selective_state_update.selective_state_update``; reference reach:
 /root/reference/models/stage2/generation.py:195-211,412-424 -> MixerModel.forward -> Block -> Mamba2.step.
 Kernel: omk_selective_state_update (omnimamba_amd/csrc/state_update.hip), in place on ``state``, graph-capturable.
+``selective_state_extend``: T tokens of a follow-up turn in one launch (omk_selective_state_extend, same file).
 """
 from __future__ import annotations
 
@@ -44,3 +45,32 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
                           z=K.T(z_v), dt_bias=K.T(tb_v), out=K.T(out), dt_softplus=int(dt_softplus), state_batch_indices=K.T(idx))
         K.run(lib, "omk_selective_state_update", p, x_v)
     return out if has_heads else out.squeeze(1)
+
+
+def selective_state_extend(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, state_batch_indices=None):
+    """T tokens of one turn applied to a cached state in one launch (omk_selective_state_extend): what T successive
+    ``selective_state_update`` calls do, with the state read once, kept in fp32 and stored once.
+    state: (batch, nheads, dim, dstate), updated IN PLACE; x, z: (batch, T, nheads, dim); dt: (batch, T, nheads[, dim]);
+    A: (nheads[, dim, dstate]); B, C: (batch, T, ngroups, dstate); D, dt_bias: (nheads[, dim]).  Returns out like x.
+    state_batch_indices: as in ``selective_state_update`` -- row b extends pool row state_batch_indices[b], a negative index is a
+    padding row (no state traffic, zero outputs)."""
+    lib = get_lib()
+    require_device(lib, state, x, dt, A, B, C, D, z, dt_bias, state_batch_indices)
+    if state.dim() != 4 or x.dim() != 4:
+        raise ValueError("selective_state_extend: state (batch, nheads, dim, dstate) and x (batch, T, nheads, dim)")
+    idx = slot_indices(state_batch_indices, x.shape[0], x.device, "state_batch_indices")
+    H, P, N = state.shape[1:]
+    # per-head parameters as stride-0 expansions (the kernel's tied form)
+    dt_v = dt[..., None].expand(*dt.shape, P) if dt.dim() == 3 else dt
+    A_v = A[:, None, None].expand(H, P, N) if A.dim() == 1 else A
+    D_v = D[:, None].expand(H, P) if (D is not None and D.dim() == 1) else D
+    tb_v = dt_bias[:, None].expand(H, P) if (dt_bias is not None and dt_bias.dim() == 1) else dt_bias
+    B_v = B if B.dtype == x.dtype else B.to(x.dtype)
+    C_v = C if C.dtype == x.dtype else C.to(x.dtype)
+    z_v = z if (z is None or z.dtype == x.dtype) else z.to(x.dtype)
+    out = torch.empty_like(x)
+    if x.numel() > 0:
+        p = K.StateExtend(state=K.T(state), x=K.T(x), dt=K.T(dt_v), A=K.T(A_v), Bm=K.T(B_v), Cm=K.T(C_v), D=K.T(D_v), z=K.T(z_v),
+                          dt_bias=K.T(tb_v), out=K.T(out), dt_softplus=int(dt_softplus), state_batch_indices=K.T(idx))
+        K.run(lib, "omk_selective_state_extend", p, x)
+    return out

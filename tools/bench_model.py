@@ -1,5 +1,5 @@
 """BASELINE.json configs[2..4] on the synthetic OmniMamba-1.3B stack (random init, synthetic data), 1 GPU or N GPUs via
-torch.distributed.run:   python tools/bench_model.py [decode|train|decode_mmu_batch|step_index_cost] [--batch B] [--seqlen L] [--steps K]
+torch.distributed.run:   python tools/bench_model.py [decode|train|decode_mmu_batch|step_index_cost|mmu_followup] [--batch B] [--seqlen L] [--steps K]
 Prints one JSON line per workload (rank 0)."""
 import argparse
 import json
@@ -215,9 +215,81 @@ def bench_step_index_cost(args, dev):
     print(json.dumps(out), flush=True)
 
 
+def _time_ms(fn, reps):
+    """Median of `reps` event-timed calls after two warm-up calls."""
+    for _ in range(2):
+        fn()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return sorted(ts)[len(ts) // 2]
+
+
+def bench_mmu_followup(args, dev):
+    """Multi-turn MMU.  (1) Per layer (1.3B shapes: H 64, P 64, N 128, batch 1): omk_selective_state_extend against the chunked scan
+    with initial states for T in {1, 8, 32, 64, 128, 256} -- the sweep behind mamba2.EXTEND_SCAN_MAX_T.  (2) Time to the first token of
+    turn 2 for --batch conversations (729 image positions, Q1 of 24 ids, A1 of 32 ids, Q2 of 24 ids): mmu_continue from the turn-1
+    states against re-prefilling the whole conversation with mmu_generate_batch.  fp32 and bf16 weights, eager both ways."""
+    from omnimamba_amd.selective_state_update import selective_state_extend
+    from omnimamba_amd.ssd_combined import mamba_chunk_scan_combined
+    H, P, N = 64, 64, 128
+    g = torch.Generator().manual_seed(2)
+    for wdt in (torch.float32, torch.bfloat16):
+        name = "bf16" if wdt == torch.bfloat16 else "f32"
+        A = -(torch.rand(H, generator=g) * 15 + 1).to(dev)
+        D, dtb = torch.randn(H, generator=g).to(dev), (torch.randn(H, generator=g) - 2).to(dev)
+        rows = []
+        with torch.inference_mode():
+            for T in (1, 8, 32, 64, 128, 256):
+                x = torch.randn(1, T, H, P, generator=g).to(wdt).to(dev)
+                dt = torch.randn(1, T, H, generator=g).to(wdt).to(dev)
+                Bm, Cm = torch.randn(1, T, 1, N, generator=g).to(wdt).to(dev), torch.randn(1, T, 1, N, generator=g).to(wdt).to(dev)
+                st = torch.randn(1, H, P, N, generator=g).to(wdt).to(dev)
+                work = st.clone()
+                t_ext = _time_ms(lambda: (work.copy_(st), selective_state_extend(work, x, dt, A, Bm, Cm, D=D, dt_bias=dtb, dt_softplus=True)), 50)
+                t_copy = _time_ms(lambda: work.copy_(st), 50)
+                t_scan = _time_ms(lambda: mamba_chunk_scan_combined(x, dt, A, Bm, Cm, chunk_size=256, D=D, dt_bias=dtb, initial_states=st,
+                                                                    dt_softplus=True, return_final_states=True), 50)
+                rows.append({"T": T, "extend_us": round((t_ext - t_copy) * 1e3, 1), "chunk_scan_us": round(t_scan * 1e3, 1)})
+        print(json.dumps({"workload": "per-layer state extend vs chunked scan with initial states", "dtype": name, "H": H, "P": P, "N": N,
+                          "rows": rows}), flush=True)
+    cfg = StackConfig.omnimamba_1_3b()
+    n = args.batch
+    for wdt in (torch.float32, torch.bfloat16):
+        torch.manual_seed(0)
+        model = OmniMambaPath(cfg, stage="inference", device=dev, dtype=wdt)
+        g = torch.Generator().manual_seed(3)
+        feats = [torch.randn(1, 729, cfg.fused_vision_dim, generator=g).to(dev).to(wdt) for _ in range(n)]
+        q1 = [torch.randint(0, 50000, (1, 24), generator=g).to(dev) for _ in range(n)]
+        q2 = [torch.randint(0, 50000, (1, 24), generator=g).to(dev) for _ in range(n)]
+        ids1, st1 = model.mmu_generate_batch(feats, q1, max_length=4 + 729 + 24 + 32, max_batch=args.max_batch, cg=False, return_states=True)
+        full = [torch.cat([a, i[:, 4 + a.shape[1]:], b], dim=1) for a, i, b in zip(q1, ids1, q2)]
+        L2 = [s.seqlen + 1 + b.shape[1] + 1 for s, b in zip(st1, q2)]          # one sampled id: the first token of turn 2
+
+        def cont():
+            return model.mmu_continue(st1, q2, max_length=L2, max_batch=args.max_batch, cg=False)
+
+        def again():
+            return model.mmu_generate_batch(feats, full, max_length=L2, max_batch=args.max_batch, cg=False)
+        t_cont = _time_ms(cont, args.steps)
+        t_full = _time_ms(again, args.steps)
+        same = sum(int(a[0, -1]) == int(b[0, -1]) for a, b in zip(cont()[0], again()))
+        print(json.dumps({"workload": "OmniMamba-1.3B MMU turn 2, time to first token", "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
+                          "conversations": n, "max_batch": args.max_batch, "turn2_positions": L2[0] - 1,
+                          "continue_ms": round(t_cont, 2), "reprefill_ms": round(t_full, 2), "speedup": round(t_full / t_cont, 2),
+                          "first_ids_equal": same}), flush=True)
+        del model
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["decode", "train", "decode_mmu_batch", "step_index_cost"])
+    ap.add_argument("what", choices=["decode", "train", "decode_mmu_batch", "step_index_cost", "mmu_followup"])
     ap.add_argument("--max-batch", type=int, default=8, help="decode_mmu_batch: slots of the ragged decoder")
     ap.add_argument("--only", choices=["plain", "indexed"], default=None, help="step_index_cost: capture and replay one step only")
     ap.add_argument("--batch", type=int, default=1)
@@ -239,6 +311,8 @@ def main():
         bench_decode_mmu_batch(args, dev)
     elif args.what == "step_index_cost":
         bench_step_index_cost(args, dev)
+    elif args.what == "mmu_followup":
+        bench_mmu_followup(args, dev)
     else:
         bench_train(args, dev, rank, world)
 
