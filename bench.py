@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json configs[1]: one Mamba-2 block (OmniMamba-1.3B shape), forward + backward,
 B=8 L=4096 d_model=2048 d_state=128, bf16 autocast over fp32 parameters, synthetic data, on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE
 in the environment) or started plainly, in which case it re-executes itself under torch.distributed.run on 127.0.0.1.
@@ -10,11 +10,15 @@ in the environment) or started plainly, in which case it re-executes itself unde
 Prints ONE JSON line on rank 0.  value = selective-scan M-elements/s of the whole job =
 world * B * L * (H*P = 4096 scanned channels) / step_time / 1e6, a step being fwd + bwd of the block (in_proj GEMM ->
 fused conv1d + SSD scan + gated RMSNorm + out_proj node and its backward; with N > 1 the block is wrapped in DDP so the
-parameter gradients are all-reduced over RCCL, overlapped with backward).  The timed region is EXACTLY K steps (`steps` = K);
-a sustained region of the same step (>= --min-seconds, default 5 s: the driver's utilisation sampler has a 5 s period) follows and
-is reported separately under `sustained`.
+parameter gradients are all-reduced over RCCL, overlapped with backward).  The timed region is EXACTLY K steps (`steps` = K).
   roofline / roofline_bwd   the SSD scan forward / backward launches (algorithmic bytes of SURVEY.md section 8d) timed
                             with HIP events on the launch stream inside the timed region
+
+A plain run does only what that line needs: set-up, W warm-up steps, the K timed steps, the dump of --dump-outputs.  --full
+measures the rest as well, behind the timed region (--min-seconds 0 and the --no-* options leave single parts out again); a plain
+run reports each of them as null:
+  sustained                 a region of the same step (>= --min-seconds, default 5 s: the driver's utilisation sampler has a 5 s
+                            period); the HIP-event timing of the roofline then runs over both regions
   cpu_baseline              the CPU oracle (a port: mamba_ssm is absent) on a bounded sample of the same workload
   train_1p3b                BASELINE configs[3]: OmniMamba-1.3B stage-1 MMU step (projector + MMU LoRA train), L=2048,
                             bf16 autocast, DDP over RCCL when N > 1 -- tokens/s of the whole job
@@ -447,7 +451,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="length of the sustained region behind the K timed steps (0 = none)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the sustained region, cpu_baseline, "
+                                                        "selscan_cfg1, scan_target, decode_1p3b, train_1p3b and train_1p3b_stage2")
+    ap.add_argument("--min-seconds", type=float, default=5.0, help="with --full: length of the sustained region behind the K timed steps (0 = none)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-1p3b", action="store_true")
     ap.add_argument("--no-selscan-cfg1", action="store_true")
@@ -462,6 +468,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run: nothing behind the timed region but the dump and the line
+        args.min_seconds = 0.0
+        args.no_cpu_baseline = args.no_train_1p3b = args.no_selscan_cfg1 = args.no_scan_target = args.no_decode = True
 
     if (args.gpus > 1 or args.force_dist) and "WORLD_SIZE" not in os.environ:
         self_launch(args)

@@ -8,7 +8,7 @@ Reference: ``MambaVLM.decode_to_img`` (/root/reference/models/mamba_vlm.py:104-1
 ``quant_conv.*`` / ``quantize.codebook_used``).
 
 It is a convolutional network behind the hot path, not a scan: the kernels are the library's (MIOpen convolutions, the fused attention of
-``scaled_dot_product_attention``).  What is decided here is how it runs on the MI355X, by measurement (`bench.py` -> `decode_1p3b.vq_tail_ms`,
+``scaled_dot_product_attention``).  What is decided here is how it runs on the MI355X, by measurement (`bench.py --full` -> `decode_1p3b.vq_tail_ms`,
 batch 1, 256 ids -> 3 x 256 x 256, 42.6 M parameters): eager fp32 6.4 ms, one hipGraph replay (``graphed``) 6.25 ms, replay under bf16 autocast
 5.8 ms, bf16 + channels-last 6.6 ms -- the convolutions at 128^2 / 256^2 pixels are the time, not the 60 launches, and NHWC buys nothing
 from the library here, so NCHW is the default and channels-last an option (``set_channels_last``).  Against the 440 ms of the 256-token

@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--min-seconds", "0", "--no-train-1p3b", "--no-decode"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -46,7 +47,7 @@ def test_bench_json_contract():
 
 @pytest.mark.gpu
 def test_bench_times_exactly_k_steps_and_reports_the_sustained_region_separately():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--min-seconds", "1.0", "--no-train-1p3b", "--no-selscan-cfg1", "--no-scan-target", "--no-decode"], capture_output=True,
                        text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -56,6 +57,26 @@ def test_bench_times_exactly_k_steps_and_reports_the_sustained_region_separately
     su = j["sustained"]                                              # the >= 1 s region behind it (utilisation sampling), never the headline
     assert su["steps"] > 3 and su["seconds"] >= 0.8
     assert j["roofline"]["launches_timed"] == 3 + su["steps"]        # the scan launches are HIP-event timed over both regions
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_does_only_what_the_headline_needs():
+    """Without --full: set-up, warm-up, the K timed steps and the line, in which everything --full adds is null -- and at most 30 s
+    of the run's wall time outside its K + W steps."""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["metric"] == "selective-scan M-elements/sec" and j["unit"] == "M-elements/s" and j["higher_is_better"] is True and j["dtype"] == "bf16"
+    assert j["steps"] == 3 and j["warmup"] == 1 and abs(j["ms_per_step"] - j["timed_seconds"] / 3 * 1e3) < 0.02 * j["ms_per_step"]
+    for k in ("sustained", "cpu_baseline", "train_1p3b", "train_1p3b_stage2", "selscan_cfg1", "scan_target", "decode_1p3b"):
+        assert k in j and j[k] is None, k
+    assert j["roofline"]["launches_timed"] == 3 and j["roofline_bwd"]["launches_timed"] == 3
+    assert wall - 4 * j["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 @pytest.mark.gpu
