@@ -24,11 +24,11 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 9
+#define OMK_ABI_VERSION 10
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
-typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices only */ } omk_dtype;
+typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices; ABI 10: per-row lengths */ } omk_dtype;
 typedef void* omk_stream; /* hipStream_t */
 
 typedef struct {
@@ -125,6 +125,12 @@ typedef struct {
   OmkTensor out;            /* (B, C, L) logical */
   OmkTensor final_states;   /* optional out (B, C, W-1) */
   int32_t silu;
+  /* ABI 10, optional int32 (B), 0 <= seq_lens[b] <= L: the rows of a right-padded batch end at different positions.  final_states[b]
+   * holds the last state_len inputs BEFORE position seq_lens[b] (left zero-padded, initial_states standing in front as without it)
+   * instead of before L; out is the same at every position.  Read on the device only (graph-capturable); a value outside 0 .. L is
+   * clamped.  Present, the final states are written by a second small launch (B * C * state_len
+   * threads) instead of the channel-last kernels' epilogues.  Absent: every row has length L. */
+  OmkTensor seq_lens;
 } OmkConv1dFwd;
 int omk_causal_conv1d_fwd(const OmkConv1dFwd* p, omk_stream stream);
 
@@ -358,6 +364,13 @@ typedef struct {
                              * split): otherwise OMK_EUNSUPPORTED and the caller runs conv + scan separately.
                              * reference: models/stage2/generation.py:195-211 prefill, scripts/inference_mmu.py:137-147 */
   OmkTensor conv_bias;      /* optional (H * P) */
+  OmkTensor seq_lens;       /* ABI 10, optional int32 (B), 0 <= seq_lens[b] <= L: the rows of a right-padded batch end at different positions.
+                             * Tokens t >= seq_lens[b] do not change row b's state: final_states[b] is the state after seq_lens[b] tokens
+                             * (after 0 tokens: initial_states[b], or zero); out[b, t] for t < seq_lens[b] is what it is without seq_lens,
+                             * for the masked t it is finite for finite inputs and otherwise unspecified.  The masked tokens enter every
+                             * scan kernel with dt' = +0 (written by the dt preparation), the way tokens behind L already do inside the
+                             * last chunk; no chunk is skipped.  Works with initial_states and conv_weight; window_states / the state-only
+                             * pass take none (OMK_EINVAL).  Read on the device only (graph-capturable).  Absent: every row has length L. */
 } OmkSsdFwd;
 /* OmkSsdFwd::flags / OmkSsdBwd::flags */
 #define OMK_SSD_PRECISE      1  /* forward, bf16 MFMA scan: the carried state meets C as a bf16 hi + lo pair and the state-update operand is

@@ -11,9 +11,9 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 9
+OMK_ABI_VERSION = 10
 OMK_MAX_DIMS = 5
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices only
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices, per-row lengths
 
 
 class OmkTensor(C.Structure):
@@ -56,7 +56,7 @@ NormGatedFwd = _S("OmkNormGatedFwd", [(n, _t) for n in ("x", "z", "weight", "bia
 NormGatedBwd = _S("OmkNormGatedBwd", [(n, _t) for n in ("dy", "x", "z", "weight", "dx", "dz", "dweight")] + _ws
                   + [("group_size", _i64), ("eps", _f), ("norm_before_gate", _i)])
 Conv1dFwd = _S("OmkConv1dFwd", [(n, _t) for n in ("x", "weight", "bias", "initial_states", "out", "final_states")]
-               + [("silu", _i)])
+               + [("silu", _i), ("seq_lens", _t)])   # ABI 10: per-row lengths of a right-padded batch
 Conv1dBwd = _S("OmkConv1dBwd", [(n, _t) for n in ("x", "weight", "bias", "initial_states", "dout", "dx", "dweight",
                                                   "dbias", "dinitial_states")] + [("silu", _i), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)])
 Conv1dUpdate = _S("OmkConv1dUpdate", [(n, _t) for n in ("x", "conv_state", "weight", "bias", "out")] + [("silu", _i), ("conv_state_indices", _t)])
@@ -78,7 +78,7 @@ LoraUpBwd = _S("OmkLoraUpBwd", [(n, _t) for n in ("dy", "lora_b", "h", "dh", "dl
 SsdFwd = _S("OmkSsdFwd", [(n, _t) for n in ("x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "initial_states", "out",
                                             "out_x", "final_states", "window_states")] + _ws
             + [("dt_min", _f), ("dt_max", _f), ("dt_softplus", _i), ("chunk_size", _i), ("force_generic", _i), ("flags", _i),
-               ("conv_weight", _t), ("conv_bias", _t)])
+               ("conv_weight", _t), ("conv_bias", _t), ("seq_lens", _t)])
 # OmkSsdFwd.flags / OmkSsdBwd.flags (include/omk.h)
 SSD_PRECISE, SSD_KHILO, SSD_EVERY_CHUNK, SSD_NO_SPLIT, SSD_COLUMN_SLICE, SSD_SEQUENTIAL_BWD = 1, 2, 4, 8, 16, 32
 SsdBwd = _S("OmkSsdBwd", [(n, _t) for n in ("x", "dt", "A", "Bm", "Cm", "D", "dt_bias", "initial_states", "y", "dout",

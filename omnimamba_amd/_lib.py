@@ -48,6 +48,13 @@ def require_device(lib, *tensors):
             raise RuntimeError(f"tensors on different devices: {dev} vs {t.device}")
 
 
+def forward_only_seq_lens(seq_lens, *tensors):
+    """seq_lens (per-row lengths of a right-padded prefill batch) exists in the forward kernels only: a call that would record a
+    backward refuses it.  Checked by the public wrappers, where the grad mode is the caller's (inside an autograd node it is off)."""
+    if seq_lens is not None and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError("seq_lens is forward-only (ragged prefill): no gradient through a call that passes it")
+
+
 def slot_indices(idx, batch, device, name):
     """Host checks of a slot-index tensor (state_batch_indices / conv_state_indices): 1-D, `batch` long, on `device`, int32 -- or
     int64, cast here with one extra launch.  The values are never read on the host: a step that carries them stays capturable."""

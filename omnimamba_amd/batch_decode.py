@@ -11,6 +11,11 @@ retires on EOS or at its own ``max_length``; its slot goes to the next request. 
 Multi-turn (MMU follow-ups): a request may carry the ``DecodeState`` its previous turn left (``return_states=True``).  Admission copies it
 into the free slot and extends the slot by the pending id and the new turn's tokens (Mamba2's extend path: the conversation is never
 re-prefilled), then the request decodes like any other.
+
+Ragged prefill (both off by default).  ``prefill_batch`` > 1: the plain requests at the head of the queue that find a free slot at the
+same moment are admitted by ONE right-padded prefill (``InferenceParams.seq_lens``: the kernels leave every row's states as after its
+own length) into the first rows of a staging cache, which are then copied into their slots.  ``prefill_bucket`` > 0 with ``cg``: a
+prompt longer than the exact-length capture limit replays a captured batch-1 prefill of its length rounded up to the bucket.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ from typing import List, Tuple
 
 import torch
 
+from . import generation as G
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
 
 
@@ -91,27 +97,41 @@ def _pool_cache(model, max_batch, max_seqlen, task, cg):
     if (c is None or (c["device"], c["dtype"], c["task"], c["cg"]) != (p0.device, p0.dtype, task, cg)
             or max_batch > c["max_batch"] or max_seqlen > c["max_seqlen"]):
         c = {"device": p0.device, "dtype": p0.dtype, "task": task, "cg": cg, "max_batch": max_batch, "max_seqlen": max_seqlen,
-             "pool": model.allocate_inference_cache(max_batch, max_seqlen, p0.dtype), "buckets": {}, "prefill": {},
+             "pool": model.allocate_inference_cache(max_batch, max_seqlen, p0.dtype), "buckets": {}, "prefill": {}, "staging": {},
              "mempool": torch.cuda.graphs.graph_pool_handle() if cg else None}
         model._ragged_cache = None       # (the old pool and graphs go before the new ones are captured)
         model._ragged_cache = c
     return c
 
 
-def _prefill(model, c, slot, emb, task, cg):
+def _bucket_len(seqlen, bucket, n_pos):
+    """Length of the captured bucket a prompt of `seqlen` positions replays, 0 = none (run it eager).  The stack adds the position
+    table to the whole padded buffer, so a bucket never reaches past the table's rows: it is clamped to them, and a prompt that does
+    not fit the clamped bucket runs eager (and raises there what it raises today)."""
+    if bucket <= 0 or seqlen <= G.PREFILL_GRAPH_MAX_LEN or not G._prefill_graphs_enabled():
+        return 0
+    blen = -(-seqlen // bucket) * bucket
+    if n_pos is not None:
+        blen = min(blen, n_pos)
+    return blen if blen >= seqlen else 0
+
+
+def _prefill(model, c, slot, emb, task, cg, bucket=0, n_pos=None):
     """Batch-1 prefill of one prompt into pool slot `slot` -> logits (1, vocab).  Eager: straight into views of the slot.  Captured
     (prompts of <= 512 positions, as generation.decode): a PrefillGraph per prompt length on a batch-1 cache of its own, whose states
-    are then copied into the slot."""
+    are then copied into the slot.  bucket > 0: longer prompts take a captured graph per length bucket (_bucket_len), their true
+    length in its static seq_lens buffer; same LRU, same MAX_PREFILL_GRAPHS."""
     seqlen = emb.shape[1]
-    if cg and _prefill_graph_ok(seqlen):
-        key = (seqlen, emb.dtype)
+    blen = _bucket_len(seqlen, bucket, n_pos) if cg else 0
+    if cg and (blen or _prefill_graph_ok(seqlen)):
+        key = (blen, emb.dtype, "bucket") if blen else (seqlen, emb.dtype)
         pg = c["prefill"].get(key)
         if pg is None:
             if len(c["prefill"]) >= MAX_PREFILL_GRAPHS:
                 del c["prefill"][next(iter(c["prefill"]))]
             ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=1,
                                  key_value_memory_dict=model.allocate_inference_cache(1, c["max_seqlen"], c["dtype"]))
-            pg = PrefillGraph(model, ip, 1, seqlen, emb.shape[-1], task, emb.dtype, mempool=c["mempool"])
+            pg = PrefillGraph(model, ip, 1, blen or seqlen, emb.shape[-1], task, emb.dtype, mempool=c["mempool"], ragged=bool(blen))
         c["prefill"][key] = c["prefill"].pop(key, pg)          # most recently used last
         lg = pg.run(emb)
         src = [t for k in sorted(pg.ip.key_value_memory_dict) for t in pg.ip.key_value_memory_dict[k]]
@@ -121,6 +141,28 @@ def _prefill(model, c, slot, emb, task, cg):
     ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=1,
                          key_value_memory_dict={k: tuple(t[slot:slot + 1] for t in v) for k, v in c["pool"].items()})
     out = model(None, emb, position_ids=None, task=task, inference_params=ip, num_last_tokens=1)
+    return (out.t2i_logits if task == "t2i" else out.mmu_logits).squeeze(1)
+
+
+def _prefill_group(model, c, slots, embs, task):
+    """ONE right-padded prefill of several prompts -> logits (len(embs), vocab), row j read at the last position of prompt j.  The rows
+    run on the first rows of ONE staging cache (the states are batch-leading; it grows to the largest group seen);
+    InferenceParams.seq_lens makes every row's states those after its own length, and they are then copied into the pool rows `slots`.  Pad positions of the embedding buffer are zeros."""
+    g, dev = len(embs), embs[0].device
+    lens_h = [e.shape[1] for e in embs]
+    buf = torch.zeros(g, max(lens_h), embs[0].shape[-1], dtype=embs[0].dtype, device=dev)
+    for j, e in enumerate(embs):
+        buf[j, :lens_h[j]].copy_(e[0])
+    if c["staging"].get("rows", 0) < g:
+        c["staging"] = {"rows": g, "cache": model.allocate_inference_cache(g, c["max_seqlen"], c["dtype"])}
+    st = {k: tuple(t[:g] for t in v) for k, v in c["staging"]["cache"].items()}
+    ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=g, key_value_memory_dict=st,
+                         seq_lens=torch.tensor(lens_h, dtype=torch.int32).to(dev, non_blocking=True))
+    out = model(None, buf, position_ids=None, task=task, inference_params=ip, num_last_tokens=1)
+    rows = torch.tensor(slots, dtype=torch.long).to(dev, non_blocking=True)
+    for k in sorted(c["pool"]):
+        for dst, src in zip(c["pool"][k], st[k]):
+            dst.index_copy_(0, rows, src)
     return (out.t2i_logits if task == "t2i" else out.mmu_logits).squeeze(1)
 
 
@@ -150,7 +192,7 @@ def _save(c, slot, seqlen, pending_id, task):
 
 @torch.inference_mode()
 def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
-                  min_p=0.0, cg=True, return_states=False):
+                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0):
     """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
     generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
     model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
@@ -160,7 +202,12 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     left `state` (a DecodeState; 'mmu' only).  Its embeddings are the new turn's only; the slot continues from the state at position
     state.seqlen with [state.pending_id] + the new turn, and max_length counts the whole conversation's positions.  Its ids are
     input_ids followed by the sampled ids.  return_states=True: returns (ids_list, states_list), states_list[i] the DecodeState of
-    request i when it finished."""
+    request i when it finished.
+
+    prefill_batch > 1: up to that many plain requests (not continued ones) that are queued while as many slots are free are admitted
+    by one right-padded prefill (_prefill_group); admission stays FIFO, a continued request ends the group before it, and nothing
+    waits for a larger group.  prefill_bucket > 0 (with cg): prompts longer than generation.PREFILL_GRAPH_MAX_LEN replay a captured
+    prefill of their length rounded up to a multiple of it (_prefill).  With both at their defaults nothing changes."""
     n = len(requests)
     if n == 0:
         return ([], []) if return_states else []
@@ -169,6 +216,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
         raise ValueError(f"decode_ragged: {len(lens)} max_length values for {n} requests")
     if max_batch < 1:
         raise ValueError("decode_ragged: max_batch must be >= 1")
+    if prefill_batch < 1 or prefill_bucket < 0:
+        raise ValueError("decode_ragged: prefill_batch must be >= 1 and prefill_bucket >= 0")
     for r in requests:
         if len(r) not in (2, 3):
             raise ValueError("decode_ragged: every request is (input_ids, input_embeddings) or (input_ids, input_embeddings, state)")
@@ -209,28 +258,40 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
 
     while queue or live:
         while queue and free:                                  # admit FIFO into free slots
-            i = queue.popleft()
-            s = free.pop(0)
-            ids, emb = requests[i][:2]
-            if len(requests[i]) == 3:
-                st = requests[i][2]
-                off = st.seqlen + 1 + emb.shape[1]
-                if n_pos is not None and off > n_pos:
-                    raise IndexError(f"decode_ragged: request {i} continues to position {off - 1}, outside the {task} position table of "
-                                     f"{n_pos} rows (StackConfig.{{t2i,mmu}}_positions)")
-                tok = draw(_extend(model, c, s, st, emb, task))
+            grp = []                                           # the plain requests at the head of the queue that find a slot now
+            while prefill_batch > 1 and len(grp) < min(prefill_batch, len(free), len(queue)) and len(requests[queue[len(grp)]]) == 2:
+                grp.append(queue[len(grp)])
+            if len(grp) > 1:
+                for _ in grp:
+                    queue.popleft()
+                slots = [free.pop(0) for _ in grp]
+                toks = draw(_prefill_group(model, c, slots, [requests[i][1] for i in grp], task))   # (len(grp),)
+                toks_h = toks.tolist() if check_eos else [None] * len(grp)
+                admitted = [(i, s, requests[i][1].shape[1], toks[j:j + 1], toks_h[j]) for j, (i, s) in enumerate(zip(grp, slots))]
             else:
-                tok = draw(_prefill(model, c, s, emb, task, cg))   # (1,)
-                off = emb.shape[1]
-            last[s:s + 1].copy_(tok)
-            drawn.append(tok)
-            pieces[i].append(n_drawn)
-            n_drawn += 1
-            tok_h = int(tok[0]) if check_eos else None
-            if finished(i, tok_h, off):
-                retire(i, s, off, tok_h)
-            else:
-                live.append([i, s, off])
+                i = queue.popleft()
+                s = free.pop(0)
+                ids, emb = requests[i][:2]
+                if len(requests[i]) == 3:
+                    st = requests[i][2]
+                    off = st.seqlen + 1 + emb.shape[1]
+                    if n_pos is not None and off > n_pos:
+                        raise IndexError(f"decode_ragged: request {i} continues to position {off - 1}, outside the {task} position table of "
+                                         f"{n_pos} rows (StackConfig.{{t2i,mmu}}_positions)")
+                    tok = draw(_extend(model, c, s, st, emb, task))
+                else:
+                    tok = draw(_prefill(model, c, s, emb, task, cg, prefill_bucket, n_pos))   # (1,)
+                    off = emb.shape[1]
+                admitted = [(i, s, off, tok, int(tok[0]) if check_eos else None)]
+            for i, s, off, tok, tok_h in admitted:
+                last[s:s + 1].copy_(tok)
+                drawn.append(tok)
+                pieces[i].append(n_drawn)
+                n_drawn += 1
+                if finished(i, tok_h, off):
+                    retire(i, s, off, tok_h)
+                else:
+                    live.append([i, s, off])
         if not live:
             continue
         if n_pos is not None:

@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _capi as K
-from ._lib import get_lib, require_device, slot_indices
+from ._lib import forward_only_seq_lens, get_lib, require_device, slot_indices
 
 
 def _act_flag(activation):
@@ -22,15 +22,16 @@ def _act_flag(activation):
 class CausalConv1dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias=None, initial_states=None, return_final_states=False, final_states_out=None,
-                activation=None):
+                activation=None, seq_lens=None):
         lib = get_lib()
-        require_device(lib, x, weight, bias, initial_states, final_states_out)
+        require_device(lib, x, weight, bias, initial_states, final_states_out, seq_lens)
         if x.dim() != 3:
             raise ValueError("causal_conv1d_fn: x must be (batch, dim, seqlen)")
         if x.stride(2) != 1 and x.stride(1) != 1:
             x = x.contiguous()
         B, Cc, L = x.shape
         W = weight.shape[1]
+        seq_lens = slot_indices(seq_lens, B, x.device, "seq_lens")
         if initial_states is not None and initial_states.dtype != x.dtype:
             initial_states = initial_states.to(x.dtype)
         out = torch.empty_like(x)  # keeps x's (channel-last or channel-first) strides
@@ -42,7 +43,7 @@ class CausalConv1dFn(torch.autograd.Function):
                 fin = torch.empty(B, W - 1, Cc, dtype=x.dtype, device=x.device).transpose(1, 2)
         if x.numel() > 0:
             p = K.Conv1dFwd(x=K.T(x), weight=K.T(weight), bias=K.T(bias), initial_states=K.T(initial_states), out=K.T(out),
-                            final_states=K.T(fin), silu=_act_flag(activation))
+                            final_states=K.T(fin), silu=_act_flag(activation), seq_lens=K.T(seq_lens))
             K.run(lib, "omk_causal_conv1d_fwd", p, x)
         ctx.save_for_backward(x, weight, bias, initial_states)
         ctx.silu = _act_flag(activation)
@@ -72,16 +73,20 @@ class CausalConv1dFn(torch.autograd.Function):
                             dx=K.T(dx), dweight=K.T(dw), dbias=K.T(db), dinitial_states=K.T(dinit), silu=ctx.silu)
             ws = K.workspace(lib, "omk_causal_conv1d_bwd_workspace_bytes", p, x)   # partial dw / db rows: no atomics, the same sums on every run
             K.run(lib, "omk_causal_conv1d_bwd", p, x)
-        return dx, dw.to(weight.dtype), None if bias is None else db.to(bias.dtype), dinit, None, None, None
+        return dx, dw.to(weight.dtype), None if bias is None else db.to(bias.dtype), dinit, None, None, None, None
 
 
 def causal_conv1d_fn(x, weight, bias=None, seq_idx=None, initial_states=None, return_final_states=False,
-                     final_states_out=None, activation=None):
+                     final_states_out=None, activation=None, seq_lens=None):
     """x: (batch, dim, seqlen); weight: (dim, width); bias: (dim,); initial_states: (batch, dim, width-1).
-    Returns out (batch, dim, seqlen) [, final_states (batch, dim, width-1)]."""
+    Returns out (batch, dim, seqlen) [, final_states (batch, dim, width-1)].
+    seq_lens (extension, forward-only): optional (batch,) int32 (int64 is cast) with 0 <= seq_lens[b] <= seqlen, the lengths of
+    right-padded rows: final_states[b] then holds the inputs in front of position seq_lens[b] instead of seqlen; out is unchanged.
+    The values are never read on the host (graph-capturable)."""
     if seq_idx is not None:
         raise NotImplementedError("seq_idx never reaches the mixer in OmniMamba (mixer_seq_simple.py:375,408-420)")
-    return CausalConv1dFn.apply(x, weight, bias, initial_states, return_final_states, final_states_out, activation)
+    forward_only_seq_lens(seq_lens, x, weight, bias, initial_states)
+    return CausalConv1dFn.apply(x, weight, bias, initial_states, return_final_states, final_states_out, activation, seq_lens)
 
 
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, cache_seqlens=None,

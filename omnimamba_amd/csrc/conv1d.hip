@@ -22,7 +22,16 @@ struct ConvArgs {
   int64_t xsb, xsc, xsl, osb, osc, osl, isb, isc, isl, fsb, fsc, fsl, dosb, dosc, dosl, dxsb, dxsc, dxsl, disb, disc, disl;
   int64_t wsc, wsk;
   int B, C, L, W, silu, wdt, bdt, idt, fdt;
+  const int* lens;   // optional (B): final_states[b] ends at position lens[b] instead of L (right-padded rows of a ragged prefill); read by
+                     // conv1d_final_states_kernel only -- with it the channel-last kernels run without their epilogue (omk_causal_conv1d_fwd)
 };
+
+// where row b's final_states end: its own length (clamped to 0 .. L, so a bad value cannot address outside x), or L
+__device__ __forceinline__ int conv_fin_end(const ConvArgs& a, int b) {
+  if (!a.lens) return a.L;
+  const int n = a.lens[b];
+  return n < 0 ? 0 : (n > a.L ? a.L : n);
+}
 
 __device__ __forceinline__ float silu_grad(float pre) {
   float s = sigmoid_fast(pre);
@@ -320,7 +329,7 @@ __global__ void conv1d_final_states_kernel(ConvArgs a) {
   const int Wm = a.FW;
   if (g >= (int64_t)a.B * a.C * Wm) return;
   const int c = (int)(g % a.C), j = (int)((g / a.C) % Wm), b = (int)(g / ((int64_t)a.C * Wm));
-  float v = conv_in<T>(a, (const T*)a.x, b, c, a.L + j - Wm);
+  float v = conv_in<T>(a, (const T*)a.x, b, c, conv_fin_end(a, b) + j - Wm);
   store_rt(a.fin, (int64_t)b * a.fsb + (int64_t)c * a.fsc + (int64_t)j * a.fsl, a.fdt, v);
 }
 
@@ -863,8 +872,17 @@ extern "C" int omk_causal_conv1d_fwd(const OmkConv1dFwd* p, omk_stream stream) {
     a.FW = (int)p->final_states.shape[2];
     a.fsb = p->final_states.stride[0]; a.fsc = p->final_states.stride[1]; a.fsl = p->final_states.stride[2];
   }
+  if (present(p->seq_lens)) {
+    OMK_REQUIRE(p->seq_lens.dtype == OMK_I32 && p->seq_lens.ndim == 1 && p->seq_lens.shape[0] == a.B && p->seq_lens.stride[0] == 1, "causal_conv1d_fwd: seq_lens must be dense int32 (B)");
+    a.lens = (const int*)p->seq_lens.data;
+  }
   if ((int64_t)a.B * a.C * a.L == 0) return OMK_OK;
   const bool fast = cl_fast_ok(p->x, a.C) && cl_fast_ok(p->out, a.C);   // (fp32 too: the prefill of the reference's fp32 inference ran the scalar kernel at 0.85 TB/s)
+  // Per-row lengths: the final states come from conv1d_final_states_kernel (B * C * state_len threads, one launch of a few us) behind the
+  // channel-last kernels too, whose epilogues are left out.  Reading lens[b] inside those epilogues cost the per-thread tile kernel two
+  // VGPRs in every instantiation and its bf16 width-2 one a wave per SIMD (80 -> 82 VGPRs, occupancy 6 -> 5) for every caller, ragged or not.
+  void* const fin_all = a.fin;
+  if (a.lens) a.fin = nullptr;
   if (fast) {
     // 4 channels (8 bytes) per lane and 8 tokens per load group: 100 VGPRs / 4 waves per SIMD measured fastest on the
     // 1.3B shape (141 us vs 171 us for 8 channels per lane, which needs 158 VGPRs)
@@ -903,11 +921,12 @@ extern "C" int omk_causal_conv1d_fwd(const OmkConv1dFwd* p, omk_stream stream) {
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     int lf = (a.xsl == 1 && a.xsc != 1) ? 1 : 0;
     OMK_DISPATCH_DTYPE(p->x.dtype, T, OMK_LAUNCH((conv1d_fwd_generic_kernel<T>), grid, block, 0, stream, a, lf));
-    if (a.fin) {
-      int64_t m = (int64_t)a.B * a.C * a.FW;
-      dim3 g2((unsigned)((m + 255) / 256));
-      OMK_DISPATCH_DTYPE(p->x.dtype, T, OMK_LAUNCH((conv1d_final_states_kernel<T>), g2, block, 0, stream, a));
-    }
+  }
+  a.fin = fin_all;
+  if (a.fin && (!fast || a.lens)) {
+    int64_t m = (int64_t)a.B * a.C * a.FW;
+    dim3 g2((unsigned)((m + 255) / 256)), block(256);
+    OMK_DISPATCH_DTYPE(p->x.dtype, T, OMK_LAUNCH((conv1d_final_states_kernel<T>), g2, block, 0, stream, a));
   }
   return finish_launch("causal_conv1d_fwd");
 }

@@ -19,6 +19,8 @@ struct DtPrepArgs {
   const void* dt; const void* bias; float* dtp; float* dsoft;
   int64_t sb, sl, sh; int B, L, H, dt_dt, bias_dt, softplus; float lo, hi;
   float* zero[3]; int nzero[3];   // backward: the small accumulators (dA, dD, d dt_bias) cleared by workgroup 0 -- three 4 us launches less
+  const int* lens;   // forward, optional (B): tokens t >= lens[b] leave as dt' = +0 -- exp(A 0) = 1 and 0 B x: the state of a right-padded row
+                     // stays what it was after lens[b] tokens in every scan kernel (they treat the tokens behind L the same way)
 };
 // block = 32 tokens x 32 heads of one batch element: loads follow the unit-stride head dimension of (B, L, H), the stores
 // the unit-stride token dimension of (B, H, L); the tile turns in LDS (a direct per-element mapping writes 4 bytes per
@@ -35,6 +37,7 @@ __global__ __launch_bounds__(256) void ssd_dt_prep_kernel(DtPrepArgs a) {
       for (int i = threadIdx.x; i < a.nzero[k]; i += 256) a.zero[k][i] = 0.f;
   }
   const float bias = (a.bias && h < a.H) ? load_rt(a.bias, h, a.bias_dt) : 0.f;
+  const int len = a.lens ? a.lens[b] : a.L;
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const int t = lb * 32 + ty + 8 * j;
@@ -51,6 +54,7 @@ __global__ __launch_bounds__(256) void ssd_dt_prep_kernel(DtPrepArgs a) {
       }
       if (v < a.lo) { v = a.lo; d = 0.f; }
       if (v > a.hi) { v = a.hi; d = 0.f; }
+      if (t >= len) { v = 0.f; d = 0.f; }
     }
     sv[ty + 8 * j][tx] = v;
     sd[ty + 8 * j][tx] = d;
@@ -95,6 +99,7 @@ __global__ __launch_bounds__(256) void ssd_dt_prep_vec_kernel(DtPrepArgs a) {
     load_vec<T, 2>(src + (int64_t)(t < a.L ? t : a.L - 1) * a.sl, raw[j]);
   }
   const bool want_d = a.dsoft != nullptr;
+  const int len = a.lens ? a.lens[b] : a.L;
 #pragma unroll
   for (int j = 0; j < TOK / 8; j++) {
     const int tl = 8 * j + tr, t = lb * TOK + tl;
@@ -110,6 +115,7 @@ __global__ __launch_bounds__(256) void ssd_dt_prep_vec_kernel(DtPrepArgs a) {
         }
         if (v < a.lo) { v = a.lo; d = 0.f; }
         if (v > a.hi) { v = a.hi; d = 0.f; }
+        if (t >= len) { v = 0.f; d = 0.f; }
         v2[e] = v; d2[e] = d;
       }
     }
@@ -532,9 +538,10 @@ static int ssd_check_common(const OmkTensor& x, const OmkTensor& dt, const OmkTe
 }
 
 static void launch_dt_prep(const OmkTensor& dt, const OmkTensor& dtb, const SsdDims& d, float* dtp, float* dsoft, int softplus, float lo, float hi, omk_stream stream,
-                           float* z0 = nullptr, int64_t n0 = 0, float* z1 = nullptr, int64_t n1 = 0, float* z2 = nullptr, int64_t n2 = 0) {
+                           const int* lens = nullptr, float* z0 = nullptr, int64_t n0 = 0, float* z1 = nullptr, int64_t n1 = 0, float* z2 = nullptr, int64_t n2 = 0) {
   DtPrepArgs a = {};
   a.zero[0] = z0; a.nzero[0] = z0 ? (int)n0 : 0; a.zero[1] = z1; a.nzero[1] = z1 ? (int)n1 : 0; a.zero[2] = z2; a.nzero[2] = z2 ? (int)n2 : 0;
+  a.lens = lens;
   a.dt = dt.data; a.bias = dtb.data; a.dtp = dtp; a.dsoft = dsoft; a.sb = dt.stride[0]; a.sl = dt.stride[1]; a.sh = dt.stride[2];
   a.B = d.B; a.L = d.L; a.H = d.H; a.dt_dt = dt.dtype; a.bias_dt = dtb.dtype; a.softplus = softplus; a.lo = lo;
   a.hi = hi > 0.f ? hi : INFINITY;
@@ -624,6 +631,10 @@ extern "C" int omk_ssd_scan_fwd(const OmkSsdFwd* p, omk_stream stream) {
     if (state_only || present(p->z) || present(p->out_x) || present(p->window_states) || (p->flags & OMK_SSD_PRECISE) || p->force_generic || p->x.dtype != OMK_BF16)
       return fail(OMK_EUNSUPPORTED, "ssd_scan_fwd: the fused conv exists for the plain bf16 forward only (no gate / pre-gate copy / window states / PRECISE): run omk_causal_conv1d_fwd and the scan separately");
   }
+  if (present(p->seq_lens)) {
+    OMK_REQUIRE(p->seq_lens.dtype == OMK_I32 && p->seq_lens.ndim == 1 && p->seq_lens.shape[0] == d.B && p->seq_lens.stride[0] == 1, "ssd_scan_fwd: seq_lens must be dense int32 (B)");
+    OMK_REQUIRE(!state_only && !present(p->window_states), "ssd_scan_fwd: seq_lens goes with neither the state-only pass nor window_states (training paths)");
+  }
   if ((int64_t)d.B * d.L * d.H * d.P == 0) return OMK_OK;
   kernels_reset();
   float* dtp = (float*)p->workspace;
@@ -631,7 +642,7 @@ extern "C" int omk_ssd_scan_fwd(const OmkSsdFwd* p, omk_stream stream) {
   // (tried in round 2: the scan reading the raw (B, L, H) dt itself and applying bias / softplus / clamp in its scalar pass, to
   // save this 16 us launch -- 280 us against 236 + 16 us: the 2-byte loads at stride H are 64 requests per wave and chunk and the
   // softplus lands on wave 0's critical path between the publish and the barrier.  Not kept.)
-  launch_dt_prep(p->dt, p->dt_bias, d, dtp, nullptr, p->dt_softplus, p->dt_min, p->dt_max, stream);
+  launch_dt_prep(p->dt, p->dt_bias, d, dtp, nullptr, p->dt_softplus, p->dt_min, p->dt_max, stream, (const int*)p->seq_lens.data);
   g.mode = GS_Y; g.U = make_src(p->x, false); g.K = make_src(p->Bm, true); g.Q = make_src(p->Cm, true);
   if (present(p->z)) g.Z = make_src(p->z, false);
   g.dtp = dtp; g.A = (const float*)p->A.data; g.B = d.B; g.H = d.H; g.G = d.G; g.L = d.L; g.DU = d.P; g.DK = d.N; g.reverse = 0; g.w_is_dt = 1;
@@ -836,7 +847,7 @@ extern "C" int omk_ssd_scan_bwd(const OmkSsdBwd* p, omk_stream stream) {
   BwdWs w = bwd_ws_layout(p->workspace, d.B, d.L, d.H, d.P, d.G, d.N, has_dfin, path, cp && bwd_cp_direct(p, d));
   const int64_t bhl = (int64_t)d.B * d.H * d.L, blgn = (int64_t)d.B * d.L * d.G * d.N;
   if (!mfma) { launch_zero(w.e, bhl, stream); launch_zero(w.wsum, bhl, stream); launch_zero(w.dB32, blgn, stream); launch_zero(w.dC32, blgn, stream); }
-  launch_dt_prep(p->dt, p->dt_bias, d, w.dtp, w.dsoft, p->dt_softplus, p->dt_min, p->dt_max, stream, (float*)p->dA.data, d.H,
+  launch_dt_prep(p->dt, p->dt_bias, d, w.dtp, w.dsoft, p->dt_softplus, p->dt_min, p->dt_max, stream, nullptr, (float*)p->dA.data, d.H,
                  present(p->dD) ? (float*)p->dD.data : nullptr, present(p->dD) ? numel(p->dD) : 0,
                  present(p->ddt_bias) ? (float*)p->ddt_bias.data : nullptr, d.H);
   const float* A = (const float*)p->A.data;

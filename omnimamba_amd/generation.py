@@ -26,6 +26,10 @@ class InferenceParams:
     # continuous batching (omnimamba_amd/batch_decode.py): int32 (batch,) slot of each step row in the cache's state pool, -1 = an empty
     # row.  Set, the decode step reads and writes pool rows through it; None, row b is cache row b as before.
     state_indices: Optional[torch.Tensor] = None
+    # ragged prefill: int32 (batch,) number of valid positions of every right-padded row of a prefill (seqlen_offset == 0).  Set, the
+    # caches hold the states after seq_lens[b] positions of row b and the head reads row seq_lens[b] - 1; read on the device only,
+    # so one captured prefill serves every length up to its buffer's.  None: every row is as long as the batch.
+    seq_lens: Optional[torch.Tensor] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen
@@ -44,12 +48,18 @@ def _top_p_filter_(logits, top_p):
 
 
 MAX_PREFILL_GRAPHS = 4
+PREFILL_GRAPH_MAX_LEN = 512     # longest prompt captured at its exact length
+
+
+def _prefill_graphs_enabled():
+    import os
+    return os.environ.get("OMK_PREFILL_GRAPH", "1") != "0"
 
 
 def _prefill_graph_ok(seqlen):
-    """Short prompts are launch bound: capture them.  Long ones (MMU prompts) run eager -- one graph per length would pin memory."""
-    import os
-    return os.environ.get("OMK_PREFILL_GRAPH", "1") != "0" and seqlen <= 512
+    """Short prompts are launch bound: capture them.  Long ones (MMU prompts) run eager -- one graph per length would pin memory
+    (batch_decode's prefill_bucket captures them per length bucket instead: PrefillGraph(ragged=True))."""
+    return _prefill_graphs_enabled() and seqlen <= PREFILL_GRAPH_MAX_LEN
 
 
 def _stream_base():
@@ -150,12 +160,18 @@ class StepGraph:
 class PrefillGraph:
     """The captured PREFILL of a fixed (batch, prompt length): one replay instead of ~20 eager launches per layer (the T2I prompt is
     always the same length -- caption of 73 ids, omnimamba.py:264 -- and at 72 tokens the prefill is launch bound: 16 ms eager for
-    the 1.3B stack).  Static embedding buffer refreshed by copy_, the caches filled in place by the fused prefill node."""
+    the 1.3B stack).  Static embedding buffer refreshed by copy_, the caches filled in place by the fused prefill node.
+    ragged=True: `seqlen` is the length of a BUCKET -- a static int32 seq_lens buffer (InferenceParams.seq_lens) carries the true
+    length of every row, read by the kernels on the device, so one graph serves every prompt of up to `seqlen` positions."""
 
-    def __init__(self, model, inference_params, batch_size, seqlen, d_model, task, dtype, n_warmups=2, mempool=None):
+    def __init__(self, model, inference_params, batch_size, seqlen, d_model, task, dtype, n_warmups=2, mempool=None, ragged=False):
         dev = next(iter(model.parameters())).device
         self.ip = inference_params
         self.emb = torch.zeros(batch_size, seqlen, d_model, dtype=dtype, device=dev)
+        self.seq_lens = None
+        if ragged:
+            self.seq_lens = torch.full((batch_size,), seqlen, dtype=torch.int32, device=dev)
+            inference_params.seq_lens = self.seq_lens
         off = inference_params.seqlen_offset
         inference_params.seqlen_offset = 0
 
@@ -176,7 +192,13 @@ class PrefillGraph:
         inference_params.seqlen_offset = off
 
     def run(self, embeddings):
-        self.emb.copy_(embeddings)
+        if self.seq_lens is not None:      # right-padded into the bucket: zeros behind the prompt, its length into the static buffer
+            n = embeddings.shape[1]
+            self.emb[:, :n].copy_(embeddings)
+            self.emb[:, n:].zero_()
+            self.seq_lens.fill_(n)
+        else:
+            self.emb.copy_(embeddings)
         self.graph.replay()
         return self.logits.clone()
 

@@ -119,8 +119,14 @@ class Mamba2(nn.Module):
             batch = batch_seqlen // seqlen
 
         conv_state, ssm_state = None, None
+        # ragged prefill: int32 (batch,) lengths of right-padded rows -- the caches end up as after seq_lens[b] tokens of row b
+        seq_lens = None
         if inference_params is not None:
             conv_state, ssm_state = self._get_states_from_cache(inference_params, batch)
+            seq_lens = getattr(inference_params, "seq_lens", None)
+            if seq_lens is not None and inference_params.seqlen_offset > 0:
+                raise NotImplementedError("InferenceParams.seq_lens belongs to the prefill (seqlen_offset == 0): extending and stepping "
+                                          "rows of different lengths is not implemented")
             if inference_params.seqlen_offset > 0 and seqlen > 1:
                 return self._extend(u, batch, seqlen, seqlen_og, conv_state, ssm_state, inference_params)
             if inference_params.seqlen_offset > 0:
@@ -149,7 +155,8 @@ class Mamba2(nn.Module):
                 rmsnorm_weight=self.norm.weight if self.rmsnorm else None,
                 rmsnorm_eps=self.norm.eps if self.rmsnorm else 1e-6, outproj_weight=self.out_proj.weight,
                 outproj_bias=self.out_proj.bias, headdim=None if self.D_has_hdim else self.headdim,
-                ngroups=self.ngroups, norm_before_gate=self.norm_before_gate, conv_state_out=conv_state, **dt_limit_kwargs)
+                ngroups=self.ngroups, norm_before_gate=self.norm_before_gate, conv_state_out=conv_state, seq_lens=seq_lens,
+                **dt_limit_kwargs)
             ssm_state.copy_(last_state)
             if seqlen_og is not None:
                 out = out.reshape(batch * seqlen, -1)
@@ -168,18 +175,23 @@ class Mamba2(nn.Module):
 
         z0, x0, z, xBC, dt = torch.split(
             zxbcdt, [d_mlp, d_mlp, self.d_ssm, self.d_ssm + 2 * self.ngroups * self.d_state, self.nheads], dim=-1)
-        if conv_state is not None:
-            # conv_state <- last d_conv columns of the pre-conv xBC (left zero padded): fully overwritten
-            xBC_t = xBC.transpose(1, 2)
-            conv_state.copy_(F.pad(xBC_t, (self.d_conv - xBC_t.shape[-1], 0)))
-        xBC = causal_conv1d_fn(xBC.transpose(1, 2), self.conv1d.weight.squeeze(1), self.conv1d.bias,
-                               activation=self.activation).transpose(1, 2)
+        if conv_state is not None and seq_lens is not None:
+            # per row: the d_conv pre-conv inputs in front of position seq_lens[b], written by conv1d_final_states_kernel behind the conv
+            xBC = causal_conv1d_fn(xBC.transpose(1, 2), self.conv1d.weight.squeeze(1), self.conv1d.bias, return_final_states=True,
+                                   final_states_out=conv_state, activation=self.activation, seq_lens=seq_lens)[0].transpose(1, 2)
+        else:
+            if conv_state is not None:
+                # conv_state <- last d_conv columns of the pre-conv xBC (left zero padded): fully overwritten
+                xBC_t = xBC.transpose(1, 2)
+                conv_state.copy_(F.pad(xBC_t, (self.d_conv - xBC_t.shape[-1], 0)))
+            xBC = causal_conv1d_fn(xBC.transpose(1, 2), self.conv1d.weight.squeeze(1), self.conv1d.bias,
+                                   activation=self.activation).transpose(1, 2)
         x, B, C = torch.split(xBC, [self.d_ssm, self.ngroups * self.d_state, self.ngroups * self.d_state], dim=-1)
         y = mamba_chunk_scan_combined(
             x.unflatten(-1, (self.nheads, self.headdim)), dt, A, B.unflatten(-1, (self.ngroups, self.d_state)),
             C.unflatten(-1, (self.ngroups, self.d_state)), chunk_size=self.chunk_size, D=self._D(),
             z=z.unflatten(-1, (self.nheads, self.headdim)) if not self.rmsnorm else None, dt_bias=self.dt_bias,
-            dt_softplus=True, return_final_states=ssm_state is not None, **dt_limit_kwargs)
+            dt_softplus=True, return_final_states=ssm_state is not None, seq_lens=seq_lens, **dt_limit_kwargs)
         if ssm_state is not None:
             y, last_state = y
             ssm_state.copy_(last_state)
@@ -198,6 +210,8 @@ class Mamba2(nn.Module):
         the chunked scan, EXTEND_SCAN_MAX_T) -> gated norm -> out_proj, as the prefill's unfused branch."""
         if getattr(inference_params, "state_indices", None) is not None:
             raise NotImplementedError("Mamba2 extend runs one cache row per sequence (a view of its slot), not state_indices")
+        if getattr(inference_params, "seq_lens", None) is not None:
+            raise NotImplementedError("Mamba2 extend takes rows of one length: InferenceParams.seq_lens belongs to the prefill")
         if torch.is_grad_enabled():
             raise NotImplementedError("Mamba2 extend is an inference path (no autograd through the cached states)")
         zxbcdt = linear(u, self.in_proj.weight, self.in_proj.bias) if type(self.in_proj) is nn.Linear else self.in_proj(u)

@@ -205,33 +205,38 @@ class OmniMambaPath(nn.Module):
 
     @torch.no_grad()
     def mmu_generate_batch(self, images_feat_list, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1,
-                           top_p=0.0, max_batch=8, cg=True, return_states=False):
+                           top_p=0.0, max_batch=8, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0):
         """Many MMU requests at once (continuous batching, omnimamba_amd/batch_decode.py): request i is images_feat_list[i] (1, n_img,
         fused_vision_dim) with the question input_ids_list[i] (1, T_i), its prompt built as in mmu_generate.  max_length: an int or one
         per request.  Returns one id tensor per request, each equal to what mmu_generate returns for that request alone.
-        return_states=True: returns (ids, states), states[i] the batch_decode.DecodeState that ``mmu_continue`` takes for a follow-up."""
+        return_states=True: returns (ids, states), states[i] the batch_decode.DecodeState that ``mmu_continue`` takes for a follow-up.
+        prefill_batch / prefill_bucket: batched admission and bucketed prefill graphs of decode_ragged (both off by default; 8 and 128
+        are the suggested values for MMU prompts; DESIGN.md 4.5 says what was measured)."""
         from .batch_decode import decode_ragged
         if len(images_feat_list) != len(input_ids_list):
             raise ValueError("mmu_generate_batch: one images_feat per question")
         reqs = [self._mmu_prompt(f, q) for f, q in zip(images_feat_list, input_ids_list)]
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
-                             top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=return_states)
+                             top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=return_states,
+                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket)
 
     @torch.no_grad()
     def mmu_continue(self, states, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1, top_p=0.0, max_batch=8,
-                     cg=True):
+                     cg=True, prefill_batch=1, prefill_bucket=0):
         """The follow-up turn of each conversation: states[i] is the DecodeState its previous turn returned (mmu_generate_batch or
         mmu_continue with states), input_ids_list[i] (1, T_i) the new turn's ids, already templated by the caller.  The conversation is
         not re-prefilled: the state takes the previous turn's last sampled id and the new ids (text only, embedded with
         embed_input_ids), then decodes.  max_length: an int or one per conversation, counted over the whole conversation's positions
         as in mmu_generate on the full prompt.  Returns (ids, states): ids[i] the new ids followed by the generated ids, states[i] the
-        DecodeState for the turn after."""
+        DecodeState for the turn after.  prefill_batch / prefill_bucket are accepted and passed on; a continued request is extended, never
+        prefilled, so they change nothing here yet."""
         from .batch_decode import decode_ragged
         if len(states) != len(input_ids_list):
             raise ValueError("mmu_continue: one state per conversation")
         reqs = [(q, self.llm_backbone.embed_input_ids(q), st) for st, q in zip(states, input_ids_list)]
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
-                             top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=True)
+                             top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=True,
+                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket)
 
     # ---- T2I generation (omnimamba.py:311-337 minus the VQ decoder network)
     @torch.no_grad()

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import _capi as K
 from . import _prof
-from ._lib import get_lib, require_device
+from ._lib import forward_only_seq_lens, get_lib, require_device, slot_indices
 from .causal_conv1d import causal_conv1d_fn
 from .layernorm_gated import rmsnorm_fn
 from .linear import frozen_cast, weight_grad
@@ -65,11 +65,16 @@ def save_window_states_enabled() -> bool:
 
 def ssd_scan_fwd(x, dt, A, B, C, D=None, z=None, dt_bias=None, initial_states=None, dt_softplus=False,
                  dt_limit=(0.0, _INF), return_final_states=False, want_out_x=False, chunk_size=256,
-                 force_generic=False, save_window_states=False, flags=None):
+                 force_generic=False, save_window_states=False, flags=None, seq_lens=None):
     """Raw (non-autograd) forward: returns (out, out_x | None, final_states | None), with save_window_states=True a fourth
-    element: the opaque window-state tensor omk_ssd_scan_bwd takes (None when this forward cannot produce it)."""
+    element: the opaque window-state tensor omk_ssd_scan_bwd takes (None when this forward cannot produce it).
+    seq_lens: optional (batch,) int32 (int64 is cast), 0 <= seq_lens[b] <= seqlen, the lengths of right-padded rows: tokens behind
+    seq_lens[b] leave row b's state alone, so final_states[b] is the state after seq_lens[b] tokens; out behind a row's length is
+    finite and otherwise unspecified (OmkSsdFwd.seq_lens).  Never read on the host."""
     lib = get_lib()
-    require_device(lib, x, dt, A, B, C, D, z, dt_bias, initial_states)
+    require_device(lib, x, dt, A, B, C, D, z, dt_bias, initial_states, seq_lens)
+    if seq_lens is not None and save_window_states:
+        raise NotImplementedError("seq_lens is forward-only (ragged prefill): a training forward that saves window states takes none")
     x, B, C, z = _last_contig(x), _last_contig(B), _last_contig(C), _last_contig(z)
     if B.dtype != x.dtype:
         B = B.to(x.dtype)
@@ -80,6 +85,7 @@ def ssd_scan_fwd(x, dt, A, B, C, D=None, z=None, dt_bias=None, initial_states=No
     A = A.float().contiguous()
     Bsz, L, H, P = x.shape
     N = B.shape[-1]
+    seq_lens = slot_indices(seq_lens, Bsz, x.device, "seq_lens")
     out = torch.empty(Bsz, L, H, P, dtype=x.dtype, device=x.device)
     out_x = torch.empty_like(out) if (want_out_x and z is not None) else None
     fin = torch.empty(Bsz, H, P, N, dtype=torch.float32, device=x.device) if return_final_states else None
@@ -89,7 +95,7 @@ def ssd_scan_fwd(x, dt, A, B, C, D=None, z=None, dt_bias=None, initial_states=No
                      initial_states=K.T(initial_states), out=K.T(out), out_x=K.T(out_x), final_states=K.T(fin),
                      dt_min=float(dt_limit[0]), dt_max=float(dt_limit[1]), dt_softplus=int(dt_softplus),
                      chunk_size=int(chunk_size), force_generic=int(force_generic),
-                     flags=int(current_scan_flags() if flags is None else flags) & ~K.SSD_SEQUENTIAL_BWD)
+                     flags=int(current_scan_flags() if flags is None else flags) & ~K.SSD_SEQUENTIAL_BWD, seq_lens=K.T(seq_lens))
         ws = K.workspace(lib, "omk_ssd_scan_fwd_workspace_bytes", p, x)  # noqa: F841
         if save_window_states:
             nbytes = lib.omk_ssd_scan_fwd_window_states_bytes(K.C.byref(p))
@@ -113,12 +119,14 @@ def fused_conv_scan_enabled() -> bool:
 
 
 def ssd_scan_fwd_fused_conv(xBC, dt, A, conv_weight, conv_bias, nheads, headdim, ngroups, d_state, D=None, dt_bias=None,
-                            dt_softplus=True, dt_limit=(0.0, _INF), return_final_states=False, conv_state_out=None, chunk_size=256):
+                            dt_softplus=True, dt_limit=(0.0, _INF), return_final_states=False, conv_state_out=None, chunk_size=256,
+                            seq_lens=None):
     """K2 fusion of the forward-only path (reference reach: models/stage2/generation.py:195-211 prefill,
     scripts/inference_mmu.py:137-147): xBC (batch, seqlen, d_ssm + 2 G N) is the PRE-conv slice of zxbcdt.  The 2 G N B / C channels go
     through a small conv launch into a dense buffer; the d_ssm x channels are convolved INSIDE the scan while it stages them
     (OmkSsdFwd.conv_weight) and never visit a conv output buffer.  conv_state_out (batch, d_ssm + 2 G N, state_len): filled with the
-    last pre-conv inputs like causal_conv1d_fn(..., final_states_out=) does.  Returns (y (batch, seqlen, nheads, headdim), final_states |
+    last pre-conv inputs like causal_conv1d_fn(..., final_states_out=) does; seq_lens (batch,) int32: the lengths of right-padded rows --
+    final_states and conv_state_out are those after seq_lens[b] tokens of row b (ssd_scan_fwd, causal_conv1d_fn).  Returns (y (batch, seqlen, nheads, headdim), final_states |
     None), or None when the kernel does not take this call (the caller then runs the separate ops) -- bit-identical results either way."""
     lib = get_lib()
     Bsz, L, Ct = xBC.shape
@@ -132,7 +140,8 @@ def ssd_scan_fwd_fused_conv(xBC, dt, A, conv_weight, conv_bias, nheads, headdim,
     # them (batch 4: + 7 us, batch 1: + 5 us; profiles/r06_k2_fusion.txt).  OMK_K2_MIN_WGS: developer override of the threshold.
     if Bsz * (H // 2) < int(os.environ.get("OMK_K2_MIN_WGS", "256")):
         return None
-    require_device(lib, xBC, dt, A, conv_weight, conv_bias, D, dt_bias)
+    require_device(lib, xBC, dt, A, conv_weight, conv_bias, D, dt_bias, seq_lens)
+    seq_lens = slot_indices(seq_lens, Bsz, xBC.device, "seq_lens")
     A = A.float().contiguous()
     x_pre = xBC[..., :d_ssm].unflatten(-1, (H, P))
     bc = torch.empty(Bsz, L, 2 * G * N, dtype=xBC.dtype, device=xBC.device)
@@ -144,11 +153,13 @@ def ssd_scan_fwd_fused_conv(xBC, dt, A, conv_weight, conv_bias, nheads, headdim,
     p = K.SsdFwd(x=K.T(x_pre), dt=K.T(dt), A=K.T(A), Bm=K.T(Bm), Cm=K.T(Cm), D=K.T(D), z=K.T(None), dt_bias=K.T(dt_bias),
                  initial_states=K.T(None), out=K.T(out), out_x=K.T(None), final_states=K.T(fin), dt_min=float(dt_limit[0]),
                  dt_max=float(dt_limit[1]), dt_softplus=int(dt_softplus), chunk_size=int(chunk_size), force_generic=0,
-                 flags=int(current_scan_flags()) & (K.SSD_KHILO | K.SSD_EVERY_CHUNK), conv_weight=K.T(wx), conv_bias=K.T(bx))
+                 flags=int(current_scan_flags()) & (K.SSD_KHILO | K.SSD_EVERY_CHUNK), conv_weight=K.T(wx), conv_bias=K.T(bx),
+                 seq_lens=K.T(seq_lens))
     ws = K.workspace(lib, "omk_ssd_scan_fwd_workspace_bytes", p, xBC)  # noqa: F841
     # the B / C conv first (the scan reads its output); its epilogue fills the B / C rows of conv_state_out
     pc = K.Conv1dFwd(x=K.T(xBC[..., d_ssm:].transpose(1, 2)), weight=K.T(wbc), bias=K.T(bbc), initial_states=K.T(None),
-                     out=K.T(bc.transpose(1, 2)), final_states=K.T(None if conv_state_out is None else conv_state_out[:, d_ssm:]), silu=1)
+                     out=K.T(bc.transpose(1, 2)), final_states=K.T(None if conv_state_out is None else conv_state_out[:, d_ssm:]), silu=1,
+                     seq_lens=K.T(seq_lens))
     fn = lib.omk_ssd_scan_fwd
     import ctypes as C_
     if lib.omk_is_emulated():
@@ -165,7 +176,11 @@ def ssd_scan_fwd_fused_conv(xBC, dt, A, conv_weight, conv_bias, nheads, headdim,
     if conv_state_out is not None:      # the x rows of the conv state: the last state_len pre-conv inputs (left zero padded)
         sl = conv_state_out.shape[-1]
         cs = conv_state_out[:, :d_ssm]
-        if L >= sl:
+        if seq_lens is not None:      # per row: the sl inputs in front of position seq_lens[b], gathered on the device
+            pos = seq_lens.long()[:, None] + torch.arange(-sl, 0, device=xBC.device)
+            rows = xBC[:, :, :d_ssm].gather(1, pos.clamp(0, L - 1)[..., None].expand(-1, -1, d_ssm))
+            cs.copy_(rows.masked_fill_((pos < 0)[..., None], 0).transpose(1, 2))
+        elif L >= sl:
             cs.copy_(xBC[:, L - sl:, :d_ssm].transpose(1, 2))
         else:
             cs[..., :sl - L].zero_()
@@ -294,14 +309,14 @@ class MambaChunkScanCombinedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, dt, A, B, C, chunk_size, D=None, z=None, dt_bias=None, initial_states=None, seq_idx=None,
                 cu_seqlens=None, dt_softplus=False, dt_limit=(0.0, _INF), return_final_states=False,
-                return_varlen_states=False):
+                return_varlen_states=False, seq_lens=None):
         if seq_idx is not None or cu_seqlens is not None or return_varlen_states:
             raise NotImplementedError("seq_idx / cu_seqlens / varlen states never reach the mixer in OmniMamba "
                                       "(models/stage2/mixer_seq_simple.py:375,408-420)")
-        keep_ws = any(ctx.needs_input_grad) and save_window_states_enabled()
+        keep_ws = any(ctx.needs_input_grad) and save_window_states_enabled() and seq_lens is None
         r = ssd_scan_fwd(x, dt, A, B, C, D=D, z=z, dt_bias=dt_bias, initial_states=initial_states, dt_softplus=dt_softplus,
                          dt_limit=dt_limit, return_final_states=return_final_states, want_out_x=True, chunk_size=chunk_size,
-                         save_window_states=keep_ws)
+                         save_window_states=keep_ws, seq_lens=seq_lens)
         (out, out_x, fin), wst = r[:3], (r[3] if keep_ws else None)
         ctx.scan_flags = current_scan_flags()
         ctx.save_for_backward(x, dt, A, B, C, D, z, dt_bias, initial_states, out_x if z is not None else out, wst)
@@ -326,18 +341,20 @@ class MambaChunkScanCombinedFn(torch.autograd.Function):
         return (g["dx"], g["ddt"].to(dt.dtype), g["dA"].to(A.dtype), g["dB"].to(B.dtype), g["dC"].to(C.dtype), None,
                 None if D is None else g["dD"].to(D.dtype), dz,
                 None if dt_bias is None else g["ddt_bias"].to(dt_bias.dtype),
-                None if dinit is None else dinit.to(initial_states.dtype), None, None, None, None, None, None)
+                None if dinit is None else dinit.to(initial_states.dtype), None, None, None, None, None, None, None)
 
 
 def mamba_chunk_scan_combined(x, dt, A, B, C, chunk_size, D=None, z=None, dt_bias=None, initial_states=None,
                               seq_idx=None, cu_seqlens=None, dt_softplus=False, dt_limit=(0.0, _INF),
-                              return_final_states=False, return_varlen_states=False):
+                              return_final_states=False, return_varlen_states=False, seq_lens=None):
     """x: (batch, seqlen, nheads, headdim); dt: (batch, seqlen, nheads); A: (nheads); B, C: (batch, seqlen, ngroups,
     dstate); D: (nheads, headdim) or (nheads,); z: like x; dt_bias: (nheads,); initial_states: (batch, nheads,
-    headdim, dstate).  Returns out like x [, final_states (batch, nheads, headdim, dstate) fp32]."""
+    headdim, dstate).  Returns out like x [, final_states (batch, nheads, headdim, dstate) fp32].
+    seq_lens (extension, forward-only): (batch,) int32 lengths of right-padded rows, see ssd_scan_fwd."""
+    forward_only_seq_lens(seq_lens, x, dt, A, B, C, D, z, dt_bias, initial_states)
     return MambaChunkScanCombinedFn.apply(x, dt, A, B, C, chunk_size, D, z, dt_bias, initial_states, seq_idx,
                                           cu_seqlens, dt_softplus, dt_limit, return_final_states,
-                                          return_varlen_states)
+                                          return_varlen_states, seq_lens)
 
 
 class MambaSplitConv1dScanCombinedFn(torch.autograd.Function):
@@ -350,7 +367,7 @@ class MambaSplitConv1dScanCombinedFn(torch.autograd.Function):
     def forward(ctx, zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, chunk_size, initial_states=None, seq_idx=None,
                 dt_limit=(0.0, _INF), return_final_states=False, activation="silu", rmsnorm_weight=None,
                 rmsnorm_eps=1e-6, outproj_weight=None, outproj_bias=None, headdim=None, ngroups=1,
-                norm_before_gate=True, conv_state_out=None):
+                norm_before_gate=True, conv_state_out=None, seq_lens=None):
         if seq_idx is not None:
             raise NotImplementedError("seq_idx never reaches the mixer in OmniMamba")
         if activation not in ("silu", "swish"):
@@ -375,7 +392,7 @@ class MambaSplitConv1dScanCombinedFn(torch.autograd.Function):
             # forward-only (prefill / inference): K2 fusion -- the x channels are convolved inside the scan's staging
             fused = ssd_scan_fwd_fused_conv(xBC, dt, A, conv1d_weight, conv1d_bias, H, P, G, N, D=D, dt_bias=dt_bias, dt_softplus=True,
                                             dt_limit=dt_limit, return_final_states=return_final_states, conv_state_out=conv_state_out,
-                                            chunk_size=chunk_size)
+                                            chunk_size=chunk_size, seq_lens=seq_lens)
         if fused is not None:
             y, fin = fused
             out_n = rmsnorm_fn(y.reshape(Bsz, L, d_ssm), rmsnorm_weight, None, z=z, eps=rmsnorm_eps, group_size=d_ssm // G,
@@ -390,16 +407,16 @@ class MambaSplitConv1dScanCombinedFn(torch.autograd.Function):
             # prefill: the conv kernel's epilogue leaves the last `state_len` pre-conv inputs in the
             # cache's conv_state (left zero padded when L < state_len) -- no separate pad / copy pass
             xBC_c = causal_conv1d_fn(xBC.transpose(1, 2), conv1d_weight, conv1d_bias, return_final_states=True,
-                                     final_states_out=conv_state_out, activation=activation)[0].transpose(1, 2)
+                                     final_states_out=conv_state_out, activation=activation, seq_lens=seq_lens)[0].transpose(1, 2)
         else:
             xBC_c = causal_conv1d_fn(xBC.transpose(1, 2), conv1d_weight, conv1d_bias, activation=activation).transpose(1, 2)
         x, Bm, Cm = torch.split(xBC_c, [d_ssm, G * N, G * N], dim=-1)
         zz = z.reshape(Bsz, L, H, P) if z.is_contiguous() else z.unflatten(-1, (H, P))
-        keep_ws = any(ctx.needs_input_grad) and save_window_states_enabled()
+        keep_ws = any(ctx.needs_input_grad) and save_window_states_enabled() and seq_lens is None
         r = ssd_scan_fwd(x.unflatten(-1, (H, P)), dt, A, Bm.unflatten(-1, (G, N)), Cm.unflatten(-1, (G, N)), D=D,
                          z=None if use_norm else zz, dt_bias=dt_bias, initial_states=initial_states,
                          dt_softplus=True, dt_limit=dt_limit, return_final_states=return_final_states,
-                         want_out_x=True, chunk_size=chunk_size, save_window_states=keep_ws)
+                         want_out_x=True, chunk_size=chunk_size, save_window_states=keep_ws, seq_lens=seq_lens)
         (y, y_x, fin), wst = r[:3], (r[3] if keep_ws else None)
         y_pre = y if (use_norm or y_x is None) else y_x        # pre-gate / pre-norm scan output (D*x included)
         if use_norm:
@@ -514,18 +531,21 @@ class MambaSplitConv1dScanCombinedFn(torch.autograd.Function):
         return (dzxbcdt, dw.to(conv_w.dtype), None if conv_b is None else db.to(conv_b.dtype),
                 g["ddt_bias"].to(dt_bias.dtype), g["dA"].to(A.dtype), g["dD"].to(D.dtype), None,
                 None if dinit is None else dinit.to(initial_states.dtype), None, None, None, None, d_norm_w, None,
-                d_outproj_w, d_outproj_b, None, None, None, None)
+                d_outproj_w, d_outproj_b, None, None, None, None, None)
 
 
 def mamba_split_conv1d_scan_combined(zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, chunk_size, initial_states=None,
                                      seq_idx=None, dt_limit=(0.0, _INF), return_final_states=False, activation="silu",
                                      rmsnorm_weight=None, rmsnorm_eps=1e-6, outproj_weight=None, outproj_bias=None,
-                                     headdim=None, ngroups=1, norm_before_gate=True, conv_state_out=None):
+                                     headdim=None, ngroups=1, norm_before_gate=True, conv_state_out=None, seq_lens=None):
     """zxbcdt: (batch, seqlen, 2 * dim + 2 * ngroups * dstate + nheads); conv1d_weight: (dim + 2 * ngroups * dstate,
     width); dt_bias, A: (nheads); D: (nheads, headdim) or (nheads,).  Returns out (batch, seqlen, d_model | dim)
     [, final_states (batch, nheads, headdim, dstate)].  conv_state_out (extension for the prefill of a cached decode): a
-    (batch, dim + 2 * ngroups * dstate, state_len >= width - 1) buffer the conv kernel fills with the last pre-conv inputs."""
+    (batch, dim + 2 * ngroups * dstate, state_len >= width - 1) buffer the conv kernel fills with the last pre-conv inputs.
+    seq_lens (extension, forward-only): (batch,) int32 lengths of right-padded rows -- final_states and conv_state_out are those after
+    seq_lens[b] tokens of row b."""
+    forward_only_seq_lens(seq_lens, zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, initial_states, rmsnorm_weight, outproj_weight, outproj_bias)
     return MambaSplitConv1dScanCombinedFn.apply(zxbcdt, conv1d_weight, conv1d_bias, dt_bias, A, D, chunk_size,
                                                 initial_states, seq_idx, dt_limit, return_final_states, activation,
                                                 rmsnorm_weight, rmsnorm_eps, outproj_weight, outproj_bias, headdim,
-                                                ngroups, norm_before_gate, conv_state_out)
+                                                ngroups, norm_before_gate, conv_state_out, seq_lens)

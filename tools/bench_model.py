@@ -1,5 +1,5 @@
 """BASELINE.json configs[2..4] on the synthetic OmniMamba-1.3B stack (random init, synthetic data), 1 GPU or N GPUs via
-torch.distributed.run:   python tools/bench_model.py [decode|train|decode_mmu_batch|step_index_cost|mmu_followup] [--batch B] [--seqlen L] [--steps K]
+torch.distributed.run:   python tools/bench_model.py [decode|train|decode_mmu_batch|step_index_cost|mmu_followup|ragged_prefill] [--batch B] [--seqlen L] [--steps K]
 Prints one JSON line per workload (rank 0)."""
 import argparse
 import json
@@ -121,37 +121,87 @@ def _mmu_batch_workload(cfg, dev, n_req=32):
     return feats, qs, lens, new
 
 
+class _AdmissionClock:
+    """Times the admissions of one decode_ragged call from outside the library: batch_decode's _prefill / _prefill_group / _extend are
+    wrapped with a device synchronisation on both sides.  seconds: time spent in them (prefill or extend + state copy);
+    first_token_s: per request in admission (FIFO) order, seconds from entering the context to the end of its admission, which is when
+    its first id can be sampled.  The run it times is slower than an untimed one: do not take tokens / s from it."""
+
+    def __enter__(self):
+        from omnimamba_amd import batch_decode as BD
+        self.BD, self.real, self.seconds, self.first_token_s = BD, {}, 0.0, []
+        self.t_enter = time.perf_counter()
+        for name in ("_prefill", "_prefill_group", "_extend"):
+            self.real[name] = getattr(BD, name)
+            setattr(BD, name, self._timed(name))
+        return self
+
+    def _timed(self, name):
+        def fn(model, c, slot, *a, **k):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = self.real[name](model, c, slot, *a, **k)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            self.seconds += t1 - t0
+            self.first_token_s += [t1 - self.t_enter] * (len(slot) if name == "_prefill_group" else 1)
+            return out
+        return fn
+
+    def __exit__(self, *exc):
+        for name, fn in self.real.items():
+            setattr(self.BD, name, fn)
+
+
 def bench_decode_mmu_batch(args, dev):
     """Continuous batching of MMU requests (omnimamba_amd/batch_decode.py): generated tokens / s of mmu_generate_batch (max_batch 8) against
     the same requests through sequential mmu_generate calls, OmniMamba-1.3B with fp32 weights (as the reference runs it) and with bf16
-    weights; every bucket / graph is warmed up first, prefills are part of both timings."""
+    weights; every bucket / graph is warmed up first, prefills are part of both timings.
+    --prefill-batch / --prefill-bucket: the ragged-prefill options of decode_ragged.  --reps N: the ragged run N times (every time is
+    printed: the spread is the point).  One more run under _AdmissionClock gives the time spent in admission (prefill + state copy)
+    and the time to the first token of the first and of the last request of the opening burst; that run synchronises around every
+    admission and is not one of the timed ones.  --no-sequential: skip the sequential baseline."""
     cfg = StackConfig.omnimamba_1_3b()
-    for wdt in (torch.float32, torch.bfloat16):
+    opts = dict(prefill_batch=args.prefill_batch, prefill_bucket=args.prefill_bucket)
+    for wdt in [dict(f32=torch.float32, bf16=torch.bfloat16)[d] for d in args.dtypes.split(",")]:
         torch.manual_seed(0)
         model = OmniMambaPath(cfg, stage="inference", device=dev, dtype=wdt)
         feats, qs, lens, new = _mmu_batch_workload(cfg, dev)
         feats = [f.to(wdt) for f in feats]
         n_tok = sum(new)
         # warm-ups: the sequential step graph at the largest max_length (later calls reuse it), every bucket of the ragged step
-        model.mmu_generate(feats[0], qs[0], max_length=max(lens), cg=True)
-        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True)
+        if not args.no_sequential:
+            model.mmu_generate(feats[0], qs[0], max_length=max(lens), cg=True)
+        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        seq = [model.mmu_generate(f, q, max_length=L, cg=True) for f, q, L in zip(feats, qs, lens)]
-        torch.cuda.synchronize()
-        t_seq = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        rag = model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True)
-        torch.cuda.synchronize()
-        t_rag = time.perf_counter() - t0
-        got, want = [r.shape[1] for r in rag], [s_.shape[1] for s_ in seq]
-        assert got == want == [4 + q.shape[1] + n for q, n in zip(qs, new)], (got, want)
-        same = sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
+        seq, t_seq = None, None
+        if not args.no_sequential:
+            t0 = time.perf_counter()
+            seq = [model.mmu_generate(f, q, max_length=L, cg=True) for f, q, L in zip(feats, qs, lens)]
+            torch.cuda.synchronize()
+            t_seq = time.perf_counter() - t0
+        t_rags = []
+        for _ in range(max(args.reps, 1)):
+            t0 = time.perf_counter()
+            rag = model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
+            torch.cuda.synchronize()
+            t_rags.append(time.perf_counter() - t0)
+        t_rag = sorted(t_rags)[len(t_rags) // 2]
+        with _AdmissionClock() as clk:
+            model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
+        burst = clk.first_token_s[:min(args.max_batch, len(qs))]
+        got = [r.shape[1] for r in rag]
+        assert got == [4 + q.shape[1] + n for q, n in zip(qs, new)], got
+        same = None if seq is None else sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
         print(json.dumps({"workload": "OmniMamba-1.3B MMU continuous batching", "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
-                          "requests": len(qs), "generated_tokens": n_tok, "max_batch": args.max_batch,
-                          "sequential_s": round(t_seq, 3), "ragged_s": round(t_rag, 3),
-                          "sequential_tokens_per_s": round(n_tok / t_seq, 1), "ragged_tokens_per_s": round(n_tok / t_rag, 1),
-                          "speedup": round(t_seq / t_rag, 2), "requests_with_identical_ids": same}), flush=True)
+                          "requests": len(qs), "generated_tokens": n_tok, "max_batch": args.max_batch, **opts,
+                          "sequential_s": None if t_seq is None else round(t_seq, 3), "ragged_s": round(t_rag, 3),
+                          "ragged_s_all": [round(t, 3) for t in t_rags],
+                          "sequential_tokens_per_s": None if t_seq is None else round(n_tok / t_seq, 1),
+                          "ragged_tokens_per_s": round(n_tok / t_rag, 1), "ragged_tokens_per_s_all": [round(n_tok / t, 1) for t in t_rags],
+                          "speedup": None if t_seq is None else round(t_seq / t_rag, 2), "requests_with_identical_ids": same,
+                          "admission_s": round(clk.seconds, 3), "first_token_first_request_ms": round(burst[0] * 1e3, 1),
+                          "first_token_last_of_burst_ms": round(burst[-1] * 1e3, 1)}), flush=True)
         del model
         torch.cuda.empty_cache()
 
@@ -287,10 +337,70 @@ def bench_mmu_followup(args, dev):
         torch.cuda.empty_cache()
 
 
+def bench_ragged_prefill(args, dev):
+    """Ragged prefill of MMU prompts, per 1.3B layer (the first ResidualBlock) and for the whole stack, eager unless said otherwise:
+    ONE prefill of 8 right-padded rows of 741 .. 853 positions (InferenceParams.seq_lens) against the 8 batch-1 prefills at exact length
+    it replaces; and a CAPTURED batch-1 prefill of the 896-position bucket holding an 853-position prompt against the eager batch-1
+    prefill of that prompt.  Medians of --steps event-timed calls after two warm-up calls."""
+    from omnimamba_amd.generation import InferenceParams
+    cfg = StackConfig.omnimamba_1_3b()
+    lens = [int(x) for x in torch.linspace(741, 853, 8)]
+    for wdt in [dict(f32=torch.float32, bf16=torch.bfloat16)[d] for d in args.dtypes.split(",")]:
+        torch.manual_seed(0)
+        model = OmniMambaLM(cfg, device=dev, dtype=wdt).eval()
+        blk = model.backbone.layers[0]
+        if hasattr(blk.mixer.in_proj, "task_types"):
+            model.backbone.set_lora_mode("mmu")
+        embs = [torch.randn(1, n, cfg.d_model, device=dev, dtype=wdt) * 0.02 for n in lens]
+        buf = torch.zeros(8, max(lens), cfg.d_model, device=dev, dtype=wdt)
+        for j, e in enumerate(embs):
+            buf[j, :lens[j]] = e[0]
+        lens_t = torch.tensor(lens, dtype=torch.int32, device=dev)
+        bucket = torch.zeros(1, 896, cfg.d_model, device=dev, dtype=wdt)
+        bucket[:, :lens[-1]] = embs[-1]
+        one = torch.tensor([lens[-1]], dtype=torch.int32, device=dev)
+        row = {"workload": "ragged prefill of MMU prompts, OmniMamba-1.3B", "dtype": "bf16" if wdt == torch.bfloat16 else "f32", "lens": lens}
+        with torch.inference_mode():
+            for scope in ("layer", "stack"):
+                if scope == "layer":
+                    cache = lambda b: {0: blk.allocate_inference_cache(b, 0, dtype=wdt)}
+                    run = lambda x, ip: blk(x, None, inference_params=ip)[0]
+                else:
+                    cache = lambda b: model.allocate_inference_cache(b, 1024, wdt)
+                    run = lambda x, ip: model(None, x, position_ids=None, task="mmu", inference_params=ip, num_last_tokens=1).mmu_logits
+                ip8 = InferenceParams(max_seqlen=1024, max_batch_size=8, key_value_memory_dict=cache(8), seq_lens=lens_t)
+                ip1 = InferenceParams(max_seqlen=1024, max_batch_size=1, key_value_memory_dict=cache(1))
+                ipb = InferenceParams(max_seqlen=1024, max_batch_size=1, key_value_memory_dict=cache(1), seq_lens=one)
+                row[f"{scope}_one_prefill_of_8_rows_ms"] = round(_time_ms(lambda: run(buf, ip8), args.steps), 3)
+                row[f"{scope}_8_batch1_prefills_ms"] = round(_time_ms(lambda: [run(e, ip1) for e in embs], args.steps), 3)
+                row[f"{scope}_eager_batch1_853_ms"] = round(_time_ms(lambda: run(embs[-1], ip1), args.steps), 3)
+                row[f"{scope}_eager_bucket_896_ms"] = round(_time_ms(lambda: run(bucket, ipb), args.steps), 3)
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(2):
+                        run(bucket, ipb)
+                    side.synchronize()
+                torch.cuda.current_stream().wait_stream(side)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    keep = run(bucket, ipb)  # noqa: F841
+                row[f"{scope}_captured_bucket_896_ms"] = round(_time_ms(graph.replay, args.steps), 3)
+                del graph, keep
+        print(json.dumps(row), flush=True)
+        del model
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["decode", "train", "decode_mmu_batch", "step_index_cost", "mmu_followup"])
+    ap.add_argument("what", choices=["decode", "train", "decode_mmu_batch", "step_index_cost", "mmu_followup", "ragged_prefill"])
     ap.add_argument("--max-batch", type=int, default=8, help="decode_mmu_batch: slots of the ragged decoder")
+    ap.add_argument("--prefill-batch", type=int, default=1, help="decode_mmu_batch: requests admitted by one right-padded prefill (1 = off)")
+    ap.add_argument("--prefill-bucket", type=int, default=0, help="decode_mmu_batch: length bucket of the captured prefill graphs (0 = off; 128 for MMU)")
+    ap.add_argument("--reps", type=int, default=1, help="decode_mmu_batch: timed repetitions of the ragged run")
+    ap.add_argument("--dtypes", default="f32,bf16", help="decode_mmu_batch: weight dtypes to run")
+    ap.add_argument("--no-sequential", action="store_true", help="decode_mmu_batch: skip the sequential mmu_generate baseline")
     ap.add_argument("--only", choices=["plain", "indexed"], default=None, help="step_index_cost: capture and replay one step only")
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--seqlen", type=int, default=2048)
@@ -309,6 +419,8 @@ def main():
         (bench_decode_mmu if args.task == "mmu" else bench_decode)(args, dev)
     elif args.what == "decode_mmu_batch":
         bench_decode_mmu_batch(args, dev)
+    elif args.what == "ragged_prefill":
+        bench_ragged_prefill(args, dev)
     elif args.what == "step_index_cost":
         bench_step_index_cost(args, dev)
     elif args.what == "mmu_followup":
