@@ -13,6 +13,7 @@ import torch
 
 OMK_ABI_VERSION = 10
 OMK_MAX_DIMS = 5
+OMK_EUNSUPPORTED = -4   # omk_status: the kernel does not take this call (the caller may have another way)
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices, per-row lengths
 
 
@@ -159,6 +160,20 @@ def run(lib, fn_name: str, params, ref: torch.Tensor):
     else:
         with torch.cuda.device(ref.device):
             check(lib, fn(C.byref(params), stream_of(lib, ref)), fn_name)
+
+
+def try_run(lib, fn_name: str, params, ref: torch.Tensor) -> bool:
+    """`run` for a call the library may decline: False on OMK_EUNSUPPORTED, True when it ran; any other non-zero status raises."""
+    fn = getattr(lib, fn_name)
+    if lib.omk_is_emulated():
+        rc = fn(C.byref(params), None)
+    else:
+        with torch.cuda.device(ref.device):
+            rc = fn(C.byref(params), stream_of(lib, ref))
+    if rc == OMK_EUNSUPPORTED:
+        return False
+    check(lib, rc, fn_name)
+    return True
 
 
 def workspace(lib, fn_name: str, params, ref: torch.Tensor) -> Optional[torch.Tensor]:

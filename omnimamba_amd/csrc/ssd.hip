@@ -518,9 +518,31 @@ static Src make_src(const OmkTensor& t, bool per_group) {   // (B, L, H|G, dim) 
   Src s; s.p = t.data; s.sb = t.stride[0]; s.sl = t.stride[1]; s.sh = t.stride[2]; s.dt = t.dtype; s.per_group = per_group ? 1 : 0;
   return s;
 }
+// optional initial state (B, H, P, N) as the scan's logical [u][k]; transposed: the scans whose state is [n][p] (dC, dB)
+static void set_init(GScan& g, const OmkTensor& t, bool transposed = false) {
+  if (!present(t)) return;
+  g.init = t.data; g.init_dt = t.dtype; g.isb = t.stride[0]; g.ish = t.stride[1];
+  g.isu = t.stride[transposed ? 3 : 2]; g.isk = t.stride[transposed ? 2 : 3];
+}
+static void set_fin(GScan& g, const OmkTensor& t) {   // optional final state, f32 (B, H, P, N)
+  if (!present(t)) return;
+  g.fin = (float*)t.data; g.fsb = t.stride[0]; g.fsh = t.stride[1]; g.fsu = t.stride[2]; g.fsk = t.stride[3];
+}
+static void set_D(GScan& g, const OmkTensor& D) {   // optional D: (H) or (H, P)
+  if (!present(D)) return;
+  g.D = D.data; g.D_dt = D.dtype; g.Dsh = D.stride[0]; g.Dsp = D.ndim == 2 ? D.stride[1] : 0;
+}
 static size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct SsdDims { int B, L, H, P, G, N; };
+// the forward-state scan (U = x, K = B, Q = C, t ascending): the forward itself, and the state passes the backward recomputes with
+static GScan fwd_state_scan(const OmkTensor& x, const OmkTensor& Bm, const OmkTensor& Cm, const OmkTensor& init, const float* A, const float* dtp, const SsdDims& d) {
+  GScan g = {};
+  g.mode = GS_Y; g.U = make_src(x, false); g.K = make_src(Bm, true); g.Q = make_src(Cm, true);
+  g.dtp = dtp; g.A = A; g.B = d.B; g.H = d.H; g.G = d.G; g.L = d.L; g.DU = d.P; g.DK = d.N; g.reverse = 0; g.w_is_dt = 1;
+  set_init(g, init);
+  return g;
+}
 static int ssd_check_common(const OmkTensor& x, const OmkTensor& dt, const OmkTensor& A, const OmkTensor& Bm, const OmkTensor& Cm,
                             const OmkTensor& D, const OmkTensor& dtb, const OmkTensor& init, SsdDims* d, const char* who) {
   OMK_REQUIRE(present(x) && present(dt) && present(A) && present(Bm) && present(Cm), "%s: x, dt, A, B, C required", who);
@@ -596,17 +618,16 @@ static size_t fwd_window_states_bytes(const OmkSsdFwd* p) {
   if (p->x.ndim != 4 || p->Bm.ndim != 4 || p->x.dtype != OMK_BF16 || p->x.shape[3] != 64 || p->Bm.shape[3] != 128) return 0;
   if (p->flags & (OMK_SSD_KHILO | OMK_SSD_PRECISE)) return 0;
   const int64_t B = p->x.shape[0], L = p->x.shape[1], H = p->x.shape[2];
-  // the same dry check the launch makes (strides, alignment, 32-bit row span): a forward the MFMA kernel cannot take must answer 0
+  // the same plan the launch follows (strides, alignment, 32-bit row span): a forward the MFMA kernel cannot take must answer 0
   // here, so that the caller allocates nothing and omk_ssd_scan_fwd takes its ordinary fall-back chain (advisor finding, round 3:
   // a bf16 x at a 2-byte storage offset failed with 'window_states asked for on a shape outside the MFMA kernel')
   if (p->x.ndim != 4 || p->Cm.ndim != 4 || p->out.ndim != 4 || p->out.dtype != OMK_BF16 || p->Bm.dtype != OMK_BF16 || p->Cm.dtype != OMK_BF16) return 0;
-  GScan g = {};
-  g.mode = GS_Y; g.U = make_src(p->x, false); g.K = make_src(p->Bm, true); g.Q = make_src(p->Cm, true);
-  g.B = (int)B; g.H = (int)H; g.G = (int)p->Bm.shape[2]; g.L = (int)L; g.DU = 64; g.DK = 128;
-  if (g.G < 1 || g.H % g.G != 0) return 0;
+  const SsdDims d = {(int)B, (int)L, (int)H, 64, (int)p->Bm.shape[2], 128};
+  if (d.G < 1 || d.H % d.G != 0) return 0;
+  GScan g = fwd_state_scan(p->x, p->Bm, p->Cm, OmkTensor{}, nullptr, nullptr, d);
   g.out = p->out.data; g.osb = p->out.stride[0]; g.osl = p->out.stride[1]; g.osh = p->out.stride[2]; g.out_dt = p->out.dtype;
-  if (present(p->D)) { g.D = p->D.data; g.D_dt = p->D.dtype; g.Dsh = p->D.stride[0]; g.Dsp = p->D.ndim == 2 ? p->D.stride[1] : 0; }
-  if (ssd_mfma_launch(g, nullptr, 1) != OMK_OK) return 0;
+  set_D(g, p->D);
+  if (ssd_class_a_plan(g).family == CA_NONE) return 0;
   return (size_t)B * ((L + 127) / 128) * H * 16384;
 }
 extern "C" size_t omk_ssd_scan_fwd_window_states_bytes(const OmkSsdFwd* p) { return fwd_window_states_bytes(p); }
@@ -638,24 +659,15 @@ extern "C" int omk_ssd_scan_fwd(const OmkSsdFwd* p, omk_stream stream) {
   if ((int64_t)d.B * d.L * d.H * d.P == 0) return OMK_OK;
   kernels_reset();
   float* dtp = (float*)p->workspace;
-  GScan g = {};
   // (tried in round 2: the scan reading the raw (B, L, H) dt itself and applying bias / softplus / clamp in its scalar pass, to
   // save this 16 us launch -- 280 us against 236 + 16 us: the 2-byte loads at stride H are 64 requests per wave and chunk and the
   // softplus lands on wave 0's critical path between the publish and the barrier.  Not kept.)
   launch_dt_prep(p->dt, p->dt_bias, d, dtp, nullptr, p->dt_softplus, p->dt_min, p->dt_max, stream, (const int*)p->seq_lens.data);
-  g.mode = GS_Y; g.U = make_src(p->x, false); g.K = make_src(p->Bm, true); g.Q = make_src(p->Cm, true);
+  GScan g = fwd_state_scan(p->x, p->Bm, p->Cm, p->initial_states, (const float*)p->A.data, dtp, d);
   if (present(p->z)) g.Z = make_src(p->z, false);
-  g.dtp = dtp; g.A = (const float*)p->A.data; g.B = d.B; g.H = d.H; g.G = d.G; g.L = d.L; g.DU = d.P; g.DK = d.N; g.reverse = 0; g.w_is_dt = 1;
-  if (present(p->initial_states)) {
-    g.init = p->initial_states.data; g.init_dt = p->initial_states.dtype;
-    g.isb = p->initial_states.stride[0]; g.ish = p->initial_states.stride[1]; g.isu = p->initial_states.stride[2]; g.isk = p->initial_states.stride[3];
-  }
-  if (present(p->final_states)) {
-    g.fin = (float*)p->final_states.data;
-    g.fsb = p->final_states.stride[0]; g.fsh = p->final_states.stride[1]; g.fsu = p->final_states.stride[2]; g.fsk = p->final_states.stride[3];
-  }
+  set_fin(g, p->final_states);
   g.out = p->out.data; g.osb = p->out.stride[0]; g.osl = p->out.stride[1]; g.osh = p->out.stride[2]; g.out_dt = p->out.dtype; g.outx = p->out_x.data;
-  if (present(p->D)) { g.D = p->D.data; g.D_dt = p->D.dtype; g.Dsh = p->D.stride[0]; g.Dsp = p->D.ndim == 2 ? p->D.stride[1] : 0; }
+  set_D(g, p->D);
 #ifdef OMK_PHASE_PROF
   if (getenv("OMK_PROF") && p->workspace_bytes >= omk_ssd_scan_fwd_workspace_bytes(p)) g.prof = (unsigned long long*)((char*)p->workspace + align256((size_t)d.B * d.H * d.L * 4));
   if (const char* e = getenv("OMK_ABLATE")) g.ablate = atoi(e);   // (skips phases: wrong results)
@@ -668,16 +680,15 @@ extern "C" int omk_ssd_scan_fwd(const OmkSsdFwd* p, omk_stream stream) {
     g.cw = p->conv_weight.data; g.cwsc = p->conv_weight.stride[0]; g.cwsk = p->conv_weight.stride[1]; g.cw_dt = p->conv_weight.dtype; g.cW = (int)p->conv_weight.shape[1];
     g.cb = p->conv_bias.data; g.cb_dt = p->conv_bias.dtype;
     // only ssd_a8.hip knows the fused conv: a shape it does not take (heads that do not pair up, D per (head, column), a sequence it would split) is the caller's to run unfused
-    GScan q = g;
-    if (q.seg && ssd_segments(d.B * d.H, d.L).nseg > 1) return fail(OMK_EUNSUPPORTED, "ssd_scan_fwd: fused conv on a sequence the scan splits into segments (B * H <= 128): run conv + scan separately");
+    if (g.seg && ssd_segments(d.B * d.H, d.L).nseg > 1) return fail(OMK_EUNSUPPORTED, "ssd_scan_fwd: fused conv on a sequence the scan splits into segments (B * H <= 128): run conv + scan separately");
     g.seg = nullptr;
-    rc = (ssd_mfma_launch(g, nullptr, 1) == OMK_OK && ssd_a8_applies(g)) ? ssd_a8_launch(g, stream) : OMK_EUNSUPPORTED;
+    rc = ssd_class_a_launch(ssd_class_a_plan(g), g, stream);   // (the plan of a descriptor with conv weights is that kernel's or nobody's)
     if (rc == OMK_EUNSUPPORTED) return fail(OMK_EUNSUPPORTED, "ssd_scan_fwd: fused conv on a shape outside the specialised-wave kernel: run conv + scan separately");
     if (rc) return rc;
     return finish_launch("ssd_scan_fwd");
   }
   if (state_only) {
-    rc = (p->force_generic || p->x.dtype != OMK_BF16) ? OMK_EUNSUPPORTED : ssd_mfma_state_only(g, stream);
+    rc = (p->force_generic || p->x.dtype != OMK_BF16) ? OMK_EUNSUPPORTED : ssd_mfma_launch(g, stream);   // (no `out`: the plan's state-only pass)
     if (rc == OMK_EUNSUPPORTED) return fail(OMK_EUNSUPPORTED, "ssd_scan_fwd: the state-only pass exists for the MFMA shape only (bf16, headdim 64, d_state 128); run the scan and drop its output");
     if (rc) return rc;
     return finish_launch("ssd_scan_fwd");
@@ -744,10 +755,7 @@ static void bwd_scans(const OmkSsdBwd* p, const SsdDims& d, const BwdWs& w, bool
     GScan g = base(GS_DC);
     g.U = make_src(p->Bm, true); g.K = make_src(p->x, false); g.Q = make_src(p->dout, false); g.X4 = make_src(p->Cm, true);
     g.DU = d.N; g.DK = d.P; g.reverse = 0; g.w_is_dt = 1;
-    if (present(p->initial_states)) {
-      g.init = p->initial_states.data; g.init_dt = p->initial_states.dtype;
-      g.isb = p->initial_states.stride[0]; g.ish = p->initial_states.stride[1]; g.isk = p->initial_states.stride[2]; g.isu = p->initial_states.stride[3];
-    }
+    set_init(g, p->initial_states, true);
     if (has_dfin) { g.fin = w.sfin; g.fsb = (int64_t)d.H * d.N * d.P; g.fsh = (int64_t)d.N * d.P; g.fsu = d.P; g.fsk = 1; }
     if (mfma) { g.part = w.part; g.tokscal = w.e; g.ckpt = w.ckpt; g.ckpt_every = ssd_ckpt_every(); } else { g.acc32 = w.dC32; g.tokscal = w.e; }
     *gdc = g;
@@ -756,27 +764,18 @@ static void bwd_scans(const OmkSsdBwd* p, const SsdDims& d, const BwdWs& w, bool
     GScan g = base(GS_DX);
     g.U = make_src(p->dout, false); g.K = make_src(p->Cm, true); g.Q = make_src(p->Bm, true);
     g.DU = d.P; g.DK = d.N; g.reverse = 1; g.w_is_dt = 0;
-    if (has_dfin) {
-      g.init = p->dfinal_states.data; g.init_dt = OMK_F32;
-      g.isb = p->dfinal_states.stride[0]; g.ish = p->dfinal_states.stride[1]; g.isu = p->dfinal_states.stride[2]; g.isk = p->dfinal_states.stride[3];
-    }
-    if (present(p->dinitial_states)) {
-      g.fin = (float*)p->dinitial_states.data; g.fin_extra_decay = 1;
-      g.fsb = p->dinitial_states.stride[0]; g.fsh = p->dinitial_states.stride[1]; g.fsu = p->dinitial_states.stride[2]; g.fsk = p->dinitial_states.stride[3];
-    }
+    set_init(g, p->dfinal_states);   // (f32: checked by the caller)
+    set_fin(g, p->dinitial_states); g.fin_extra_decay = present(p->dinitial_states) ? 1 : 0;
     g.seg = (p->flags & OMK_SSD_NO_SPLIT) ? nullptr : w.seg;
     g.out = p->dx.data; g.osb = p->dx.stride[0]; g.osl = p->dx.stride[1]; g.osh = p->dx.stride[2]; g.out_dt = p->dx.dtype;
-    if (present(p->D)) { g.D = p->D.data; g.D_dt = p->D.dtype; g.Dsh = p->D.stride[0]; g.Dsp = p->D.ndim == 2 ? p->D.stride[1] : 0; }
+    set_D(g, p->D);
     *gdx = g;
   }
   {  // dB: state [n][p], reverse in time
     GScan g = base(GS_DB);
     g.U = make_src(p->Cm, true); g.K = make_src(p->dout, false); g.Q = make_src(p->x, false); g.X4 = make_src(p->Bm, true);
     g.DU = d.N; g.DK = d.P; g.reverse = 1; g.w_is_dt = 0;
-    if (has_dfin) {
-      g.init = p->dfinal_states.data; g.init_dt = OMK_F32;
-      g.isb = p->dfinal_states.stride[0]; g.ish = p->dfinal_states.stride[1]; g.isk = p->dfinal_states.stride[2]; g.isu = p->dfinal_states.stride[3];
-    }
+    set_init(g, p->dfinal_states, true);
     if (mfma) { g.part = w.part; g.tokscal = w.wsum; g.ckpt = w.ckpt; g.bnd = w.bnd; g.ckpt_every = ssd_ckpt_every(); }
     else { g.acc32 = w.dB32; g.tokscal = w.wsum; }
     if (present(p->dD)) { g.dD = (float*)p->dD.data; g.dDsh = p->dD.stride[0]; g.dDsp = p->dD.ndim == 2 ? p->dD.stride[1] : 0; }
@@ -790,7 +789,7 @@ static bool bwd_mfma_applies(const OmkSsdBwd* p, const SsdDims& d) {
   BwdWs w = {};
   GScan gdc, gdx, gdb;
   bwd_scans(p, d, w, true, &gdc, &gdx, &gdb);
-  return ssd_mfma_launch(gdc, nullptr, 1) == OMK_OK && ssd_mfma_launch(gdx, nullptr, 1) == OMK_OK && ssd_mfma_launch(gdb, nullptr, 1) == OMK_OK;
+  return ssd_class_b_applies(gdc) && ssd_class_a_plan(gdx).family != CA_NONE && ssd_class_b_applies(gdb);
 }
 
 // the chunk-parallel form: bf16 block shape (the MFMA scans apply), one D per head, rows addressable through 32-bit buffer offsets
@@ -856,13 +855,7 @@ extern "C" int omk_ssd_scan_bwd(const OmkSsdBwd* p, omk_stream stream) {
   if (mfma && gdx.seg && ssd_segments(d.B * d.H, d.L).nseg > 1) {
     // few (batch, head) pairs: every scan cuts the sequence into the same segments.  Their start states come from two
     // state-only passes + folds: the forward state (x, B; shared by the dC scan) and the adjoint state (dy, C; dx and dB)
-    GScan gf = {};
-    gf.mode = GS_Y; gf.dtp = w.dtp; gf.A = A; gf.B = d.B; gf.H = d.H; gf.G = d.G; gf.L = d.L; gf.DU = d.P; gf.DK = d.N;
-    gf.U = make_src(p->x, false); gf.K = make_src(p->Bm, true); gf.Q = make_src(p->Cm, true); gf.reverse = 0; gf.w_is_dt = 1;
-    if (present(p->initial_states)) {
-      gf.init = p->initial_states.data; gf.init_dt = p->initial_states.dtype;
-      gf.isb = p->initial_states.stride[0]; gf.ish = p->initial_states.stride[1]; gf.isu = p->initial_states.stride[2]; gf.isk = p->initial_states.stride[3];
-    }
+    GScan gf = fwd_state_scan(p->x, p->Bm, p->Cm, p->initial_states, A, w.dtp, d);
     gf.seg = w.segf; gf.flags = gdx.flags;
     int fmt_f = 0, fmt_a = 0;   // element order each pass left its states in (ssd_scan.h: seg_fmt)
     if (!(cp && present(p->window_states)) && (rc = ssd_mfma_prepare_segments(gf, stream, &fmt_f))) return rc;   // (saved window states: no forward state pass at all)
@@ -875,13 +868,7 @@ extern "C" int omk_ssd_scan_bwd(const OmkSsdBwd* p, omk_stream stream) {
     // chunk-parallel: a state-only forward pass and the dx scan leave the window-boundary states of both directions behind;
     // ssd_cp.hip forms dB, dC, the token scalars, the restart values of the decay gradient and dD window by window
     const int nW = (d.L + 127) / 128;
-    GScan gf = {};
-    gf.mode = GS_Y; gf.dtp = w.dtp; gf.A = A; gf.B = d.B; gf.H = d.H; gf.G = d.G; gf.L = d.L; gf.DU = d.P; gf.DK = d.N;
-    gf.U = make_src(p->x, false); gf.K = make_src(p->Bm, true); gf.Q = make_src(p->Cm, true); gf.reverse = 0; gf.w_is_dt = 1;
-    if (present(p->initial_states)) {
-      gf.init = p->initial_states.data; gf.init_dt = p->initial_states.dtype;
-      gf.isb = p->initial_states.stride[0]; gf.ish = p->initial_states.stride[1]; gf.isu = p->initial_states.stride[2]; gf.isk = p->initial_states.stride[3];
-    }
+    GScan gf = fwd_state_scan(p->x, p->Bm, p->Cm, p->initial_states, A, w.dtp, d);
     gf.flags = gdx.flags;
     if (gdc.seg_ready) { gf.seg = w.segf; gf.seg_ready = 1; gf.seg_fmt = gdc.seg_fmt; }
     // (a training forward that saved its window states spares this pass: the same images, written by the same code)
@@ -891,7 +878,7 @@ extern "C" int omk_ssd_scan_bwd(const OmkSsdBwd* p, omk_stream stream) {
       Sf = (const uint16_t*)p->window_states.data;
     } else {
       gf.dump = w.Sf; gf.dump_nw = nW;
-      if ((rc = ssd_mfma_state_dump(gf, stream))) return rc;
+      if ((rc = ssd_mfma_launch(gf, stream))) return rc;   // (no `out`, `dump` set: the plan's state-dump pass)
     }
     gdx.dump = w.Sg; gdx.dump_nw = nW;
     if ((rc = ssd_mfma_launch(gdx, stream))) return rc;

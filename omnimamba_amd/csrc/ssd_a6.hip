@@ -558,85 +558,40 @@ __global__ __launch_bounds__(512) void ssd_a6_kernel(GScan a) {
   }
 }
 
-// The column-slice kernel takes the class A scans of head PAIRS that share a group (the row-strip kernel the others), split
-// sequences included (the zero-start state pass + fold of ssd_mfma_prepare_segments provides the segment start states).
-bool ssd_a6_applies(const GScan& g) {
-  if (g.mode != GS_Y && g.mode != GS_DX) return false;
-  if (g.H % 2 != 0 || (g.H / g.G) % 2 != 0) return false;
-  if (g.state_only) return false;
-  return true;
-}
+static_assert(QA6 == SEG_CHUNK, "segments are planned in chunks of SEG_CHUNK tokens");
 
-// state-only pass that leaves the state behind the sequence in g.fin (context-parallel shards): the scan proper with final states
-// carries exactly this state (hi + lo operand)
-int ssd_a6_state_only(const GScan& g, omk_stream stream) {
-  GScan q = g; q.state_only = 0;
-  if (!g.fin || g.mode != GS_Y || !ssd_a6_applies(q)) return OMK_EUNSUPPORTED;
-  GScan a = q;
-  a.out = nullptr; a.outx = nullptr; a.Z = Src{}; a.D = nullptr; a.dump = nullptr;
-  const SegPlan sp = a.seg ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QA6 - 1) / QA6};
-  a.nseg = sp.nseg; a.cps = sp.cps;
-  if (a.nseg > 1 && !a.seg_ready) {
-    int rc = ssd_mfma_prepare_segments(a, stream);
-    if (rc) return rc;
-  }
-  dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
-  const size_t smem = sizeof(SmemA6);
-  kernels_note("ssd_a6<state_only>");
-  if (OMK_SET_MAX_DYN_SMEM((ssd_a6_kernel<GS_Y, false, true, false, true, true>), smem)) return fail(OMK_ELAUNCH, "ssd_a6: cannot raise dynamic LDS to %zu", smem);
-  OMK_LAUNCH((ssd_a6_kernel<GS_Y, false, true, false, true, true>), grid, block, smem, stream, a);
-  return OMK_OK;
-}
+constexpr int a6_key(int mode, bool ex, bool dfold, bool dump, bool khilo) { return mode | ex << 2 | dfold << 3 | dump << 4 | khilo << 5; }
 
-// state-only pass over the whole sequence that leaves the window-boundary images in g.dump (no output): the recomputing backward
-int ssd_a6_state_dump(const GScan& g, omk_stream stream) {
-  if (!g.dump || !ssd_a6_applies(g) || g.mode != GS_Y) return OMK_EUNSUPPORTED;
-  GScan a = g;
-  a.out = nullptr; a.outx = nullptr; a.Z = Src{}; a.D = nullptr; a.fin = nullptr;
-  const SegPlan sp = (a.seg && a.seg_ready) ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QA6 - 1) / QA6};   // start states already folded
-  a.nseg = sp.nseg; a.cps = sp.cps;
+// The column-slice kernel takes the class A scans of head PAIRS that share a group which the specialised-wave kernel does not
+// (ssd_class_a_plan), split sequences included, and both state passes of the pairs: the state-only pass leaves the state a scan with
+// final states carries (hi + lo operand), the state-dump pass the images the scan proper dumps (same code, identical images).
+// One head pair (x one segment) per workgroup.
+int ssd_a6_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
   dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
-  const size_t smem = sizeof(SmemA6);
-  kernels_note("ssd_a6<state_dump>");
-  if (OMK_SET_MAX_DYN_SMEM((ssd_a6_kernel<GS_Y, false, true, true, false, true>), smem)) return fail(OMK_ELAUNCH, "ssd_a6: cannot raise dynamic LDS to %zu", smem);
-  OMK_LAUNCH((ssd_a6_kernel<GS_Y, false, true, true, false, true>), grid, block, smem, stream, a);
-  return OMK_OK;
-}
-
-// called by ssd_mfma_launch after its shape / alignment checks (same preconditions as the row-strip kernel)
-int ssd_a6_launch(const GScan& g, omk_stream stream) {
-  if (ssd_a8_applies(g)) return ssd_a8_launch(g, stream);
-  GScan a = g;
-  const SegPlan sp = a.seg ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QA6 - 1) / QA6};
-  a.nseg = sp.nseg; a.cps = sp.cps;
-  if (a.nseg > 1 && !a.seg_ready) {
-    int rc = ssd_mfma_prepare_segments(g, stream);
-    if (rc) return rc;
+  if (pl.variant == CA_STATE_ONLY) return ssd_launch(kernel_id("ssd_a6<state_only>"), ssd_a6_kernel<GS_Y, false, true, false, true, true>, grid, block, sizeof(SmemA6), stream, a);
+  if (pl.variant == CA_STATE_DUMP) return ssd_launch(kernel_id("ssd_a6<state_dump>"), ssd_a6_kernel<GS_Y, false, true, true, false, true>, grid, block, sizeof(SmemA6), stream, a);
+  void (*k)(GScan) = nullptr;
+  switch (a6_key(a.mode, pl.extras, pl.dfold, pl.dump, pl.khilo)) {
+    case a6_key(GS_Y, 0, 0, 0, 0): k = ssd_a6_kernel<GS_Y, false, false, false, false>; break;
+    case a6_key(GS_Y, 0, 0, 0, 1): k = ssd_a6_kernel<GS_Y, false, false, false, true>; break;
+    case a6_key(GS_Y, 0, 0, 1, 0): k = ssd_a6_kernel<GS_Y, false, false, true, false>; break;
+    case a6_key(GS_Y, 0, 0, 1, 1): k = ssd_a6_kernel<GS_Y, false, false, true, true>; break;
+    case a6_key(GS_Y, 0, 1, 0, 0): k = ssd_a6_kernel<GS_Y, false, true, false, false>; break;
+    case a6_key(GS_Y, 0, 1, 0, 1): k = ssd_a6_kernel<GS_Y, false, true, false, true>; break;
+    case a6_key(GS_Y, 0, 1, 1, 0): k = ssd_a6_kernel<GS_Y, false, true, true, false>; break;
+    case a6_key(GS_Y, 0, 1, 1, 1): k = ssd_a6_kernel<GS_Y, false, true, true, true>; break;
+    case a6_key(GS_Y, 1, 0, 0, 0): k = ssd_a6_kernel<GS_Y, true, false, false, false>; break;
+    case a6_key(GS_Y, 1, 0, 0, 1): k = ssd_a6_kernel<GS_Y, true, false, false, true>; break;
+    case a6_key(GS_Y, 1, 1, 0, 0): k = ssd_a6_kernel<GS_Y, true, true, false, false>; break;
+    case a6_key(GS_Y, 1, 1, 0, 1): k = ssd_a6_kernel<GS_Y, true, true, false, true>; break;
+    case a6_key(GS_DX, 0, 0, 0, 0): k = ssd_a6_kernel<GS_DX, false, false, false, false>; break;
+    case a6_key(GS_DX, 0, 0, 1, 0): k = ssd_a6_kernel<GS_DX, false, false, true, false>; break;
+    case a6_key(GS_DX, 0, 1, 0, 0): k = ssd_a6_kernel<GS_DX, false, true, false, false>; break;
+    case a6_key(GS_DX, 0, 1, 1, 0): k = ssd_a6_kernel<GS_DX, false, true, true, false>; break;
+    default: return fail(OMK_EINVAL, "ssd_a6: no instantiation for this plan");
   }
-  dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
-  const size_t smem = sizeof(SmemA6);
-  // the scaled U operand of the state update as hi + lo whenever the caller keeps the final state (prefill -> decode hand-off,
-  // context-parallel shards): the carried state is then exact to fp32 accumulation (8 more MFMAs per sub-chunk)
-  const bool khilo = (a.flags & (GSF_KHILO | GSF_PRECISE)) || a.fin != nullptr;
-#define OMK_A6K(MODE_, EX_, DF_, DU_, KH_) do { \
-    kernels_note("ssd_a6<mode=%d,ex=%d,dfold=%d,dump=%d,khilo=%d>", (int)MODE_, (int)EX_, (int)DF_, (int)DU_, (int)KH_); \
-    if (OMK_SET_MAX_DYN_SMEM((ssd_a6_kernel<MODE_, EX_, DF_, DU_, KH_>), smem)) return fail(OMK_ELAUNCH, "ssd_a6: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((ssd_a6_kernel<MODE_, EX_, DF_, DU_, KH_>), grid, block, smem, stream, a); } while (0)
-#define OMK_A6(MODE_, EX_, DF_, DU_) do { if (khilo && MODE_ == GS_Y) OMK_A6K(MODE_, EX_, DF_, DU_, (MODE_ == GS_Y)); else OMK_A6K(MODE_, EX_, DF_, DU_, false); } while (0)
-  const bool dfold = !a.D || a.Dsp == 0;   // one D per head (or none)
-  if (a.mode == GS_Y) {
-    const bool ex = a.Z.p || a.outx;
-    if (a.dump) { if (ex) return OMK_EUNSUPPORTED; if (dfold) OMK_A6(GS_Y, false, true, true); else OMK_A6(GS_Y, false, false, true); }
-    else if (ex) { if (dfold) OMK_A6(GS_Y, true, true, false); else OMK_A6(GS_Y, true, false, false); }
-    else { if (dfold) OMK_A6(GS_Y, false, true, false); else OMK_A6(GS_Y, false, false, false); }
-  } else if (dfold) {
-    if (a.dump) OMK_A6(GS_DX, false, true, true); else OMK_A6(GS_DX, false, true, false);
-  } else {
-    if (a.dump) OMK_A6(GS_DX, false, false, true); else OMK_A6(GS_DX, false, false, false);
-  }
-#undef OMK_A6
-#undef OMK_A6K
-  return OMK_OK;
+  return ssd_launch(kernel_id("ssd_a6<mode=%d,ex=%d,dfold=%d,dump=%d,khilo=%d>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.dump, (int)pl.khilo), k, grid, block,
+                    sizeof(SmemA6), stream, a);
 }
 
 }  // namespace omk

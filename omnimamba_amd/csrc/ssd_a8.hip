@@ -772,51 +772,30 @@ __global__ __launch_bounds__(512) void ssd_a8_kernel(GScan a) {
   }
 }
 
-// the plain class A scans (one D per head or none, no gate, no pre-gate copy); GSF_COLUMN_SLICE: ssd_a6.hip takes them
-bool ssd_a8_applies(const GScan& g) {
-  if (g.flags & GSF_COLUMN_SLICE) return false;
-  if (g.mode != GS_Y && g.mode != GS_DX) return false;
-  if (g.H % 2 != 0 || (g.H / g.G) % 2 != 0 || g.state_only) return false;
-  if (g.Z.p || g.outx || (g.D && g.Dsp != 0)) return false;
-  return true;
-}
+static_assert(QA8 == SEG_CHUNK, "segments are planned in chunks of SEG_CHUNK tokens");
 
-int ssd_a8_launch(const GScan& g, omk_stream stream) {
-  GScan a = g;
-  const SegPlan sp = a.seg ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QA8 - 1) / QA8};
-  a.nseg = sp.nseg; a.cps = sp.cps;
-  const bool precise = a.mode == GS_Y && (a.flags & GSF_PRECISE);
-  if (precise && a.dump) return fail(OMK_EINVAL, "ssd_a8: a PRECISE forward does not save window states");
-  // the fused conv (forward-only path): plain forward of an unsplit sequence
-  if (a.cw && (a.mode != GS_Y || a.dump || precise || a.reverse || a.nseg > 1 || a.cW < 1 || a.cW > 4)) return OMK_EUNSUPPORTED;
-  if (a.nseg > 1 && !a.seg_ready) {
-    int rc = ssd_mfma_prepare_segments(g, stream);
-    if (rc) return rc;
-  }
+constexpr int a8_key(int mode, bool dump, bool khilo, bool precise, bool conv) { return mode | dump << 2 | khilo << 3 | precise << 4 | conv << 5; }
+
+// the plain class A scans of head pairs (one D per head or none, no gate, no pre-gate copy: ssd_class_a_plan); one head pair (x one
+// segment) per workgroup
+int ssd_a8_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
   dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
-  const size_t smem = sizeof(SmemA8);
-  // the scaled U operand of the state update as hi + lo whenever the caller keeps the final state (prefill -> decode hand-off,
-  // context-parallel shards) or asks for it (OMK_SSD_KHILO / OMK_SSD_PRECISE)
-  const bool khilo = a.mode == GS_Y && ((a.flags & (GSF_KHILO | GSF_PRECISE)) || a.fin != nullptr);
-#define OMK_A8K(MODE_, DU_, KH_, PR_) do { \
-    kernels_note("ssd_a8<mode=%d,dump=%d,khilo=%d,precise=%d>", (int)MODE_, (int)DU_, (int)KH_, (int)PR_); \
-    if (OMK_SET_MAX_DYN_SMEM((ssd_a8_kernel<MODE_, DU_, KH_, PR_>), smem)) return fail(OMK_ELAUNCH, "ssd_a8: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((ssd_a8_kernel<MODE_, DU_, KH_, PR_>), grid, block, smem, stream, a); } while (0)
-#define OMK_A8C(KH_) do { \
-    kernels_note("ssd_a8<mode=0,dump=0,khilo=%d,precise=0,conv=1>", (int)KH_); \
-    if (OMK_SET_MAX_DYN_SMEM((ssd_a8_kernel<GS_Y, false, KH_, false, true>), smem)) return fail(OMK_ELAUNCH, "ssd_a8: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((ssd_a8_kernel<GS_Y, false, KH_, false, true>), grid, block, smem, stream, a); } while (0)
-  if (a.cw) { if (khilo) OMK_A8C(true); else OMK_A8C(false); }
-  else if (a.mode == GS_Y) {
-    if (precise) OMK_A8K(GS_Y, false, true, true);
-    else if (a.dump) { if (khilo) OMK_A8K(GS_Y, true, true, false); else OMK_A8K(GS_Y, true, false, false); }
-    else { if (khilo) OMK_A8K(GS_Y, false, true, false); else OMK_A8K(GS_Y, false, false, false); }
-  } else {
-    if (a.dump) OMK_A8K(GS_DX, true, false, false); else OMK_A8K(GS_DX, false, false, false);
+  void (*k)(GScan) = nullptr;
+  switch (a8_key(a.mode, pl.dump, pl.khilo, pl.precise, pl.conv)) {
+    case a8_key(GS_Y, 0, 0, 0, 0): k = ssd_a8_kernel<GS_Y, false, false, false>; break;
+    case a8_key(GS_Y, 0, 1, 0, 0): k = ssd_a8_kernel<GS_Y, false, true, false>; break;
+    case a8_key(GS_Y, 1, 0, 0, 0): k = ssd_a8_kernel<GS_Y, true, false, false>; break;
+    case a8_key(GS_Y, 1, 1, 0, 0): k = ssd_a8_kernel<GS_Y, true, true, false>; break;
+    case a8_key(GS_Y, 0, 1, 1, 0): k = ssd_a8_kernel<GS_Y, false, true, true>; break;
+    case a8_key(GS_Y, 0, 0, 0, 1): k = ssd_a8_kernel<GS_Y, false, false, false, true>; break;
+    case a8_key(GS_Y, 0, 1, 0, 1): k = ssd_a8_kernel<GS_Y, false, true, false, true>; break;
+    case a8_key(GS_DX, 0, 0, 0, 0): k = ssd_a8_kernel<GS_DX, false, false, false>; break;
+    case a8_key(GS_DX, 1, 0, 0, 0): k = ssd_a8_kernel<GS_DX, true, false, false>; break;
+    default: return fail(OMK_EINVAL, "ssd_a8: no instantiation for this plan");
   }
-#undef OMK_A8K
-#undef OMK_A8C
-  return OMK_OK;
+  const KernelId id = pl.conv ? kernel_id("ssd_a8<mode=0,dump=0,khilo=%d,precise=0,conv=1>", (int)pl.khilo)
+                              : kernel_id("ssd_a8<mode=%d,dump=%d,khilo=%d,precise=%d>", a.mode, (int)pl.dump, (int)pl.khilo, (int)pl.precise);
+  return ssd_launch(id, k, grid, block, sizeof(SmemA8), stream, a);
 }
 
 }  // namespace omk

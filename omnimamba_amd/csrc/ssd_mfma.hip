@@ -934,9 +934,10 @@ __global__ void ssd_reduce_partials_kernel(const uint16_t* part, void* out, int6
 int ssd_reduce_partials(const float* part, void* out, int64_t osb, int64_t osl, int64_t osg, int out_dt, int B, int L, int G, int H, omk_stream stream) {
   const int64_t total = (int64_t)B * L * G * 16;
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  OMK_LAUNCH(ssd_reduce_partials_kernel, grid, block, 0, stream, (const uint16_t*)part, out, osb, osl, osg, out_dt, B, L, G, H / 2);
-  return OMK_OK;
+  return ssd_launch(kernel_id("ssd_reduce_partials"), ssd_reduce_partials_kernel, grid, block, 0, stream, (const uint16_t*)part, out, osb, osl, osg, out_dt, B, L, G, H / 2);
 }
+
+static_assert(QC == SEG_CHUNK, "segments are planned in chunks of SEG_CHUNK tokens");
 
 static bool src_ok16(const Src& s, bool need) {
   if (!s.p) return !need;
@@ -946,27 +947,21 @@ static bool src_ok16(const Src& s, bool need) {
 // 32-bit per-lane offsets: row strides below 2^24 elements keep every 64-row tile offset inside 31 bits
 static bool stride_ok(int64_t s) { return s >= 0 && s < ((int64_t)1 << 24); }
 
-static int ssd_mfma_launch_b(const GScan& g, omk_stream stream, int dry) {
-  if (g.DU != 128 || g.DK != 64 || g.H % 2 != 0 || (g.H / g.G) % 2 != 0 || (!g.part && !dry)) return OMK_EUNSUPPORTED;
-  if (!src_ok16(g.U, true) || !src_ok16(g.K, true) || !src_ok16(g.Q, true) || !src_ok16(g.X4, true)) return OMK_EUNSUPPORTED;
-  if (!stride_ok(g.U.sl) || !stride_ok(g.K.sl) || !stride_ok(g.Q.sl) || !stride_ok(g.X4.sl) || !stride_ok(g.K.sh)) return OMK_EUNSUPPORTED;
-  if (!g.tokscal && !dry) return OMK_EUNSUPPORTED;
-  if (dry) return OMK_OK;
-  // one head pair (x one segment of a split sequence, start states prepared by ssd_mfma_prepare_segments) per workgroup
-  GScan a = g;
-  const SegPlan sp = (a.seg && a.seg_ready) ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QC - 1) / QC};
+// a kernel addresses one (batch, head) slice through 32-bit buffer offsets: the longest row stride times L stays inside them
+static bool span_ok(int L, int64_t s0, int64_t s1, int64_t s2 = 0, int64_t s3 = 0) {
+  int64_t ms = s0 > s1 ? s0 : s1;
+  ms = ms > s2 ? ms : s2; ms = ms > s3 ? ms : s3;
+  return (int64_t)L * ms * 2 < (int64_t)0xfffff000;
+}
+
+// nseg / cps of a launch.  SEG_PREPARE: split whenever `seg` is set, and run the state pass + fold unless the start states are there
+// already; SEG_IF_READY: split only when the caller has prepared them (the passes that share another scan's start states)
+enum { SEG_PREPARE = 0, SEG_IF_READY = 1 };
+static int ssd_plan_segments(GScan& a, int when, omk_stream stream) {
+  const bool split = a.seg && (when == SEG_PREPARE || a.seg_ready);
+  const SegPlan sp = split ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + SEG_CHUNK - 1) / SEG_CHUNK};
   a.nseg = sp.nseg; a.cps = sp.cps;
-  dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
-  const size_t smem = sizeof(SmemB3);
-#define OMK_B3(MODE_, DM_) do { \
-    if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_b3_kernel<MODE_, DM_>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((ssd_mfma_b3_kernel<MODE_, DM_>), grid, block, smem, stream, a); } while (0)
-  if (a.mode == GS_DC) OMK_B3(GS_DC, 0);
-  else if (!a.dD) OMK_B3(GS_DB, 0);
-  else if (a.dDsp == 0) OMK_B3(GS_DB, 1);
-  else OMK_B3(GS_DB, 2);
-#undef OMK_B3
-  return OMK_OK;
+  return (a.nseg > 1 && !a.seg_ready) ? ssd_mfma_prepare_segments(a, stream) : OMK_OK;
 }
 
 int ssd_mfma_prepare_segments(const GScan& g, omk_stream stream, int* seg_fmt) {
@@ -977,122 +972,133 @@ int ssd_mfma_prepare_segments(const GScan& g, omk_stream stream, int* seg_fmt) {
   a.nseg = sp.nseg; a.cps = sp.cps;
   if (!a.seg || a.nseg < 2) return OMK_OK;
   dim3 block(256), sgrid((unsigned)(a.B * a.H * (a.nseg - 1)));
-  const size_t smem = sizeof(SmemA3);
   // the state pass does not depend on the mode (no output); it reads U, K, dt' and the scan direction only.  When the caller keeps the
   // final state (prefill -> decode hand-off, context-parallel shards) the segment states carry the hi + lo operand like the scan proper
   // does then: a kept final state of a SPLIT sequence (B = 1 prefill) is exact to fp32 accumulation too, not 1e-3 off.
   const bool khilo = g.mode == GS_Y && ((g.flags & (GSF_KHILO | GSF_PRECISE)) || g.fin != nullptr);
-  if (khilo) {
-    if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<GS_Y, false, true, false, true>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem);
-    OMK_LAUNCH((ssd_mfma_a3_kernel<GS_Y, false, true, false, true>), sgrid, block, smem, stream, a);
-  } else {
-    if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<GS_Y, false, true, false>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem);
-    OMK_LAUNCH((ssd_mfma_a3_kernel<GS_Y, false, true, false>), sgrid, block, smem, stream, a);
-  }
-  kernels_note("ssd_mfma_a3<segment state pass,khilo=%d>;ssd_seg_fold", (int)khilo);
+  const int rc = ssd_launch(kernel_id("ssd_mfma_a3<segment state pass,khilo=%d>", (int)khilo),
+                            khilo ? ssd_mfma_a3_kernel<GS_Y, false, true, false, true> : ssd_mfma_a3_kernel<GS_Y, false, true, false>, sgrid, block, sizeof(SmemA3), stream, a);
+  if (rc) return rc;
   dim3 fgrid((unsigned)((int64_t)a.B * a.H * (SEG_STATE / 256)));
-  OMK_LAUNCH(ssd_seg_fold_kernel, fgrid, block, 0, stream, a);
-  return OMK_OK;
+  return ssd_launch(kernel_id("ssd_seg_fold"), ssd_seg_fold_kernel, fgrid, block, 0, stream, a);
 }
 
-int ssd_mfma_state_dump(const GScan& g, omk_stream stream) {
-  if (!g.dump || g.DU != 64 || g.DK != 128) return OMK_EUNSUPPORTED;
-  {   // the scan proper dumps with the same kernel: identical images
-    const int rc = ssd_a6_state_dump(g, stream);
-    if (rc != OMK_EUNSUPPORTED) return rc;
-  }
-  GScan a = g;
-  const SegPlan sp = (a.seg && a.seg_ready) ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QC - 1) / QC};
-  a.nseg = sp.nseg; a.cps = sp.cps;
-  dim3 grid((unsigned)(a.B * a.H * a.nseg)), block(256);
-  const size_t smem = sizeof(SmemA3);
-  if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<GS_Y, false, true, false>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem);
-  OMK_LAUNCH((ssd_mfma_a3_kernel<GS_Y, false, true, false>), grid, block, smem, stream, a);
-  return OMK_OK;
+bool ssd_class_b_applies(const GScan& g) {
+  if ((g.mode != GS_DC && g.mode != GS_DB) || g.DU != 128 || g.DK != 64 || g.H % 2 != 0 || (g.H / g.G) % 2 != 0) return false;
+  if (!src_ok16(g.U, true) || !src_ok16(g.K, true) || !src_ok16(g.Q, true) || !src_ok16(g.X4, true)) return false;
+  return stride_ok(g.U.sl) && stride_ok(g.K.sl) && stride_ok(g.Q.sl) && stride_ok(g.X4.sl) && stride_ok(g.K.sh);
 }
 
-int ssd_mfma_state_only(const GScan& g, omk_stream stream) {
-  if (g.mode != GS_Y || g.DU != 64 || g.DK != 128 || !g.fin || (g.H / g.G) < 1) return OMK_EUNSUPPORTED;
-  if (!src_ok16(g.U, true) || !src_ok16(g.K, true) || !stride_ok(g.K.sl) || !stride_ok(g.U.sl)) return OMK_EUNSUPPORTED;
-  {
-    const int64_t ms = g.K.sl > g.U.sl ? g.K.sl : g.U.sl;
-    if ((int64_t)g.L * ms * 2 >= (int64_t)0xfffff000) return OMK_EUNSUPPORTED;
-  }
-  {   // the column-slice kernel's state pass: the state a scan with final states carries
-    GScan q = g; q.Q = q.K;
-    const int rc = ssd_a6_state_only(q, stream);
-    if (rc != OMK_EUNSUPPORTED) return rc;
-  }
+static int ssd_mfma_launch_b(const GScan& g, omk_stream stream) {
+  if (!ssd_class_b_applies(g) || !g.part || !g.tokscal) return OMK_EUNSUPPORTED;
+  // one head pair (x one segment of a split sequence, start states prepared by ssd_mfma_prepare_segments) per workgroup
   GScan a = g;
-  a.Q = a.K;   // never read by the state pass; keeps the buffer descriptors well formed
-  a.state_only = 1; a.out = nullptr; a.outx = nullptr; a.dump = nullptr;
-  const SegPlan sp = a.seg ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QC - 1) / QC};
-  if (sp.nseg > 1) {
-    int rc = ssd_mfma_prepare_segments(a, stream);
-    if (rc) return rc;
-    a.seg_ready = 1;
-  }
-  a.nseg = sp.nseg; a.cps = sp.cps;
-  dim3 grid((unsigned)(a.B * a.H * a.nseg)), block(256);
-  const size_t smem = sizeof(SmemA3);
-  if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<GS_Y, false, true, false>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem);
-  OMK_LAUNCH((ssd_mfma_a3_kernel<GS_Y, false, true, false>), grid, block, smem, stream, a);
-  return OMK_OK;
+  ssd_plan_segments(a, SEG_IF_READY, stream);
+  dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
+  const int dmode = (a.mode == GS_DC || !a.dD) ? 0 : a.dDsp == 0 ? 1 : 2;
+  void (*k)(GScan) = a.mode == GS_DC ? ssd_mfma_b3_kernel<GS_DC, 0> : dmode == 0 ? ssd_mfma_b3_kernel<GS_DB, 0> : dmode == 1 ? ssd_mfma_b3_kernel<GS_DB, 1> : ssd_mfma_b3_kernel<GS_DB, 2>;
+  return ssd_launch(kernel_id("ssd_mfma_b3<mode=%d,dmode=%d>", a.mode, dmode), k, grid, block, sizeof(SmemB3), stream, a);
 }
 
-int ssd_mfma_launch(const GScan& g, omk_stream stream, int dry) {
-  if (g.mode == GS_DC || g.mode == GS_DB) return ssd_mfma_launch_b(g, stream, dry);
-  if (g.mode != GS_Y && g.mode != GS_DX) return OMK_EUNSUPPORTED;
-  if (g.DU != 64 || g.DK != 128 || (g.H / g.G) < 1) return OMK_EUNSUPPORTED;
-  if (!src_ok16(g.U, true) || !src_ok16(g.K, true) || !src_ok16(g.Q, true) || !src_ok16(g.Z, false)) return OMK_EUNSUPPORTED;
-  if (g.out_dt != OMK_BF16 || ((uintptr_t)g.out & 15) || g.osb % 8 || g.osl % 8 || g.osh % 8) return OMK_EUNSUPPORTED;
-  if (g.outx && ((uintptr_t)g.outx & 15)) return OMK_EUNSUPPORTED;
-  if (g.mode == GS_DX && g.dD) return OMK_EUNSUPPORTED;   // dD comes from the dB scan
-  if (!stride_ok(g.K.sl) || !stride_ok(g.Q.sl) || !stride_ok(g.U.sl) || !stride_ok(g.osl) || (g.Z.p && !stride_ok(g.Z.sl))) return OMK_EUNSUPPORTED;
-  {   // the class A kernel addresses one (batch, head) slice through 32-bit buffer offsets
-    int64_t ms = g.K.sl > g.Q.sl ? g.K.sl : g.Q.sl;
-    ms = ms > g.U.sl ? ms : g.U.sl; ms = ms > g.osl ? ms : g.osl;
-    if ((int64_t)g.L * ms * 2 >= (int64_t)0xfffff000) return OMK_EUNSUPPORTED;
-  }
-  if (dry) return OMK_OK;
-  // PRECISE exists as an instantiation of the specialised-wave kernel; a PRECISE call on another shape (gate / pre-gate copy in the epilogue, D per
-  // (head, column), heads that do not pair up) takes the caller's fall-back chain: the fp32 VALU scan, which rounds nothing
-  if ((g.flags & GSF_PRECISE) && g.mode == GS_Y && !ssd_a8_applies(g)) return OMK_EUNSUPPORTED;
-  if (ssd_a6_applies(g)) return ssd_a6_launch(g, stream);
-  // one head (x one segment of the sequence) per workgroup, two workgroups per CU
-  GScan a = g;
-  const SegPlan sp = a.seg ? ssd_segments(a.B * a.H, a.L) : SegPlan{1, (a.L + QC - 1) / QC};
-  a.nseg = sp.nseg; a.cps = sp.cps;
-  dim3 grid((unsigned)(a.B * a.H * a.nseg)), block(256);
-  const size_t smem = sizeof(SmemA3);
-#define OMK_A3K(MODE_, EX_, ST_, DF_, KH_, GRID_) do { \
-    kernels_note("ssd_mfma_a3<mode=%d,ex=%d,state=%d,dfold=%d,khilo=%d>", (int)MODE_, (int)EX_, (int)ST_, (int)DF_, (int)KH_); \
-    if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<MODE_, EX_, ST_, DF_, KH_>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((ssd_mfma_a3_kernel<MODE_, EX_, ST_, DF_, KH_>), GRID_, block, smem, stream, a); } while (0)
-  const bool khilo = (g.flags & (GSF_KHILO | GSF_PRECISE)) || OMK_SSD_KHILO_DEFAULT != 0;
-#define OMK_A3(MODE_, EX_, ST_, DF_, GRID_) do { \
-    if (MODE_ == GS_Y && khilo) OMK_A3K(MODE_, EX_, ST_, DF_, (MODE_ == GS_Y), GRID_); else OMK_A3K(MODE_, EX_, ST_, DF_, false, GRID_); } while (0)
-  if (a.nseg > 1 && !a.seg_ready) {
-    int rc = ssd_mfma_prepare_segments(g, stream);
-    if (rc) return rc;
-  }
-  const bool dfold = !a.D || a.Dsp == 0;   // one D per head (or none)
-  if (a.mode == GS_Y && (a.Z.p || a.outx)) { if (dfold) OMK_A3(GS_Y, true, false, true, grid); else OMK_A3(GS_Y, true, false, false, grid); }
-  else if (a.mode == GS_Y && a.dump) {   // (ssd.hip only asks for dumps without gate / pre-gate copy / KHILO)
-    if (khilo) return OMK_EUNSUPPORTED;
-    if (dfold) {
-      if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<GS_Y, false, false, true, false, true>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem);
-      OMK_LAUNCH((ssd_mfma_a3_kernel<GS_Y, false, false, true, false, true>), grid, block, smem, stream, a);
-    } else {
-      if (OMK_SET_MAX_DYN_SMEM((ssd_mfma_a3_kernel<GS_Y, false, false, false, false, true>), smem)) return fail(OMK_ELAUNCH, "ssd_mfma: cannot raise dynamic LDS to %zu", smem);
-      OMK_LAUNCH((ssd_mfma_a3_kernel<GS_Y, false, false, false, false, true>), grid, block, smem, stream, a);
+// The ONE place that decides which class A kernel takes a descriptor.  Everything here is a property of the descriptor: nothing is
+// launched, and a caller that only wants to know (window-state sizes, the backward's path, the fused conv) asks the same function.
+ClassAPlan ssd_class_a_plan(const GScan& g) {
+  const ClassAPlan none = {};
+  ClassAPlan p = {};
+  if ((g.mode != GS_Y && g.mode != GS_DX) || g.DU != 64 || g.DK != 128 || (g.H / g.G) < 1) return none;
+  p.variant = g.out ? CA_SCAN : g.dump ? CA_STATE_DUMP : CA_STATE_ONLY;
+  // the column-slice and specialised-wave kernels work on head PAIRS that share a group; the row-strip kernel takes the others
+  const bool pairs = g.H % 2 == 0 && (g.H / g.G) % 2 == 0;
+  if (p.variant != CA_SCAN) {
+    // state passes exist on the column-slice and the row-strip kernel (GSF_COLUMN_SLICE changes nothing), forward in time only
+    if (g.mode != GS_Y) return none;
+    if (p.variant == CA_STATE_ONLY) {   // (the state-dump pass belongs to a backward whose scans passed the checks of the scan proper on the same tensors)
+      if (!g.fin || !src_ok16(g.U, true) || !src_ok16(g.K, true) || !stride_ok(g.K.sl) || !stride_ok(g.U.sl) || !span_ok(g.L, g.K.sl, g.U.sl)) return none;
     }
+    p.family = pairs ? CA_A6 : CA_A3;
+    return p;
   }
-  else if (a.mode == GS_Y) { if (dfold) OMK_A3(GS_Y, false, false, true, grid); else OMK_A3(GS_Y, false, false, false, grid); }
-  else OMK_A3(GS_DX, false, false, false, grid);
-#undef OMK_A3
-#undef OMK_A3K
-  return OMK_OK;
+  // ---- the scan proper: dtype, alignment, strides, 32-bit span
+  if (!src_ok16(g.U, true) || !src_ok16(g.K, true) || !src_ok16(g.Q, true) || !src_ok16(g.Z, false)) return none;
+  if (g.out_dt != OMK_BF16 || ((uintptr_t)g.out & 15) || g.osb % 8 || g.osl % 8 || g.osh % 8) return none;
+  if (g.outx && ((uintptr_t)g.outx & 15)) return none;
+  if (g.mode == GS_DX && g.dD) return none;   // dD comes from the dB scan
+  if (!stride_ok(g.K.sl) || !stride_ok(g.Q.sl) || !stride_ok(g.U.sl) || !stride_ok(g.osl) || (g.Z.p && !stride_ok(g.Z.sl))) return none;
+  if (!span_ok(g.L, g.K.sl, g.Q.sl, g.U.sl, g.osl)) return none;
+  const bool fwd = g.mode == GS_Y;
+  p.extras = fwd && (g.Z.p || g.outx);
+  p.dfold = !g.D || g.Dsp == 0;
+  p.dump = g.dump != nullptr;
+  // the specialised-wave kernel has the plain scans only; GSF_COLUMN_SLICE hands them to the column-slice kernel
+  p.family = !pairs ? CA_A3 : (!(g.flags & GSF_COLUMN_SLICE) && !p.extras && p.dfold) ? CA_A8 : CA_A6;
+  // PRECISE exists as an instantiation of the specialised-wave kernel; a PRECISE call on another shape (gate / pre-gate copy in the
+  // epilogue, D per (head, column), heads that do not pair up) takes the caller's fall-back chain: the fp32 VALU scan, which rounds nothing
+  p.precise = fwd && (g.flags & GSF_PRECISE);
+  if (p.precise && p.family != CA_A8) return none;
+  // hi + lo state-update operand: on request (OMK_SSD_KHILO / OMK_SSD_PRECISE), and on the pair kernels whenever the caller keeps the
+  // final state (prefill -> decode hand-off, context-parallel shards: the carried state is then exact to fp32 accumulation).  The
+  // row-strip scan does NOT switch it on for a kept final state -- the families have differed in this since the pair kernels got the
+  // rule, and the difference stays (only the segment state pass of a split sequence follows the rule on every family)
+  const bool asked = (g.flags & (GSF_KHILO | GSF_PRECISE)) != 0;
+  p.khilo = fwd && (asked || (p.family == CA_A3 ? OMK_SSD_KHILO_DEFAULT != 0 : g.fin != nullptr));
+  // window states leave the plain forward only: not with a gate / pre-gate copy, not from a PRECISE scan, and the row-strip kernel has
+  // no instantiation that dumps with the hi + lo operand
+  if (fwd && p.dump && (p.extras || p.precise || (p.family == CA_A3 && p.khilo))) return none;
+  if (p.family == CA_A3 && !fwd) { p.dfold = false; p.dump = false; }   // the row-strip dx scan is one instantiation: D per column, dumps decided at run time
+  // the fused conv: the plain forward of an unsplit sequence on the specialised-wave kernel
+  p.conv = g.cw != nullptr;
+  if (p.conv && (p.family != CA_A8 || !fwd || p.dump || p.precise || g.reverse || g.cW < 1 || g.cW > 4 ||
+                 (g.seg && ssd_segments(g.B * g.H, g.L).nseg > 1))) return none;
+  return p;
+}
+
+constexpr int a3_key(int mode, bool ex, bool dfold, bool khilo, bool dump) { return mode | ex << 2 | dfold << 3 | khilo << 4 | dump << 5; }
+
+// one head (x one segment of the sequence) per workgroup, two workgroups per CU
+static int ssd_a3_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
+  dim3 grid((unsigned)(a.B * a.H * a.nseg)), block(256);
+  if (pl.variant != CA_SCAN)
+    return ssd_launch(kernel_id(pl.variant == CA_STATE_ONLY ? "ssd_mfma_a3<state_only>" : "ssd_mfma_a3<state_dump>"), ssd_mfma_a3_kernel<GS_Y, false, true, false>,
+                      grid, block, sizeof(SmemA3), stream, a);
+  void (*k)(GScan) = nullptr;
+  switch (a3_key(a.mode, pl.extras, pl.dfold, pl.khilo, pl.dump)) {
+    case a3_key(GS_Y, 0, 0, 0, 0): k = ssd_mfma_a3_kernel<GS_Y, false, false, false, false>; break;
+    case a3_key(GS_Y, 0, 0, 1, 0): k = ssd_mfma_a3_kernel<GS_Y, false, false, false, true>; break;
+    case a3_key(GS_Y, 0, 1, 0, 0): k = ssd_mfma_a3_kernel<GS_Y, false, false, true, false>; break;
+    case a3_key(GS_Y, 0, 1, 1, 0): k = ssd_mfma_a3_kernel<GS_Y, false, false, true, true>; break;
+    case a3_key(GS_Y, 1, 0, 0, 0): k = ssd_mfma_a3_kernel<GS_Y, true, false, false, false>; break;
+    case a3_key(GS_Y, 1, 0, 1, 0): k = ssd_mfma_a3_kernel<GS_Y, true, false, false, true>; break;
+    case a3_key(GS_Y, 1, 1, 0, 0): k = ssd_mfma_a3_kernel<GS_Y, true, false, true, false>; break;
+    case a3_key(GS_Y, 1, 1, 1, 0): k = ssd_mfma_a3_kernel<GS_Y, true, false, true, true>; break;
+    case a3_key(GS_Y, 0, 0, 0, 1): k = ssd_mfma_a3_kernel<GS_Y, false, false, false, false, true>; break;
+    case a3_key(GS_Y, 0, 1, 0, 1): k = ssd_mfma_a3_kernel<GS_Y, false, false, true, false, true>; break;
+    case a3_key(GS_DX, 0, 0, 0, 0): k = ssd_mfma_a3_kernel<GS_DX, false, false, false, false>; break;
+    default: return fail(OMK_EINVAL, "ssd_mfma_a3: no instantiation for this plan");
+  }
+  const KernelId id = pl.dump ? kernel_id("ssd_mfma_a3<mode=%d,ex=%d,state=0,dfold=%d,khilo=%d,dump=1>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.khilo)
+                              : kernel_id("ssd_mfma_a3<mode=%d,ex=%d,state=0,dfold=%d,khilo=%d>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.khilo);
+  return ssd_launch(id, k, grid, block, sizeof(SmemA3), stream, a);
+}
+
+int ssd_class_a_launch(const ClassAPlan& pl, const GScan& g, omk_stream stream) {
+  if (pl.family == CA_NONE) return OMK_EUNSUPPORTED;
+  GScan a = g;
+  if (pl.variant != CA_SCAN) { a.out = nullptr; a.outx = nullptr; a.Z = Src{}; a.D = nullptr; }   // a state pass writes no output
+  if (pl.variant == CA_STATE_ONLY) { a.Q = a.K; a.dump = nullptr; a.state_only = 1; }   // (Q is never read by a state pass; this keeps the buffer descriptors well formed)
+  if (pl.variant == CA_STATE_DUMP) a.fin = nullptr;
+  // the state-dump pass shares the start states the backward prepared for its dC scan; every other launch prepares its own
+  const int rc = ssd_plan_segments(a, pl.variant == CA_STATE_DUMP ? SEG_IF_READY : SEG_PREPARE, stream);
+  if (rc) return rc;
+  switch (pl.family) {
+    case CA_A8: return ssd_a8_launch(pl, a, stream);
+    case CA_A6: return ssd_a6_launch(pl, a, stream);
+    default: return ssd_a3_launch(pl, a, stream);
+  }
+}
+
+int ssd_mfma_launch(const GScan& g, omk_stream stream) {
+  if (g.mode == GS_DC || g.mode == GS_DB) return ssd_mfma_launch_b(g, stream);
+  return ssd_class_a_launch(ssd_class_a_plan(g), g, stream);
 }
 
 }  // namespace omk

@@ -7,8 +7,18 @@
 // backward dC : U = B  (group, N)  K = x (head, P)   Q = dy (head, P)   a = dt'A   w = dt'   t ascending
 //          dx : U = dy (head, P)   K = C (group, N)  Q = B (group, N)   a_t := dt'_{t+1} A, w = 1, t descending
 //          dB : U = C  (group, N)  K = dy (head, P)  Q = x (head, P)    a_t := dt'_{t+1} A, w = 1, t descending
-// (derivation checked against autograd in tests/test_bwd_derivation.py).  Two implementations consume this
-// descriptor: the shape-generic fp32 VALU kernel (ssd.hip) and the MFMA chunked kernel (ssd_mfma.hip).
+// (derivation checked against autograd in tests/test_bwd_derivation.py).
+//
+// Kernels that consume this descriptor, and who picks among them:
+//   ssd.hip       ssd_generic    any shape and dtype, fp32 VALU: the end of every fall-back chain
+//   ssd_f32.hip   ssd_f32_mfma   forward y of fp32 activations (headdim 64, d_state 128)
+//   class A (y, dx: bf16, state 64 x 128) -- ssd_class_a_plan() below is the ONE place that decides which of them takes a descriptor:
+//     ssd_a8.hip    ssd_a8       specialised waves; head pairs that share a group, no gate / pre-gate copy, one D per head
+//     ssd_a6.hip    ssd_a6       column slices; head pairs that share a group (gate, pre-gate copy, D per (head, column), state passes)
+//     ssd_mfma.hip  ssd_mfma_a3  row strips; one head per workgroup (odd head counts, one head per group)
+//   class B (dC, dB: bf16, state 128 x 64): ssd_mfma.hip ssd_mfma_b3 (ssd_class_b_applies)
+//   ssd_cp.hip    ssd_cp         chunk-parallel dB / dC from dumped window states
+// Every launch of a class A / B kernel goes through ssd_launch(), which records its id for omk_ssd_last_kernels().
 #pragma once
 #include <cstdlib>
 #include "omk_common.h"
@@ -74,6 +84,7 @@ struct GScan {
 };
 
 constexpr int SEG_STATE = 64 * 128;
+constexpr int SEG_CHUNK = 64;   // tokens per chunk of every MFMA scan kernel (QC, QA6, QA8): segments are whole chunks
 struct SegPlan { int nseg, cps; };
 // Few (batch, head) sequences leave CUs idle (B = 1, H = 64: a quarter of the chip).  Cut L so that up to two
 // workgroups per CU exist; the extra state pass re-reads x and B and costs about a third of a scan, so the split
@@ -85,7 +96,7 @@ struct SegPlan { int nseg, cps; };
 // and at L = 130 an interval of 2 already breaks the 6e-3 bound on d(dt).  So: every boundary.
 constexpr int ssd_ckpt_every() { return 1; }
 inline SegPlan ssd_segments(int BH, int L) {
-  const int nC = (L + 63) / 64;
+  const int nC = (L + SEG_CHUNK - 1) / SEG_CHUNK;
   SegPlan p = {1, nC};
   const int minc = test_hook("OMK_SSD_SEG_CHUNKS", 8);   // chunks per segment at least (the test hook lets short sequences split)
   if (BH <= 0 || BH > 128) return p;
@@ -104,24 +115,57 @@ inline size_t ssd_seg_bytes(int BH, int L) {
 
 int ssd_generic_launch(const GScan& g, omk_stream stream);
 int ssd_f32_mfma_launch(const GScan& g, omk_stream stream);   // fp32 activations on the fp32 matrix instruction (forward y only); OMK_EUNSUPPORTED otherwise
-// returns OMK_EUNSUPPORTED (without touching the error text) when the shape/dtype/layout is outside the MFMA kernel
-int ssd_mfma_launch(const GScan& g, omk_stream stream, int dry = 0);   // dry = 1: only answer whether it applies
+
+// ---- which class A kernel takes a descriptor (decided without launching) ---------------------------------------------------------
+enum { CA_NONE = 0, CA_A3, CA_A6, CA_A8 };              // ClassAPlan::family: nobody / row strips / column slices / specialised waves
+enum { CA_SCAN = 0, CA_STATE_ONLY, CA_STATE_DUMP };     // ClassAPlan::variant
+struct ClassAPlan {
+  int family;
+  // a descriptor with `out` is the scan proper.  Without: a state pass over the whole sequence that writes no output -- with `dump` it
+  // leaves the window-boundary states there (the recomputing backward), otherwise the state behind the sequence in `fin`
+  int variant;
+  // the template switches of the scan proper (a state pass has one instantiation per family)
+  bool extras;    // gate and / or pre-gate copy in the epilogue
+  bool dfold;     // one D per head (or none)
+  bool dump;      // writes window states
+  bool khilo;     // state-update operand as bf16 hi + lo
+  bool precise;   // ... and the carried state meets Q as hi + lo
+  bool conv;      // causal conv1d + SiLU on U while it is staged
+};
+ClassAPlan ssd_class_a_plan(const GScan& g);
+// launches what the plan says (segment state pass + fold first where a split sequence needs them); OMK_EUNSUPPORTED, without touching
+// the error text, for CA_NONE
+int ssd_class_a_launch(const ClassAPlan& pl, const GScan& g, omk_stream stream);
+// the per-family ends of ssd_class_a_launch, each in its kernel's file: `a` is the final descriptor (segments planned)
+int ssd_a6_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream);
+int ssd_a8_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream);
+// class B (dC / dB): shape, alignment and stride checks (the launch also needs the workspace pointers part and tokscal)
+bool ssd_class_b_applies(const GScan& g);
+// any MFMA scan: class A through its plan, class B.  OMK_EUNSUPPORTED (without touching the error text) when the shape / dtype / layout
+// is outside these kernels
+int ssd_mfma_launch(const GScan& g, omk_stream stream);
 // split sequences (GScan::seg set, class A style descriptor): state-only pass + fold; afterwards slot j - 1 of g.seg is the
 // state at the START of segment j (initial state included).  Shared by the scans whose state this is (y and dC; dx and dB).
 int ssd_mfma_prepare_segments(const GScan& g, omk_stream stream, int* seg_fmt = nullptr);   // *seg_fmt: the order it left the states in
-// the column-slice class A kernel (ssd_a6.hip): state slices in registers, 32-token sub-chunks, intra tiles shared through LDS, one
-// workgroup per head pair (its 16-token predecessor ssd_a5.hip and their experiments: git history, profiles/r04_a5_a6_experiments.txt)
-bool ssd_a6_applies(const GScan& g);
-int ssd_a6_launch(const GScan& g, omk_stream stream);
-int ssd_a6_state_only(const GScan& g, omk_stream stream);
-// the specialised-wave class A kernel (ssd_a8.hip): four compute waves of 32 state columns + four helper waves per head pair
-bool ssd_a8_applies(const GScan& g);   // (no: ssd_a6.hip takes the shape)
-int ssd_a8_launch(const GScan& g, omk_stream stream);
-int ssd_a6_state_dump(const GScan& g, omk_stream stream);   // OMK_EUNSUPPORTED when the column-slice kernel does not take the shape
-// state-only pass over the whole sequence that leaves the window-boundary states in g.dump (class A descriptor, no output)
-int ssd_mfma_state_dump(const GScan& g, omk_stream stream);
-// state-only pass that leaves the state behind the sequence in g.fin (OMK_EUNSUPPORTED outside the MFMA shape)
-int ssd_mfma_state_only(const GScan& g, omk_stream stream);
+
+// ---- the one way a class A / B kernel is launched: its id goes to omk_ssd_last_kernels(), the dynamic LDS limit is raised, then the launch
+struct KernelId { char s[96]; };
+inline KernelId kernel_id(const char* fmt, ...) {
+  KernelId k;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(k.s, sizeof(k.s), fmt, ap);
+  va_end(ap);
+  return k;
+}
+template <class T> struct arg_of { typedef T type; };   // (keeps the kernel's own parameter types: arguments convert, they are not deduced)
+template <class... P>
+int ssd_launch(const KernelId& id, void (*kern)(P...), dim3 grid, dim3 block, size_t smem, omk_stream stream, typename arg_of<P>::type... args) {
+  kernels_note("%s", id.s);
+  if (smem && OMK_SET_MAX_DYN_SMEM(kern, smem)) return fail(OMK_ELAUNCH, "%s: cannot raise dynamic LDS to %zu", id.s, smem);
+  OMK_LAUNCH(kern, grid, block, smem, stream, args...);
+  return OMK_OK;
+}
 // chunk-parallel dB / dC / token scalars from the dumped states (ssd_cp.hip)
 struct CpArgs {
   const uint16_t *X, *DY; int64_t xsb, xsl, xsh, ysb, ysl, ysh;   // (B, L, H, 64) bf16

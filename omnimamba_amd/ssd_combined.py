@@ -160,19 +160,11 @@ def ssd_scan_fwd_fused_conv(xBC, dt, A, conv_weight, conv_bias, nheads, headdim,
     pc = K.Conv1dFwd(x=K.T(xBC[..., d_ssm:].transpose(1, 2)), weight=K.T(wbc), bias=K.T(bbc), initial_states=K.T(None),
                      out=K.T(bc.transpose(1, 2)), final_states=K.T(None if conv_state_out is None else conv_state_out[:, d_ssm:]), silu=1,
                      seq_lens=K.T(seq_lens))
-    fn = lib.omk_ssd_scan_fwd
-    import ctypes as C_
-    if lib.omk_is_emulated():
-        K.run(lib, "omk_causal_conv1d_fwd", pc, xBC)
-        rc = fn(C_.byref(p), None)
-    else:
-        with torch.cuda.device(xBC.device):
-            K.run(lib, "omk_causal_conv1d_fwd", pc, xBC)
-            with _prof.range_("ssd_scan_fwd_fused_conv"):
-                rc = fn(C_.byref(p), K.stream_of(lib, xBC))
-    if rc == -4:      # OMK_EUNSUPPORTED: heads that do not pair up, a sequence the scan splits, strides outside the MFMA kernel
-        return None
-    K.check(lib, rc, "omk_ssd_scan_fwd (fused conv)")
+    K.run(lib, "omk_causal_conv1d_fwd", pc, xBC)
+    with _prof.range_("ssd_scan_fwd_fused_conv"):
+        # declined: heads that do not pair up, a sequence the scan splits, strides outside the MFMA kernel
+        if not K.try_run(lib, "omk_ssd_scan_fwd", p, xBC):
+            return None
     if conv_state_out is not None:      # the x rows of the conv state: the last state_len pre-conv inputs (left zero padded)
         sl = conv_state_out.shape[-1]
         cs = conv_state_out[:, :d_ssm]
@@ -258,17 +250,8 @@ def ssd_final_state_raw(x, dt, A, B, dt_bias=None, initial_states=None, dt_softp
                      initial_states=K.T(initial_states), final_states=K.T(fin), dt_min=float(dt_limit[0]), dt_max=float(dt_limit[1]),
                      dt_softplus=int(dt_softplus), chunk_size=256, flags=int(current_scan_flags()) & ~K.SSD_SEQUENTIAL_BWD)
         ws = K.workspace(lib, "omk_ssd_scan_fwd_workspace_bytes", p, x)  # noqa: F841
-        fn = getattr(lib, "omk_ssd_scan_fwd")
-        import ctypes as C
-        if lib.omk_is_emulated():
-            rc = fn(C.byref(p), None)
-        else:
-            with torch.cuda.device(x.device):
-                rc = fn(C.byref(p), K.stream_of(lib, x))
-        if rc == 0:
-            return fin
-        if rc != -4:       # OMK_EUNSUPPORTED (strides / alignment outside the MFMA kernel): fall through to the scan
-            K.check(lib, rc, "omk_ssd_scan_fwd (state only)")
+        if K.try_run(lib, "omk_ssd_scan_fwd", p, x):
+            return fin      # (declined -- strides / alignment outside the MFMA kernel: fall through to the scan)
     return ssd_scan_fwd(x, dt, A, B, B, dt_bias=dt_bias, initial_states=initial_states, dt_softplus=dt_softplus, dt_limit=dt_limit,
                         return_final_states=True)[2]
 
