@@ -251,9 +251,11 @@ typedef struct {
   size_t workspace_bytes;
   int32_t delta_softplus;
 } OmkSelScanBwd;
-/* ABI 6: which form omk_selective_scan_bwd takes on these views: 2 = the lanes-are-channels reverse sweep on channel-last (B, L, D) views
- * as they lie (input-dependent B / C of u's dtype, d_state <= 16, enough sequences to fill the chip), 1 = the chunked scan (L-contiguous rows),
- * 0 = the per-channel kernel.  The host mirror asks before it decides about L-contiguous copies (omk_selective_scan_fwd_form's twin). */
+/* ABI 6: which form omk_selective_scan_bwd takes on these views (nothing is launched; it is the launch's own decision): 2 = the
+ * lanes-are-channels reverse sweep on channel-last (B, L, D) views as they lie (input-dependent B / C of u's dtype, d_state <= 16, enough
+ * sequences to fill the chip), 1 = the chunked scan (L-contiguous u / delta / z / dout / du / ddelta / dz / B / C, input-dependent B / C of
+ * u's dtype, fp32 A, 8 | channels per group, L >= 64), 0 = the per-channel kernel (which refuses d_state > 16).  The host mirror asks
+ * before it decides about L-contiguous copies (omk_selective_scan_fwd_form's twin). */
 int omk_selective_scan_bwd_form(const OmkSelScanBwd* p);
 size_t omk_selective_scan_bwd_workspace_bytes(const OmkSelScanBwd* p);
 int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream);   /* L-contiguous rows, variable B / C, L >= 64, 8 | channels
@@ -383,9 +385,10 @@ typedef struct {
                                  * drifts by 2^60 (the arithmetic of the column-slice kernel, bit for bit; tests) */
 #define OMK_SSD_NO_SPLIT     8  /* never cut the sequence into segments (few (batch, head) sequences normally are: csrc/ssd_scan.h) */
 #define OMK_SSD_COLUMN_SLICE 16 /* class A scans on the column-slice kernel (ssd_a6.hip) instead of the specialised-wave kernel */
-/* Measurement aid (ABI 6): the scan kernels the LAST omk_ssd_scan_fwd / omk_ssd_scan_bwd call of this thread launched, ';'-separated,
- * template arguments included, e.g. "ssd_dt_prep;ssd_a8<mode=0,dump=1,khilo=0,precise=0>".  bench.py puts it next to its HIP-event
- * time and refuses a PMC traffic file (profiles/ssd_*_traffic.json) recorded for another kernel. */
+/* Measurement aid (ABI 6): the scan kernels the LAST scan call of this thread launched -- omk_ssd_scan_fwd / _bwd or
+ * omk_selective_scan_fwd / _bwd, whichever came last -- ';'-separated, template arguments included, e.g.
+ * "ssd_dt_prep;ssd_a8<mode=0,dump=1,khilo=0,precise=0>" or "selscan_fwd_shared<lc=8,nu=2,state_only=0>".  bench.py puts it next to its
+ * HIP-event time and refuses a PMC traffic file (profiles/ssd_*_traffic.json) recorded for another kernel. */
 const char* omk_ssd_last_kernels(void);
 size_t omk_ssd_scan_fwd_workspace_bytes(const OmkSsdFwd* p);
 /* bytes of window_states for these arguments (window_states itself is not looked at); 0 = this forward cannot save them (shape

@@ -12,8 +12,8 @@ namespace omk {
 // ---- thread-local error text --------------------------------------------------------------------------
 char* err_buf();
 int fail(int code, const char* fmt, ...);
-// which scan kernels the last omk_ssd_scan_fwd / omk_ssd_scan_bwd of this thread launched (omk_ssd_last_kernels: measurement tools tie a
-// profile to the kernel that was timed)
+// which scan kernels the last scan call of this thread launched -- omk_ssd_scan_fwd / _bwd or omk_selective_scan_fwd / _bwd, each resets
+// the list on entry (omk_ssd_last_kernels: measurement tools tie a profile to the kernel that was timed, the dispatch tests read it)
 void kernels_reset();
 void kernels_note(const char* fmt, ...);
 #define OMK_REQUIRE(cond, ...) \
@@ -48,6 +48,25 @@ inline bool strides_multiple_of(const OmkTensor& t, int64_t elems) {
   return true;
 }
 int finish_launch(const char* what);
+
+// ---- the one way a scan kernel is launched: its id goes to omk_ssd_last_kernels(), the dynamic LDS limit is raised, then the launch
+struct KernelId { char s[96]; };
+inline KernelId kernel_id(const char* fmt, ...) {
+  KernelId k;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(k.s, sizeof(k.s), fmt, ap);
+  va_end(ap);
+  return k;
+}
+template <class T> struct arg_of { typedef T type; };   // (keeps the kernel's own parameter types: arguments convert, they are not deduced)
+template <class... P>
+int omk_launch(const KernelId& id, void (*kern)(P...), dim3 grid, dim3 block, size_t smem, omk_stream stream, typename arg_of<P>::type... args) {
+  kernels_note("%s", id.s);
+  if (smem && OMK_SET_MAX_DYN_SMEM(kern, smem)) return fail(OMK_ELAUNCH, "%s: cannot raise dynamic LDS to %zu", id.s, smem);
+  OMK_LAUNCH(kern, grid, block, smem, stream, args...);
+  return OMK_OK;
+}
 
 // ---- test hooks -------------------------------------------------------------------------------------------
 // The only environment the library reads: a hook lowers a size threshold so that the tests reach a path at

@@ -1494,111 +1494,132 @@ static bool ss_tile_states(const OmkTensor& t, int B, int Dm, int L, int N) {
   if (t.shape[0] == B && t.shape[1] == Dm && t.shape[2] == nP && t.shape[3] == N) return false;   // the chunked form
   return t.shape[0] == B && t.shape[1] == nT && t.shape[2] == N && t.shape[3] == Dm;
 }
+static_assert(SSR_TP % SCL_TB == 0 && SSB_TL % SCL_TB == 0, "the lanes = channels sweep leaves states at multiples of its 16-token block");
 
-// The lanes = channels sweep (selscan_fwd_lanes_kernel) takes the call when it applies and the batch fills the chip by itself:
-// returns 0 (no), 2 (channel-last storage) or 3 (L-contiguous storage) and fills the buffer ranges.
-static int ss_lanes_form(SsArgs& a, int udt) {
-  if (!a.out || !a.Bvar || !a.Cvar || a.N > 16 || a.bdt != udt || a.cdt != udt) return 0;
-  if (a.ckpt && (a.TLB % SCL_TB) != 0) return 0;
-  const bool z = a.z != nullptr;
-  const bool cl = a.usd == 1 && a.dsd == 1 && (!z || a.zsd == 1) && a.osd == 1;
-  const bool lc = a.usl == 1 && a.dsl == 1 && (!z || a.zsl == 1) && a.osl == 1;
-  if (!cl && !lc) return 0;
-  const int64_t es = (int64_t)dtype_size(udt), lim = (int64_t)1 << 31;
-  auto span = [&](int64_t sd, int64_t sl, int64_t nd) -> int64_t { return (sd < 0 || sl < 0) ? lim : es * ((nd + 64) * sd + ((int64_t)a.L + 64) * sl); };
-  const int64_t su = span(a.usd, a.usl, a.Dm), sdl = span(a.dsd, a.dsl, a.Dm), sz = z ? span(a.zsd, a.zsl, a.Dm) : 0, so = span(a.osd, a.osl, a.Dm);
-  const int64_t sb = span(a.Bsn, a.Bsl, 16), sc = span(a.Csn, a.Csl, 16);
-  if (su >= lim || sdl >= lim || sz >= lim || so >= lim || sb >= lim || sc >= lim) return 0;
-  const int dpg = a.Dm / a.G;
-  const int64_t nw = (int64_t)a.B * a.G * ((dpg + 63) / 64);
+// ---- who decides: ss_fwd_plan() and ss_bwd_plan(), pure functions of the filled arguments.  The launches, both _form queries and the
+// pass_states checks of the entry points ask them (tests/test_selscan_dispatch.py holds the table call by call).
+// The layout predicates.  u / delta / z / out (absent ones aside) have unit stride along L, or along the channels (channel-last storage)
+static bool ss_unit_stride(const SsArgs& a, bool l) { return (l ? a.usl : a.usd) == 1 && (l ? a.dsl : a.dsd) == 1 && (!a.z || (l ? a.zsl : a.zsd) == 1) && (!a.out || (l ? a.osl : a.osd) == 1); }
+static bool ss_bwd_unit_stride(const SsBwdArgs& q, bool l) {   // ... and dout / du / ddelta / dz as well
+  return ss_unit_stride(q.f, l) && (l ? q.gsl : q.gsd) == 1 && (l ? q.dusl : q.dusd) == 1 && (l ? q.ddsl : q.ddsd) == 1 && (!q.f.z || (l ? q.dzsl : q.dzsd) == 1);
+}
+static bool ss_bc_along_l(const SsArgs& a) { return (!a.Bvar || a.Bsl == 1) && (!a.Cvar || a.Csl == 1); }
+// 8 adjacent channels of one group can work from one copy of the B / C rows: input-dependent B / C of u's dtype, fp32 A
+static bool ss_group_rows(const SsArgs& a, int udt) { return a.Bvar && a.Cvar && (a.Dm / a.G) % 8 == 0 && a.bdt == udt && a.cdt == udt && a.adt == OMK_F32; }
+// buffer ranges of the lanes = channels kernels, in bytes (2^31: not addressable): what the prefetching kernels may touch of nd rows
+// (up to 64 rows and 64 tokens past the end), and what one batch element spans
+constexpr int64_t SS_LIM = (int64_t)1 << 31;
+static int64_t ss_span(int64_t es, int64_t sd, int64_t sl, int64_t nd, int64_t L) { return (sd < 0 || sl < 0) ? SS_LIM : es * ((nd + 64) * sd + (L + 64) * sl); }
+static int64_t ss_ext(int64_t es, int64_t sd, int64_t sl, int64_t nd, int64_t L) { return (sd < 0 || sl < 0) ? SS_LIM : es * ((nd - 1) * sd + (L - 1) * sl + 1); }
+static int64_t ss_lanes_waves(const SsArgs& a) { return (int64_t)a.B * a.G * ((a.Dm / a.G + 63) / 64); }
+// The lanes = channels sweep (selscan_fwd_lanes_kernel, selscan_bwd_lanes_kernel) applies, on channel-last (*cl) or L-contiguous storage:
+// input-dependent B / C of u's dtype, d_state <= 16, addressable ranges, and a batch that fills the chip by itself
+static bool ss_lanes_apply(const SsArgs& a, int udt, bool* cl) {
+  if (!a.Bvar || !a.Cvar || a.N > 16 || a.bdt != udt || a.cdt != udt) return false;
+  *cl = ss_unit_stride(a, false);
+  if (!*cl && !ss_unit_stride(a, true)) return false;
+  const int64_t es = (int64_t)dtype_size(udt);
+  if (ss_span(es, a.usd, a.usl, a.Dm, a.L) >= SS_LIM || ss_span(es, a.dsd, a.dsl, a.Dm, a.L) >= SS_LIM || (a.z && ss_span(es, a.zsd, a.zsl, a.Dm, a.L) >= SS_LIM) ||
+      (a.out && ss_span(es, a.osd, a.osl, a.Dm, a.L) >= SS_LIM) || ss_span(es, a.Bsn, a.Bsl, 16, a.L) >= SS_LIM || ss_span(es, a.Csn, a.Csl, 16, a.L) >= SS_LIM)
+    return false;
   // few sequences: time has to be cut (the chunked scan).  Measured crossovers at L 1024, D 768 (tools/bench_selscan.py): channel-last
   // storage from ~200 waves (the alternative pays L-contiguous copies), L-contiguous storage from one wave per SIMD.
   // Test hook OMK_SELSCAN_LANES=1: no minimum number of waves
   const bool any_waves = test_hook("OMK_SELSCAN_LANES", 0) == 1;
-  if (!any_waves && nw < (cl ? 192 : 1024) && a.L >= 64) return 0;
-  auto ext = [&](int64_t sd, int64_t sl, int64_t nd) -> uint32_t { return (uint32_t)(es * ((nd - 1) * sd + ((int64_t)a.L - 1) * sl + 1)); };
-  a.xu = ext(a.usd, a.usl, a.Dm); a.xd = ext(a.dsd, a.dsl, a.Dm); a.xz = z ? ext(a.zsd, a.zsl, a.Dm) : 0u; a.xo = ext(a.osd, a.osl, a.Dm);
-  a.xB = ext(a.Bsn, a.Bsl, a.N); a.xC = ext(a.Csn, a.Csl, a.N);
-  return cl ? 2 : 3;
+  return any_waves || ss_lanes_waves(a) >= (*cl ? 192 : 1024) || a.L < 64;
 }
 
-// pass_ckpt: first pass of the chunked backward (a.ckpt = state in front of every 512-token pass, no output)
-static int ss_launch_fwd(SsArgs& a, int udt, omk_stream stream, bool pass_ckpt = false) {
-  if (const int form = pass_ckpt ? 0 : ss_lanes_form(a, udt)) {
-    const int dpg = a.Dm / a.G;
-    dim3 grid((unsigned)((int64_t)a.B * a.G * ((dpg + 63) / 64))), block(64);
-    if (form == 2) OMK_DISPATCH_DTYPE(udt, T, OMK_LAUNCH((selscan_fwd_lanes_kernel<T, false>), grid, block, 0, stream, a));
-    else OMK_DISPATCH_DTYPE(udt, T, OMK_LAUNCH((selscan_fwd_lanes_kernel<T, true>), grid, block, 0, stream, a));
-    return OMK_OK;
-  }
-  // L-contiguous storage (upstream's layout): the chunked associative scan, one wave per (batch, channel)
-  const bool lcontig = pass_ckpt || (a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.out && a.osl == 1 && (!a.Bvar || a.Bsl == 1) &&
-                                     (!a.Cvar || a.Csl == 1) && (!a.ckpt || a.TLB == SSR_TP) && a.L >= 64);
-  if (lcontig) {
-    const int64_t nseq = (int64_t)a.B * a.Dm;
-    // few sequences: fewer, longer passes; many: occupancy.  (Pass states: 512-token passes.)
-    const bool lc16 = !pass_ckpt && !a.ckpt && a.L >= 1024 && nseq < 4096;
-    const int lc = lc16 ? 16 : 8;
-    // shared B / C rows: 8 adjacent channels of one group per workgroup, rows of u's dtype, <= 64 KB of LDS
-    const size_t es = dtype_size(udt);
-    const size_t bc_bytes = (size_t)((a.Bvar ? a.N : 0) + (a.Cvar && !pass_ckpt ? a.N : 0)) * 64 * lc * es;
-    const bool share = a.Bvar && a.Cvar && (a.Dm / a.G) % 8 == 0 && a.bdt == udt && a.cdt == udt && a.adt == OMK_F32 && a.N <= 64 &&
-                       bc_bytes <= 64 * 1024;
-    if (share) {
-      dim3 grid((unsigned)(nseq / 8)), block(512);
-#define SSC_SH(T, LC_, NU_) do { \
-        if (OMK_SET_MAX_DYN_SMEM((selscan_fwd_shared_kernel<T, LC_, NU_>), bc_bytes)) return fail(OMK_ELAUNCH, "selective_scan_fwd: cannot raise dynamic LDS to %zu", bc_bytes); \
-        OMK_LAUNCH((selscan_fwd_shared_kernel<T, LC_, NU_>), grid, block, bc_bytes, stream, a); } while (0)
-#define SSC_ST(T) do { \
-        if (OMK_SET_MAX_DYN_SMEM((selscan_fwd_shared_kernel<T, 8, 1, true>), bc_bytes)) return fail(OMK_ELAUNCH, "selective_scan_bwd: cannot raise dynamic LDS to %zu", bc_bytes); \
-        OMK_LAUNCH((selscan_fwd_shared_kernel<T, 8, 1, true>), grid, block, bc_bytes, stream, a); } while (0)
-      if (pass_ckpt) OMK_DISPATCH_DTYPE(udt, T, SSC_ST(T));
-      else if (lc16) OMK_DISPATCH_DTYPE(udt, T, SSC_SH(T, 16, 1));
-      else OMK_DISPATCH_DTYPE(udt, T, SSC_SH(T, 8, 2));   // packed token pairs in the n loop
-#undef SSC_SH
-#undef SSC_ST
-    } else {
-      dim3 grid((unsigned)((nseq + 3) / 4)), block(256);
-      if (lc16) OMK_DISPATCH_DTYPE(udt, T, OMK_LAUNCH((selscan_fwd_chunked_kernel<T, 16>), grid, block, 0, stream, a));
-      else OMK_DISPATCH_DTYPE(udt, T, OMK_LAUNCH((selscan_fwd_chunked_kernel<T, 8>), grid, block, 0, stream, a));
-    }
-    return OMK_OK;
-  }
+// what a forward pass is for: the scan proper writes `out` (and pass_states when asked); the others start a backward, write no output, and leave the state
+enum SsRole { SS_SCAN,
+              SS_PASS_STATES,     // chunked backward: in front of every 512-token pass (the state-only instantiation of the chunked scan)
+              SS_TILE_STATES,     // lanes = channels backward: in front of every 16-token tile, channels innermost (selscan_fwd_lanes_kernel)
+              SS_CHECKPOINTS };   // per-channel backward: at every SSB_TL-token boundary (always selscan_fwd_kernel)
+struct SsFwdPlan {
+  int form;                         // 0 per-channel, 1 chunked, 2 lanes = channels (what omk_selective_scan_fwd_form answers); -1: SS_TILE_STATES where the lanes form does not apply
+  bool lcontig;                     // lanes: L-contiguous storage (tiles turned in LDS) instead of channel-last
+  bool shared, state_only;          // chunked: 8 adjacent channels of one group per workgroup share the B / C rows; no output
+  int lc, nu;                       // chunked: chunks per lane (8 / 16); shared: tokens per step of the n loop
+  int nreg, DT;                     // per-channel: state registers (16 / 64), channels per workgroup
+  dim3 grid, block; size_t smem;    // smem: dynamic LDS bytes
+  uint32_t xu, xd, xz, xo, xB, xC;  // lanes: the buffer ranges (SsArgs)
+};
+static SsFwdPlan ss_fwd_plan(const SsArgs& a, int udt, SsRole role) {
+  SsFwdPlan pl = {};
   const int dpg = a.Dm / a.G;
-  a.DT = dpg >= 128 ? 128 : ((dpg + 63) / 64) * 64;
-  const int tiles_per_group = (dpg + a.DT - 1) / a.DT;
-  dim3 grid((unsigned)((int64_t)a.B * a.G * tiles_per_group)), block(a.DT);
-  const size_t smem = (size_t)4 * SS_TL * a.DT * dtype_size(udt) + (size_t)2 * SS_TL * a.N * 4;
-#define SS_GO(T, NREG) OMK_LAUNCH((selscan_fwd_kernel<T, NREG>), grid, block, smem, stream, a)
-  OMK_DISPATCH_DTYPE(udt, T, { if (a.N <= 16) SS_GO(T, 16); else SS_GO(T, 64); });
-#undef SS_GO
-  return OMK_OK;
+  const int64_t es = (int64_t)dtype_size(udt), nseq = (int64_t)a.B * a.Dm;
+  if (bool cl = false; (role == SS_SCAN || role == SS_TILE_STATES) && ss_lanes_apply(a, udt, &cl)) {
+    pl.form = 2; pl.lcontig = !cl;
+    pl.grid = dim3((unsigned)ss_lanes_waves(a)); pl.block = dim3(64);
+    pl.xu = (uint32_t)ss_ext(es, a.usd, a.usl, a.Dm, a.L); pl.xd = (uint32_t)ss_ext(es, a.dsd, a.dsl, a.Dm, a.L);
+    pl.xz = a.z ? (uint32_t)ss_ext(es, a.zsd, a.zsl, a.Dm, a.L) : 0u; pl.xo = a.out ? (uint32_t)ss_ext(es, a.osd, a.osl, a.Dm, a.L) : 0u;
+    pl.xB = (uint32_t)ss_ext(es, a.Bsn, a.Bsl, a.N, a.L); pl.xC = (uint32_t)ss_ext(es, a.Csn, a.Csl, a.N, a.L);
+    return pl;
+  }
+  if (role == SS_TILE_STATES) { pl.form = -1; return pl; }
+  // L-contiguous storage (upstream's layout): the chunked associative scan, one wave per (batch, channel)
+  pl.state_only = role == SS_PASS_STATES;
+  if (pl.state_only || (role == SS_SCAN && ss_unit_stride(a, true) && ss_bc_along_l(a) && a.L >= 64)) {
+    pl.form = 1;
+    // few sequences: fewer, longer passes; many: occupancy.  (Pass states: 512-token passes.)
+    pl.lc = !pl.state_only && !a.ckpt && a.L >= 1024 && nseq < 4096 ? 16 : 8;
+    // shared B / C rows (the state-only pass reads no C): rows of u's dtype, <= 64 KB of LDS
+    const size_t bc_bytes = (size_t)((a.Bvar ? a.N : 0) + (a.Cvar && !pl.state_only ? a.N : 0)) * 64 * pl.lc * es;
+    pl.shared = ss_group_rows(a, udt) && bc_bytes <= 64 * 1024;
+    pl.nu = pl.state_only || pl.lc == 16 ? 1 : 2;
+    pl.grid = dim3((unsigned)(pl.shared ? nseq / 8 : (nseq + 3) / 4)); pl.block = dim3(pl.shared ? 512 : 256); pl.smem = pl.shared ? bc_bytes : 0;
+    return pl;
+  }
+  pl.nreg = a.N <= 16 ? 16 : 64; pl.DT = dpg > 64 ? 128 : 64;
+  pl.grid = dim3((unsigned)((int64_t)a.B * a.G * ((dpg + pl.DT - 1) / pl.DT))); pl.block = dim3(pl.DT);
+  pl.smem = (size_t)4 * SS_TL * pl.DT * es + (size_t)2 * SS_TL * a.N * 4;
+  return pl;
+}
+
+static int ss_fwd_launch(const SsFwdPlan& pl, SsArgs a, int udt, omk_stream stream) {
+  a.DT = pl.DT; a.xu = pl.xu; a.xd = pl.xd; a.xz = pl.xz; a.xo = pl.xo; a.xB = pl.xB; a.xC = pl.xC;
+  const KernelId id = pl.form == 2 ? kernel_id("selscan_fwd_lanes<lc=%d>", (int)pl.lcontig) : pl.form == 0 ? kernel_id("selscan_fwd<nreg=%d>", pl.nreg)
+                      : pl.shared  ? kernel_id("selscan_fwd_shared<lc=%d,nu=%d,state_only=%d>", pl.lc, pl.nu, (int)pl.state_only)
+                                   : kernel_id("selscan_fwd_chunked<lc=%d>", pl.lc);
+  int rc = OMK_OK;
+  auto go = [&](auto kern) { rc = omk_launch(id, kern, pl.grid, pl.block, pl.smem, stream, a); };
+  if (pl.form == 2 && !pl.lcontig) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_lanes_kernel<T, false>));
+  else if (pl.form == 2) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_lanes_kernel<T, true>));
+  else if (pl.form == 1 && pl.shared && pl.state_only) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_shared_kernel<T, 8, 1, true>));
+  else if (pl.form == 1 && pl.shared && pl.lc == 16) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_shared_kernel<T, 16, 1>));
+  else if (pl.form == 1 && pl.shared) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_shared_kernel<T, 8, 2>));   // packed token pairs in the n loop
+  else if (pl.form == 1 && pl.lc == 16) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_chunked_kernel<T, 16>));
+  else if (pl.form == 1) OMK_DISPATCH_DTYPE(udt, T, go(selscan_fwd_chunked_kernel<T, 8>));
+  else OMK_DISPATCH_DTYPE(udt, T, { if (pl.nreg == 16) go(selscan_fwd_kernel<T, 16>); else go(selscan_fwd_kernel<T, 64>); });
+  return rc;
+}
+
+// out, last_state and pass_states into the arguments (ss_fill has run); true: pass_states has the tile form
+static bool ss_fwd_outputs(SsArgs& a, const OmkSelScanFwd* p) {
+  a.out = p->out.data; a.last = (float*)p->last_state.data;
+  a.osb = p->out.stride[0]; a.osd = p->out.stride[1]; a.osl = p->out.stride[2];
+  const bool tiles = ss_tile_states(p->pass_states, a.B, a.Dm, a.L, a.N);
+  if (present(p->pass_states)) { a.ckpt = (float*)p->pass_states.data; a.TLB = tiles ? SBL_T : SSR_TP; a.nTB = (a.L + a.TLB - 1) / a.TLB; a.ckpt_cl = tiles; }
+  return tiles;
 }
 
 extern "C" int omk_selective_scan_fwd(const OmkSelScanFwd* p, omk_stream stream) {
+  kernels_reset();
   OMK_REQUIRE(p && present(p->out), "selective_scan_fwd: out required");
   SsArgs a = {};
   int rc = ss_fill(a, p->u, p->delta, p->A, p->Bm, p->Cm, p->D, p->z, p->delta_bias, p->delta_softplus, "selective_scan_fwd");
   if (rc) return rc;
   OMK_REQUIRE(p->out.ndim == 3 && p->out.dtype == p->u.dtype, "selective_scan_fwd: out must be (B, D, L) of u's dtype");
   OMK_REQUIRE(!present(p->last_state) || p->last_state.dtype == OMK_F32, "selective_scan_fwd: last_state must be f32");
-  a.out = p->out.data; a.last = (float*)p->last_state.data;
-  a.osb = p->out.stride[0]; a.osd = p->out.stride[1]; a.osl = p->out.stride[2];
   if ((int64_t)a.B * a.Dm * a.L == 0) return OMK_OK;
-  if (ss_tile_states(p->pass_states, a.B, a.Dm, a.L, a.N)) {
-    a.ckpt = (float*)p->pass_states.data; a.TLB = SBL_T; a.nTB = (a.L + SBL_T - 1) / SBL_T; a.ckpt_cl = 1;
-    if (ss_lanes_form(a, p->u.dtype) != 2) return fail(OMK_EUNSUPPORTED, "selective_scan_fwd: tile states (B, ceil(L / 16), N, D) belong to the lanes = channels form (channel-last views, d_state <= 16)");
-  } else if (present(p->pass_states)) {
-    const int nP = (a.L + SSR_TP - 1) / SSR_TP;
-    OMK_REQUIRE(p->pass_states.dtype == OMK_F32 && is_dense(p->pass_states) && numel(p->pass_states) == (int64_t)a.B * a.Dm * nP * a.N,
+  const bool tiles = ss_fwd_outputs(a, p);
+  const SsFwdPlan pl = ss_fwd_plan(a, p->u.dtype, SS_SCAN);
+  if (tiles && (pl.form != 2 || pl.lcontig)) return fail(OMK_EUNSUPPORTED, "selective_scan_fwd: tile states (B, ceil(L / 16), N, D) belong to the lanes = channels form (channel-last views, d_state <= 16)");
+  if (!tiles && present(p->pass_states)) {
+    OMK_REQUIRE(p->pass_states.dtype == OMK_F32 && is_dense(p->pass_states) && numel(p->pass_states) == (int64_t)a.B * a.Dm * a.nTB * a.N,
                 "selective_scan_fwd: pass_states must be contiguous f32 (B, D, ceil(L / 512), N)");
-    a.ckpt = (float*)p->pass_states.data; a.TLB = SSR_TP; a.nTB = nP;
-    if (!ss_lanes_form(a, p->u.dtype) &&
-        !(a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.osl == 1 && (!a.Bvar || a.Bsl == 1) && (!a.Cvar || a.Csl == 1) && a.L >= 64))
-      return fail(OMK_EUNSUPPORTED, "selective_scan_fwd: pass_states need L-contiguous u / delta / z / out / B / C and L >= 64");
+    if (pl.form == 0) return fail(OMK_EUNSUPPORTED, "selective_scan_fwd: pass_states need L-contiguous u / delta / z / out / B / C and L >= 64");
   }
-  if ((rc = ss_launch_fwd(a, p->u.dtype, stream))) return rc;
-  return finish_launch("selective_scan_fwd");
+  return (rc = ss_fwd_launch(pl, a, p->u.dtype, stream)) ? rc : finish_launch("selective_scan_fwd");
 }
 
 extern "C" int omk_selective_scan_fwd_form(const OmkSelScanFwd* p) {
@@ -1606,49 +1627,74 @@ extern "C" int omk_selective_scan_fwd_form(const OmkSelScanFwd* p) {
   SsArgs a = {};
   int rc = ss_fill(a, p->u, p->delta, p->A, p->Bm, p->Cm, p->D, p->z, p->delta_bias, p->delta_softplus, "selective_scan_fwd_form");
   if (rc) return rc;
-  a.out = p->out.data; a.osb = p->out.stride[0]; a.osd = p->out.stride[1]; a.osl = p->out.stride[2];
-  if (present(p->pass_states)) { a.ckpt = (float*)p->pass_states.data; a.TLB = SSR_TP; }
-  if (ss_lanes_form(a, p->u.dtype)) return 2;
-  const bool lcontig = a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && a.osl == 1 && (!a.Bvar || a.Bsl == 1) && (!a.Cvar || a.Csl == 1) &&
-                       a.L >= 64;
-  return lcontig ? 1 : 0;
+  ss_fwd_outputs(a, p);
+  return ss_fwd_plan(a, p->u.dtype, SS_SCAN).form;
 }
 
-// channel-last views of everything, input-dependent B / C of u's dtype, d_state <= 16, and as many waves as the forward's lanes form asks
-// for: fills the buffer ranges of both kernels.  q.f and the gradient strides must be filled.
-static bool ss_bwd_lanes_applies(SsBwdArgs& q, const OmkSelScanBwd* p, int udt) {
-  SsArgs& a = q.f;
-  if ((present(p->pass_states) && !ss_tile_states(p->pass_states, a.B, a.Dm, a.L, a.N)) || !a.Bvar || !a.Cvar || a.N > 16 || a.bdt != udt || a.cdt != udt) return false;
-  const bool z = a.z != nullptr;
-  if (!(a.usd == 1 && a.dsd == 1 && (!z || (a.zsd == 1 && q.dzsd == 1)) && q.gsd == 1 && q.dusd == 1 && q.ddsd == 1)) return false;
-  if (a.Dm == 1) return false;   // (a single channel is both layouts: the chunked form takes it)
-  SsArgs probe = a;              // the forward's criteria (spans, number of waves, OMK_SELSCAN_LANES) on an output laid out like u
-  probe.out = const_cast<void*>(a.u); probe.osb = a.usb; probe.osd = a.usd; probe.osl = a.usl; probe.ckpt = nullptr;
-  if (ss_lanes_form(probe, udt) != 2) return false;
-  a.xu = probe.xu; a.xd = probe.xd; a.xz = probe.xz; a.xB = probe.xB; a.xC = probe.xC; a.xo = 0u;
-  const int64_t es = (int64_t)dtype_size(udt), lim = (int64_t)1 << 31;
-  auto ext = [&](int64_t sd, int64_t sl) -> int64_t { return (sd < 0 || sl < 0) ? lim : es * (((int64_t)a.Dm - 1) * sd + ((int64_t)a.L - 1) * sl + 1); };
-  const int64_t eg = ext(q.gsd, q.gsl), eu = ext(q.dusd, q.dusl), ed = ext(q.ddsd, q.ddsl), ez = z ? ext(q.dzsd, q.dzsl) : 0;
-  if (eg >= lim || eu >= lim || ed >= lim || ez >= lim) return false;
-  q.xg = (uint32_t)eg; q.xdu = (uint32_t)eu; q.xdd = (uint32_t)ed; q.xdz = (uint32_t)ez;
-  return true;
+struct SsBwdPlan {
+  int form;                     // 0 per-channel, 1 chunked, 2 lanes = channels (what omk_selective_scan_bwd_form answers)
+  bool refused;                 // the per-channel kernel holds d_state <= SSB_N
+  bool first_pass; SsFwdPlan fwd;   // nobody handed the states in: `fwd` runs first and leaves them
+  int NW, NB, nOct;             // chunked: waves per workgroup, state indices per LDS block, channel tiles per workgroup
+  dim3 grid, block; size_t smem;
+  uint32_t xg, xdu, xdd, xdz;   // lanes: the buffer ranges (SsBwdArgs)
+};
+
+// q.f and the strides of dout / du / ddelta / dz must be filled; `states` is OmkSelScanBwd::pass_states
+static SsBwdPlan ss_bwd_plan(const SsBwdArgs& q, int udt, const OmkTensor& states) {
+  const SsArgs& a = q.f;
+  SsBwdPlan pl = {};
+  const int dpg = a.Dm / a.G;
+  const int64_t es = (int64_t)dtype_size(udt);
+  // ---- channel-last views of everything and what the forward's lanes form asks for: the lanes = channels reverse sweep
+  // (selscan_bwd_lanes_kernel).  (A single channel is both layouts: the chunked form takes it)
+  if (((pl.first_pass = !present(states)) || ss_tile_states(states, a.B, a.Dm, a.L, a.N)) && a.Dm > 1 && ss_bwd_unit_stride(q, false)) {
+    pl.fwd = ss_fwd_plan(a, udt, SS_TILE_STATES);
+    const int64_t eg = ss_ext(es, q.gsd, q.gsl, a.Dm, a.L), eu = ss_ext(es, q.dusd, q.dusl, a.Dm, a.L), ed = ss_ext(es, q.ddsd, q.ddsl, a.Dm, a.L),
+                  ez = a.z ? ss_ext(es, q.dzsd, q.dzsl, a.Dm, a.L) : 0;
+    if (pl.fwd.form == 2 && !pl.fwd.lcontig && eg < SS_LIM && eu < SS_LIM && ed < SS_LIM && ez < SS_LIM) {
+      pl.form = 2; pl.grid = pl.fwd.grid; pl.block = dim3(64);
+      pl.xg = (uint32_t)eg; pl.xdu = (uint32_t)eu; pl.xdd = (uint32_t)ed; pl.xdz = (uint32_t)ez;
+      return pl;
+    }
+  }
+  // ---- L-contiguous storage, input-dependent B and C of u's dtype, 8 | channels per group: the chunked associative scan in both directions
+  if (ss_group_rows(a, udt) && ss_bwd_unit_stride(q, true) && ss_bc_along_l(a) && a.L >= 64) {
+    pl.form = 1; pl.fwd = ss_fwd_plan(a, udt, SS_PASS_STATES);
+    pl.NW = dpg % 16 == 0 ? 16 : 8; pl.NB = a.N < 16 ? a.N : 16; pl.nOct = 1;
+    if (a.N <= pl.NB)
+      for (int o = 4; o > 1; o >>= 1)
+        if (dpg % (pl.NW * o) == 0 && (int64_t)a.B * a.Dm / (pl.NW * o) >= 512) { pl.nOct = o; break; }
+    // test hook OMK_SELSCAN_BWD_OCT = 1 / 2 / 4: that many channel tiles per workgroup at any number of workgroups
+    const int oct = test_hook("OMK_SELSCAN_BWD_OCT", 0);
+    if ((oct == 1 || oct == 2 || oct == 4) && a.N <= pl.NB && dpg % (pl.NW * oct) == 0) pl.nOct = oct;
+    pl.smem = (size_t)pl.NB * SSR_TP * (8 + 2 * es) + (size_t)(3 * pl.nOct * pl.NW * (pl.nOct > 1 ? 16 : 64) + pl.NW * 64) * 4;
+    pl.grid = dim3((unsigned)((int64_t)a.B * a.Dm / (pl.NW * pl.nOct))); pl.block = dim3(pl.NW * 64);
+    return pl;
+  }
+  // ---- anything else: the per-channel adjoint sweep, tiles last to first, behind a forward pass that leaves the state at every tile boundary
+  pl.refused = a.N > SSB_N; pl.first_pass = true; pl.fwd = ss_fwd_plan(a, udt, SS_CHECKPOINTS);
+  pl.grid = dim3((unsigned)((int64_t)a.B * a.G * ((dpg + SSB_DT - 1) / SSB_DT))); pl.block = dim3(SSB_DT);
+  pl.smem = (size_t)SSB_TL * SSB_N * SSB_DT * 4 + (size_t)4 * SSB_TL * SSB_N * 4 + (size_t)7 * SSB_TL * SSB_DT * es;
+  return pl;
 }
 
-// 2: omk_selective_scan_bwd would run the lanes = channels reverse sweep on these (channel-last) views as they lie; 0 / 1: it wants the
-// L-contiguous rows of the chunked form (1) or falls to the per-channel kernel (0) -- the host mirror decides about copies with it
+// dout / du / ddelta / dz into the arguments
+static void ss_bwd_views(SsBwdArgs& q, const OmkSelScanBwd* p) {
+  q.dout = p->dout.data; q.gsb = p->dout.stride[0]; q.gsd = p->dout.stride[1]; q.gsl = p->dout.stride[2];
+  q.du = p->du.data; q.dusb = p->du.stride[0]; q.dusd = p->du.stride[1]; q.dusl = p->du.stride[2];
+  q.ddelta = p->ddelta.data; q.ddsb = p->ddelta.stride[0]; q.ddsd = p->ddelta.stride[1]; q.ddsl = p->ddelta.stride[2];
+  if (present(p->dz)) { q.dz = p->dz.data; q.dzsb = p->dz.stride[0]; q.dzsd = p->dz.stride[1]; q.dzsl = p->dz.stride[2]; }
+}
+
 extern "C" int omk_selective_scan_bwd_form(const OmkSelScanBwd* p) {
   if (!p || !present(p->dout) || !present(p->du) || !present(p->ddelta)) return fail(OMK_EINVAL, "selective_scan_bwd_form: dout, du, ddelta required");
   SsBwdArgs q = {};
   int rc = ss_fill(q.f, p->u, p->delta, p->A, p->Bm, p->Cm, p->D, p->z, p->delta_bias, p->delta_softplus, "selective_scan_bwd_form");
   if (rc) return rc;
   if (p->dout.ndim != 3 || p->du.ndim != 3 || p->ddelta.ndim != 3) return 0;
-  q.gsd = p->dout.stride[1]; q.gsl = p->dout.stride[2]; q.dusd = p->du.stride[1]; q.dusl = p->du.stride[2];
-  q.ddsd = p->ddelta.stride[1]; q.ddsl = p->ddelta.stride[2];
-  if (present(p->dz)) { q.dzsd = p->dz.stride[1]; q.dzsl = p->dz.stride[2]; }
-  if (ss_bwd_lanes_applies(q, p, p->u.dtype)) return 2;
-  const SsArgs& a = q.f;
-  const bool lc = a.Bvar && a.Cvar && a.usl == 1 && a.dsl == 1 && (!a.z || a.zsl == 1) && q.gsl == 1 && a.Bsl == 1 && a.Csl == 1 && a.L >= 64;
-  return lc ? 1 : 0;
+  ss_bwd_views(q, p);
+  return ss_bwd_plan(q, p->u.dtype, p->pass_states).form;
 }
 
 extern "C" size_t omk_selective_scan_bwd_workspace_bytes(const OmkSelScanBwd* p) {
@@ -1658,6 +1704,7 @@ extern "C" size_t omk_selective_scan_bwd_workspace_bytes(const OmkSelScanBwd* p)
 }
 
 extern "C" int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream) {
+  kernels_reset();
   OMK_REQUIRE(p && present(p->dout) && present(p->du) && present(p->ddelta) && present(p->dA) && present(p->dB) && present(p->dC),
               "selective_scan_bwd: dout, du, ddelta, dA, dB, dC required");
   SsBwdArgs q = {};
@@ -1676,81 +1723,33 @@ extern "C" int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream)
   OMK_REQUIRE(!present(p->z) || present(p->dz), "selective_scan_bwd: dz required when z is given");
   OMK_REQUIRE(p->workspace && p->workspace_bytes >= omk_selective_scan_bwd_workspace_bytes(p), "selective_scan_bwd: workspace too small");
   if ((int64_t)a.B * a.Dm * a.L == 0) return OMK_OK;
-  q.dout = p->dout.data; q.gsb = p->dout.stride[0]; q.gsd = p->dout.stride[1]; q.gsl = p->dout.stride[2];
-  q.du = p->du.data; q.dusb = p->du.stride[0]; q.dusd = p->du.stride[1]; q.dusl = p->du.stride[2];
-  q.ddelta = p->ddelta.data; q.ddsb = p->ddelta.stride[0]; q.ddsd = p->ddelta.stride[1]; q.ddsl = p->ddelta.stride[2];
-  if (present(p->dz)) { q.dz = p->dz.data; q.dzsb = p->dz.stride[0]; q.dzsd = p->dz.stride[1]; q.dzsl = p->dz.stride[2]; }
+  ss_bwd_views(q, p);
   q.dA = (float*)p->dA.data; q.dB = (float*)p->dB.data; q.dC = (float*)p->dC.data; q.dD = (float*)p->dD.data; q.ddb = (float*)p->ddelta_bias.data;
   if (a.Bvar) { q.dBsb = p->dB.stride[0]; q.dBsg = p->dB.stride[1]; q.dBsn = p->dB.stride[2]; q.dBsl = p->dB.stride[3]; }
   else { q.dBsg = p->dB.stride[0]; q.dBsn = p->dB.stride[1]; }
   if (a.Cvar) { q.dCsb = p->dC.stride[0]; q.dCsg = p->dC.stride[1]; q.dCsn = p->dC.stride[2]; q.dCsl = p->dC.stride[3]; }
   else { q.dCsg = p->dC.stride[0]; q.dCsn = p->dC.stride[1]; }
-  const int dpg = a.Dm / a.G;
-  // ---- channel-last storage with enough sequences to fill the chip: the lanes = channels reverse sweep (selscan_bwd_lanes_kernel)
-  if (ss_bwd_lanes_applies(q, p, udt)) {
-    a.ckpt = (float*)p->workspace; a.TLB = SBL_T; a.nTB = (a.L + SBL_T - 1) / SBL_T; a.ckpt_cl = 1;
-    dim3 grid((unsigned)((int64_t)a.B * a.G * ((dpg + 63) / 64))), block(64);
-    if (present(p->pass_states)) a.ckpt = (float*)p->pass_states.data;   // (the training forward left them: no pass 1)
-    else {   // pass 1: the forward sweep once more, no output, the state in front of every 16-token tile as (B, tile, n, D)
-      SsArgs f = a;
-      f.out = nullptr; f.xo = 0u; f.last = nullptr; f.z = nullptr; f.xz = 0u; f.D = nullptr;
-      OMK_DISPATCH_DTYPE(udt, T, OMK_LAUNCH((selscan_fwd_lanes_kernel<T, false>), grid, block, 0, stream, f));
-    }
-    OMK_DISPATCH_DTYPE(udt, T, OMK_LAUNCH((selscan_bwd_lanes_kernel<T>), grid, block, 0, stream, q));
-    return finish_launch("selective_scan_bwd");
-  }
-  // ---- L-contiguous storage, input-dependent B and C of u's dtype: the chunked associative scan in both directions
-  const bool chunked = a.Bvar && a.Cvar && a.usl == 1 && a.dsl == 1 && (!a.z || (a.zsl == 1 && q.dzsl == 1)) && q.gsl == 1 && q.dusl == 1 &&
-                       q.ddsl == 1 && a.Bsl == 1 && a.Csl == 1 && a.bdt == udt && a.cdt == udt && a.adt == OMK_F32 && dpg % 8 == 0 &&
-                       a.L >= 64;
-  OMK_REQUIRE(!present(p->pass_states) || chunked, "selective_scan_bwd: pass_states belong to the chunked form (L-contiguous rows, variable B / C, L >= 64) or, as tile states, to the lanes = channels form");
-  if (chunked) {
-    a.TLB = SSR_TP; a.nTB = (a.L + SSR_TP - 1) / SSR_TP;
-    if (present(p->pass_states)) {
-      OMK_REQUIRE(p->pass_states.dtype == OMK_F32 && is_dense(p->pass_states) && numel(p->pass_states) == (int64_t)a.B * a.Dm * a.nTB * a.N,
-                  "selective_scan_bwd: pass_states must be contiguous f32 (B, D, ceil(L / 512), N)");
-      a.ckpt = (float*)p->pass_states.data;
-    } else {
-      a.ckpt = (float*)p->workspace;
-      SsArgs f = a;
-      f.out = nullptr; f.last = nullptr; f.z = nullptr; f.D = nullptr;
-      if ((rc = ss_launch_fwd(f, udt, stream, true))) return rc;
-    }
-    const int NW = dpg % 16 == 0 ? 16 : 8;
-    const size_t es = dtype_size(udt);
-    q.NB = a.N < 16 ? a.N : 16;
-    q.nOct = 1;
-    if (a.N <= q.NB)
-      for (int o = 4; o > 1; o >>= 1)
-        if (dpg % (NW * o) == 0 && (int64_t)a.B * a.Dm / (NW * o) >= 512) { q.nOct = o; break; }
-    // test hook OMK_SELSCAN_BWD_OCT = 1 / 2 / 4: that many channel tiles per workgroup at any number of workgroups
-    const int oct = test_hook("OMK_SELSCAN_BWD_OCT", 0);
-    if ((oct == 1 || oct == 2 || oct == 4) && a.N <= q.NB && dpg % (NW * oct) == 0) q.nOct = oct;
-    const size_t smem = (size_t)q.NB * SSR_TP * (8 + 2 * es) + (size_t)(3 * q.nOct * NW * (q.nOct > 1 ? 16 : 64) + NW * 64) * 4;
-    dim3 grid((unsigned)((int64_t)a.B * a.Dm / (NW * q.nOct))), block(NW * 64);
-#define SSR_GO(T) do { if (OMK_SET_MAX_DYN_SMEM((selscan_bwd_chunked_kernel<T>), smem)) return fail(OMK_ELAUNCH, "selective_scan_bwd: cannot raise dynamic LDS to %zu", smem); \
-      OMK_LAUNCH((selscan_bwd_chunked_kernel<T>), grid, block, smem, stream, q); } while (0)
-    OMK_DISPATCH_DTYPE(udt, T, SSR_GO(T));
-#undef SSR_GO
-    return finish_launch("selective_scan_bwd");
-  }
-  if (a.N > SSB_N) return fail(OMK_EUNSUPPORTED, "selective_scan_bwd: d_state %d > %d needs L-contiguous u / delta / z / dout / B / C (upstream's layout), L >= 64 "
-                                                 "and 8 | channels per group", a.N, SSB_N);
-  // pass 1: the forward recurrence once more, leaving the state at every SSB_TL-token boundary in the workspace
-  a.ckpt = (float*)p->workspace; a.TLB = SSB_TL; a.nTB = (a.L + SSB_TL - 1) / SSB_TL;
-  {
+  const OmkTensor& ps = p->pass_states;
+  const SsBwdPlan pl = ss_bwd_plan(q, udt, ps);
+  OMK_REQUIRE(!present(ps) || pl.form != 0, "selective_scan_bwd: pass_states belong to the chunked form (L-contiguous rows, variable B / C, L >= 64) or, as tile states, to the lanes = channels form");
+  // the state in front of every 512-token pass (chunked) or 16-token tile (lanes: channels innermost; per-channel): the caller's, or pass 1 leaves it in the workspace
+  a.TLB = pl.form == 1 ? SSR_TP : SSB_TL; a.nTB = (a.L + a.TLB - 1) / a.TLB; a.ckpt_cl = pl.form == 2;
+  OMK_REQUIRE(pl.form != 1 || !present(ps) || (ps.dtype == OMK_F32 && is_dense(ps) && numel(ps) == (int64_t)a.B * a.Dm * a.nTB * a.N),
+              "selective_scan_bwd: pass_states must be contiguous f32 (B, D, ceil(L / 512), N)");
+  if (pl.refused) return fail(OMK_EUNSUPPORTED, "selective_scan_bwd: d_state %d > %d needs L-contiguous u / delta / z / dout / B / C (upstream's layout), L >= 64 "
+                                                "and 8 | channels per group", a.N, SSB_N);
+  a.ckpt = present(ps) ? (float*)ps.data : (float*)p->workspace;
+  a.xu = pl.fwd.xu; a.xd = pl.fwd.xd; a.xz = pl.fwd.xz; a.xB = pl.fwd.xB; a.xC = pl.fwd.xC; q.xg = pl.xg; q.xdu = pl.xdu; q.xdd = pl.xdd; q.xdz = pl.xdz;   // (buffer ranges: the lanes form, zero otherwise)
+  a.DT = SSB_DT; q.NB = pl.NB; q.nOct = pl.nOct;
+  if (pl.first_pass) {   // the forward once more: no output, only the states
     SsArgs f = a;
-    f.out = nullptr; f.last = nullptr; f.z = nullptr;
-    if ((rc = ss_launch_fwd(f, udt, stream))) return rc;
+    f.out = nullptr; f.last = nullptr; f.z = nullptr; f.D = nullptr;
+    if ((rc = ss_fwd_launch(pl.fwd, f, udt, stream))) return rc;
   }
-  // pass 2: adjoint sweep, tiles last to first
-  a.DT = SSB_DT;
-  const int tiles_per_group = (dpg + SSB_DT - 1) / SSB_DT;
-  dim3 grid((unsigned)((int64_t)a.B * a.G * tiles_per_group)), block(SSB_DT);
-  const size_t smem = (size_t)SSB_TL * SSB_N * SSB_DT * 4 + (size_t)4 * SSB_TL * SSB_N * 4 + (size_t)7 * SSB_TL * SSB_DT * dtype_size(udt);
-#define SSB_GO(T) do { if (OMK_SET_MAX_DYN_SMEM((selscan_bwd_kernel<T>), smem)) return fail(OMK_ELAUNCH, "selective_scan_bwd: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((selscan_bwd_kernel<T>), grid, block, smem, stream, q); } while (0)
-  OMK_DISPATCH_DTYPE(udt, T, SSB_GO(T));
-#undef SSB_GO
-  return finish_launch("selective_scan_bwd");
+  const KernelId id = pl.form == 2 ? kernel_id("selscan_bwd_lanes") : pl.form == 0 ? kernel_id("selscan_bwd") : kernel_id("selscan_bwd_chunked<nw=%d,nb=%d,noct=%d>", pl.NW, pl.NB, pl.nOct);
+  auto go = [&](auto kern) { rc = omk_launch(id, kern, pl.grid, pl.block, pl.smem, stream, q); };
+  if (pl.form == 2) OMK_DISPATCH_DTYPE(udt, T, go(selscan_bwd_lanes_kernel<T>));
+  else if (pl.form == 1) OMK_DISPATCH_DTYPE(udt, T, go(selscan_bwd_chunked_kernel<T>));
+  else OMK_DISPATCH_DTYPE(udt, T, go(selscan_bwd_kernel<T>));
+  return rc ? rc : finish_launch("selective_scan_bwd");
 }

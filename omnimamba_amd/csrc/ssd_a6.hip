@@ -568,8 +568,8 @@ constexpr int a6_key(int mode, bool ex, bool dfold, bool dump, bool khilo) { ret
 // One head pair (x one segment) per workgroup.
 int ssd_a6_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
   dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
-  if (pl.variant == CA_STATE_ONLY) return ssd_launch(kernel_id("ssd_a6<state_only>"), ssd_a6_kernel<GS_Y, false, true, false, true, true>, grid, block, sizeof(SmemA6), stream, a);
-  if (pl.variant == CA_STATE_DUMP) return ssd_launch(kernel_id("ssd_a6<state_dump>"), ssd_a6_kernel<GS_Y, false, true, true, false, true>, grid, block, sizeof(SmemA6), stream, a);
+  if (pl.variant == CA_STATE_ONLY) return omk_launch(kernel_id("ssd_a6<state_only>"), ssd_a6_kernel<GS_Y, false, true, false, true, true>, grid, block, sizeof(SmemA6), stream, a);
+  if (pl.variant == CA_STATE_DUMP) return omk_launch(kernel_id("ssd_a6<state_dump>"), ssd_a6_kernel<GS_Y, false, true, true, false, true>, grid, block, sizeof(SmemA6), stream, a);
   void (*k)(GScan) = nullptr;
   switch (a6_key(a.mode, pl.extras, pl.dfold, pl.dump, pl.khilo)) {
     case a6_key(GS_Y, 0, 0, 0, 0): k = ssd_a6_kernel<GS_Y, false, false, false, false>; break;
@@ -590,7 +590,7 @@ int ssd_a6_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
     case a6_key(GS_DX, 0, 1, 1, 0): k = ssd_a6_kernel<GS_DX, false, true, true, false>; break;
     default: return fail(OMK_EINVAL, "ssd_a6: no instantiation for this plan");
   }
-  return ssd_launch(kernel_id("ssd_a6<mode=%d,ex=%d,dfold=%d,dump=%d,khilo=%d>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.dump, (int)pl.khilo), k, grid, block,
+  return omk_launch(kernel_id("ssd_a6<mode=%d,ex=%d,dfold=%d,dump=%d,khilo=%d>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.dump, (int)pl.khilo), k, grid, block,
                     sizeof(SmemA6), stream, a);
 }
 

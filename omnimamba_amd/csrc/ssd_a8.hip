@@ -795,7 +795,7 @@ int ssd_a8_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
   }
   const KernelId id = pl.conv ? kernel_id("ssd_a8<mode=0,dump=0,khilo=%d,precise=0,conv=1>", (int)pl.khilo)
                               : kernel_id("ssd_a8<mode=%d,dump=%d,khilo=%d,precise=%d>", a.mode, (int)pl.dump, (int)pl.khilo, (int)pl.precise);
-  return ssd_launch(id, k, grid, block, sizeof(SmemA8), stream, a);
+  return omk_launch(id, k, grid, block, sizeof(SmemA8), stream, a);
 }
 
 }  // namespace omk

@@ -934,7 +934,7 @@ __global__ void ssd_reduce_partials_kernel(const uint16_t* part, void* out, int6
 int ssd_reduce_partials(const float* part, void* out, int64_t osb, int64_t osl, int64_t osg, int out_dt, int B, int L, int G, int H, omk_stream stream) {
   const int64_t total = (int64_t)B * L * G * 16;
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  return ssd_launch(kernel_id("ssd_reduce_partials"), ssd_reduce_partials_kernel, grid, block, 0, stream, (const uint16_t*)part, out, osb, osl, osg, out_dt, B, L, G, H / 2);
+  return omk_launch(kernel_id("ssd_reduce_partials"), ssd_reduce_partials_kernel, grid, block, 0, stream, (const uint16_t*)part, out, osb, osl, osg, out_dt, B, L, G, H / 2);
 }
 
 static_assert(QC == SEG_CHUNK, "segments are planned in chunks of SEG_CHUNK tokens");
@@ -976,11 +976,11 @@ int ssd_mfma_prepare_segments(const GScan& g, omk_stream stream, int* seg_fmt) {
   // final state (prefill -> decode hand-off, context-parallel shards) the segment states carry the hi + lo operand like the scan proper
   // does then: a kept final state of a SPLIT sequence (B = 1 prefill) is exact to fp32 accumulation too, not 1e-3 off.
   const bool khilo = g.mode == GS_Y && ((g.flags & (GSF_KHILO | GSF_PRECISE)) || g.fin != nullptr);
-  const int rc = ssd_launch(kernel_id("ssd_mfma_a3<segment state pass,khilo=%d>", (int)khilo),
+  const int rc = omk_launch(kernel_id("ssd_mfma_a3<segment state pass,khilo=%d>", (int)khilo),
                             khilo ? ssd_mfma_a3_kernel<GS_Y, false, true, false, true> : ssd_mfma_a3_kernel<GS_Y, false, true, false>, sgrid, block, sizeof(SmemA3), stream, a);
   if (rc) return rc;
   dim3 fgrid((unsigned)((int64_t)a.B * a.H * (SEG_STATE / 256)));
-  return ssd_launch(kernel_id("ssd_seg_fold"), ssd_seg_fold_kernel, fgrid, block, 0, stream, a);
+  return omk_launch(kernel_id("ssd_seg_fold"), ssd_seg_fold_kernel, fgrid, block, 0, stream, a);
 }
 
 bool ssd_class_b_applies(const GScan& g) {
@@ -997,7 +997,7 @@ static int ssd_mfma_launch_b(const GScan& g, omk_stream stream) {
   dim3 grid((unsigned)(a.B * (a.H / 2) * a.nseg)), block(512);
   const int dmode = (a.mode == GS_DC || !a.dD) ? 0 : a.dDsp == 0 ? 1 : 2;
   void (*k)(GScan) = a.mode == GS_DC ? ssd_mfma_b3_kernel<GS_DC, 0> : dmode == 0 ? ssd_mfma_b3_kernel<GS_DB, 0> : dmode == 1 ? ssd_mfma_b3_kernel<GS_DB, 1> : ssd_mfma_b3_kernel<GS_DB, 2>;
-  return ssd_launch(kernel_id("ssd_mfma_b3<mode=%d,dmode=%d>", a.mode, dmode), k, grid, block, sizeof(SmemB3), stream, a);
+  return omk_launch(kernel_id("ssd_mfma_b3<mode=%d,dmode=%d>", a.mode, dmode), k, grid, block, sizeof(SmemB3), stream, a);
 }
 
 // The ONE place that decides which class A kernel takes a descriptor.  Everything here is a property of the descriptor: nothing is
@@ -1058,7 +1058,7 @@ constexpr int a3_key(int mode, bool ex, bool dfold, bool khilo, bool dump) { ret
 static int ssd_a3_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream) {
   dim3 grid((unsigned)(a.B * a.H * a.nseg)), block(256);
   if (pl.variant != CA_SCAN)
-    return ssd_launch(kernel_id(pl.variant == CA_STATE_ONLY ? "ssd_mfma_a3<state_only>" : "ssd_mfma_a3<state_dump>"), ssd_mfma_a3_kernel<GS_Y, false, true, false>,
+    return omk_launch(kernel_id(pl.variant == CA_STATE_ONLY ? "ssd_mfma_a3<state_only>" : "ssd_mfma_a3<state_dump>"), ssd_mfma_a3_kernel<GS_Y, false, true, false>,
                       grid, block, sizeof(SmemA3), stream, a);
   void (*k)(GScan) = nullptr;
   switch (a3_key(a.mode, pl.extras, pl.dfold, pl.khilo, pl.dump)) {
@@ -1077,7 +1077,7 @@ static int ssd_a3_launch(const ClassAPlan& pl, const GScan& a, omk_stream stream
   }
   const KernelId id = pl.dump ? kernel_id("ssd_mfma_a3<mode=%d,ex=%d,state=0,dfold=%d,khilo=%d,dump=1>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.khilo)
                               : kernel_id("ssd_mfma_a3<mode=%d,ex=%d,state=0,dfold=%d,khilo=%d>", a.mode, (int)pl.extras, (int)pl.dfold, (int)pl.khilo);
-  return ssd_launch(id, k, grid, block, sizeof(SmemA3), stream, a);
+  return omk_launch(id, k, grid, block, sizeof(SmemA3), stream, a);
 }
 
 int ssd_class_a_launch(const ClassAPlan& pl, const GScan& g, omk_stream stream) {

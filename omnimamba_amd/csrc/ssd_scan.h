@@ -18,7 +18,7 @@
 //     ssd_mfma.hip  ssd_mfma_a3  row strips; one head per workgroup (odd head counts, one head per group)
 //   class B (dC, dB: bf16, state 128 x 64): ssd_mfma.hip ssd_mfma_b3 (ssd_class_b_applies)
 //   ssd_cp.hip    ssd_cp         chunk-parallel dB / dC from dumped window states
-// Every launch of a class A / B kernel goes through ssd_launch(), which records its id for omk_ssd_last_kernels().
+// Every launch of a class A / B kernel goes through omk_launch() (omk_common.h), which records its id for omk_ssd_last_kernels().
 #pragma once
 #include <cstdlib>
 #include "omk_common.h"
@@ -148,24 +148,6 @@ int ssd_mfma_launch(const GScan& g, omk_stream stream);
 // state at the START of segment j (initial state included).  Shared by the scans whose state this is (y and dC; dx and dB).
 int ssd_mfma_prepare_segments(const GScan& g, omk_stream stream, int* seg_fmt = nullptr);   // *seg_fmt: the order it left the states in
 
-// ---- the one way a class A / B kernel is launched: its id goes to omk_ssd_last_kernels(), the dynamic LDS limit is raised, then the launch
-struct KernelId { char s[96]; };
-inline KernelId kernel_id(const char* fmt, ...) {
-  KernelId k;
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(k.s, sizeof(k.s), fmt, ap);
-  va_end(ap);
-  return k;
-}
-template <class T> struct arg_of { typedef T type; };   // (keeps the kernel's own parameter types: arguments convert, they are not deduced)
-template <class... P>
-int ssd_launch(const KernelId& id, void (*kern)(P...), dim3 grid, dim3 block, size_t smem, omk_stream stream, typename arg_of<P>::type... args) {
-  kernels_note("%s", id.s);
-  if (smem && OMK_SET_MAX_DYN_SMEM(kern, smem)) return fail(OMK_ELAUNCH, "%s: cannot raise dynamic LDS to %zu", id.s, smem);
-  OMK_LAUNCH(kern, grid, block, smem, stream, args...);
-  return OMK_OK;
-}
 // chunk-parallel dB / dC / token scalars from the dumped states (ssd_cp.hip)
 struct CpArgs {
   const uint16_t *X, *DY; int64_t xsb, xsl, xsh, ysb, ysl, ysh;   // (B, L, H, 64) bf16

@@ -15,6 +15,12 @@ from . import _capi as K
 from ._lib import get_lib, require_device
 
 
+def _rows_along_l(rows, bc):
+    """L-contiguous (B, D, L) rows (None passes) and input-dependent (B, G, N, L) B / C, copied where they are not: the chunked scan has lanes = time."""
+    return ([t if t is None or t.stride(-1) == 1 else t.contiguous() for t in rows],
+            [t if t.dim() != 4 or t.stride(-1) == 1 else t.contiguous() for t in bc])
+
+
 class SelectiveScanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
@@ -42,12 +48,8 @@ class SelectiveScanFn(torch.autograd.Function):
                 out = o
         took_lanes = out is not None
         if out is None and L >= 64:
-            # the chunked associative scan wants L-contiguous rows (lanes = time): one copy pass here costs far less than the per-channel
-            # sequential kernel
-            u, delta = (t if t.stride(-1) == 1 else t.contiguous() for t in (u, delta))
-            z = z if z is None or z.stride(-1) == 1 else z.contiguous()
-            B4 = B4 if B4.dim() != 4 or B4.stride(-1) == 1 else B4.contiguous()
-            C4 = C4 if C4.dim() != 4 or C4.stride(-1) == 1 else C4.contiguous()
+            # the chunked associative scan wants L-contiguous rows: one copy pass here costs far less than the per-channel sequential kernel
+            (u, delta, z), (B4, C4) = _rows_along_l((u, delta, z), (B4, C4))
         if out is None:
             out = torch.empty_like(u)
         last = torch.empty(Bsz, Dm, A.shape[1], dtype=torch.float32, device=u.device) if return_last_state else None
@@ -63,7 +65,8 @@ class SelectiveScanFn(torch.autograd.Function):
         if (ps is None and not lanes_fwd and L >= 64 and any(ctx.needs_input_grad) and B4.dim() == 4 and C4.dim() == 4 and B4.dtype == u.dtype and C4.dtype == u.dtype and
                 (Dm // B4.shape[1]) % 8 == 0 and (out.stride(1) == 1 or all(t is None or t.stride(-1) == 1 for t in (u, delta, z, B4, C4))) and
                 not os.environ.get("OMK_SELSCAN_NO_PASS_STATES")):
-            # = the conditions of the chunked backward (selscan.hip); without the tensor the backward runs a state-only forward pass first
+            # = the conditions of the chunked backward (ss_bwd_plan, selscan.hip); without the tensor the backward runs a state-only forward
+            # pass first
             ps = torch.empty(Bsz, Dm, (L + 511) // 512, A.shape[1], dtype=torch.float32, device=u.device)
         if u.numel() > 0:
             p = K.SelScanFwd(u=K.T(u), delta=K.T(delta), A=K.T(Af), Bm=K.T(B4),
@@ -84,7 +87,7 @@ class SelectiveScanFn(torch.autograd.Function):
         directions (any d_state <= 64); other layouts the per-channel sequential kernel (d_state <= 16)."""
         lib = get_lib()
         u, delta, A, B4, C4, D, z, delta_bias, ps = ctx.saved_tensors
-        dout = dout.to(u.dtype)
+        dout, Af = dout.to(u.dtype), A.float() if A.dtype != torch.float32 else A
         lanes = False
         tile_ps = ps is not None and ps.shape[-1] == u.shape[1] and ps.shape[1] == (u.shape[2] + 15) // 16
         if u.stride(1) == 1 and u.shape[1] > 1 and u.numel() > 0 and (ps is None or tile_ps):
@@ -96,7 +99,7 @@ class SelectiveScanFn(torch.autograd.Function):
             du_c = torch.empty(Bsz, L, Dm, dtype=u.dtype, device=u.device).transpose(1, 2)
             dd_c = torch.empty(Bsz, L, Dm, dtype=u.dtype, device=u.device).transpose(1, 2)
             dz_c = None if z is None else torch.empty(Bsz, L, Dm, dtype=u.dtype, device=u.device).transpose(1, 2)
-            probe = K.SelScanBwd(u=K.T(u), delta=K.T(delta_c), A=K.T(A.float() if A.dtype != torch.float32 else A), Bm=K.T(B4), Cm=K.T(C4),
+            probe = K.SelScanBwd(u=K.T(u), delta=K.T(delta_c), A=K.T(Af), Bm=K.T(B4), Cm=K.T(C4),
                                  D=K.T(D), z=K.T(z_c), delta_bias=K.T(delta_bias), dout=K.T(dout_c), du=K.T(du_c), ddelta=K.T(dd_c),
                                  dA=K.T(None), dB=K.T(None), dC=K.T(None), dD=K.T(None), dz=K.T(dz_c), ddelta_bias=K.T(None),
                                  pass_states=K.T(ps), delta_softplus=int(ctx.delta_softplus))
@@ -106,11 +109,7 @@ class SelectiveScanFn(torch.autograd.Function):
             ps = None          # (tile states are of no use to the other forms)
         if not lanes and u.shape[-1] >= 64:
             # (the forward may have read channel-last views as they lay: the chunked backward wants rows along L)
-            u, delta, dout = (t if t.stride(-1) == 1 else t.contiguous() for t in (u, delta, dout))
-            z = z if z is None or z.stride(-1) == 1 else z.contiguous()
-            B4 = B4 if B4.dim() != 4 or B4.stride(-1) == 1 else B4.contiguous()
-            C4 = C4 if C4.dim() != 4 or C4.stride(-1) == 1 else C4.contiguous()
-        Af = A.float() if A.dtype != torch.float32 else A
+            (u, delta, dout, z), (B4, C4) = _rows_along_l((u, delta, dout, z), (B4, C4))
         if lanes:
             du, ddelta, dz = du_c, dd_c, dz_c
         else:
