@@ -24,11 +24,13 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 10
+#define OMK_ABI_VERSION 11
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
-typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices; ABI 10: per-row lengths */ } omk_dtype;
+typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices; ABI 10: per-row lengths */,
+               OMK_F8E4M3 = 5 /* ABI 11: OCP e4m3fn (bias 7, max 448, 0x7F / 0xFF NaN, no infinities; NOT the fnuz form) -- the weight of
+                                 omk_norm_linear only, together with OmkNormLinear.weight_scale */ } omk_dtype;
 typedef void* omk_stream; /* hipStream_t */
 
 typedef struct {
@@ -265,13 +267,22 @@ int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream);   /* L-co
  * one launch for: reference block.py:86-95 (fused add + RMSNorm) -> lora.py:185-279 (base + task LoRA) at one token
  * per sequence, and for Mamba2.step's gated RMSNorm -> out_proj (upstream mamba2.py step()).  One sequence: any dtype mix.  Two to eight
  * sequences: one dtype for activations / weights / norm weight / LoRA (fp32 or bf16), in_features 1024 / 2048 / 4096.
- * Anything else returns OMK_EUNSUPPORTED: use the separate ops.                                                     */
+ * Anything else returns OMK_EUNSUPPORTED: use the separate ops.
+ *
+ * ABI 11, weight-only fp8: `weight` may hold OMK_F8E4M3 codes with one fp32 scale per output row in `weight_scale`:
+ *   out = rstd * (weight_scale[row] * sum_i decode(weight[row, i]) * u_i  +  lora_scale * B (A u))  [+ bias, conv tail as above]
+ * The codes are converted at the multiply and the scale is applied once per row, in fp32, behind the wave reduction; no dequantised copy
+ * of the matrix exists.  Activations, norm weight, LoRA factors, bias, conv tensors and the output keep ONE dtype (fp32 or bf16, the dtype
+ * of x; the residual fp32 or that dtype).  Served by the uniform-dtype kernels only -- one norm group, LoRA rank <= 8, in_features 1024 /
+ * 2048 / 4096, B <= 8 (two to eight sequences: the vector form), weight rows 16-byte aligned (stride(0) % 16 == 0); anything else
+ * returns OMK_EUNSUPPORTED, never the run-time-dtype kernel.  weight_scale without an fp8 weight, an fp8 weight without weight_scale, or a
+ * scale that is not contiguous fp32 (out): OMK_EINVAL.                                                                */
 typedef struct {
   OmkTensor x;             /* (B, in) */
   OmkTensor residual;      /* optional (B, in): added before the norm */
   OmkTensor z;             /* optional (B, in): gate of the gated norm (dtype of x) */
   OmkTensor norm_weight;   /* optional (in): RMSNorm weight; absent = no normalisation */
-  OmkTensor weight;        /* (out, in) f32 / bf16 / f16, 16-byte aligned rows */
+  OmkTensor weight;        /* (out, in) f32 / bf16 / f16, or OMK_F8E4M3 with weight_scale (ABI 11); 16-byte aligned rows */
   OmkTensor bias;          /* optional (out) */
   OmkTensor lora_a;        /* optional (r, in), r <= 16 */
   OmkTensor lora_b;        /* optional (out, r) */
@@ -295,6 +306,8 @@ typedef struct {
    * read or written and its conv columns [conv_offset, conv_offset + C) of out are zeros (the other columns are computed as
    * usual).  Two rows with the same non-negative index: undefined result.  Indices are read on the device only. */
   OmkTensor conv_state_indices;
+  /* ABI 11, fp32 contiguous (out): the per-row scale of an OMK_F8E4M3 weight.  Present exactly when weight.dtype == OMK_F8E4M3. */
+  OmkTensor weight_scale;
 } OmkNormLinear;
 int omk_norm_linear(const OmkNormLinear* p, omk_stream stream);
 

@@ -11,10 +11,11 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 10
+OMK_ABI_VERSION = 11
 OMK_MAX_DIMS = 5
 OMK_EUNSUPPORTED = -4   # omk_status: the kernel does not take this call (the caller may have another way)
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4}   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices, per-row lengths
+_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4,   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices, per-row lengths
+       torch.float8_e4m3fn: 5}                                                                                # 5 = OMK_F8E4M3: the weight of omk_norm_linear only (ABI 11)
 
 
 class OmkTensor(C.Structure):
@@ -28,7 +29,7 @@ def T(t: Optional[torch.Tensor]) -> OmkTensor:
         return o
     dt = _DT.get(t.dtype)
     if dt is None:
-        raise TypeError(f"unsupported dtype {t.dtype} (f32/bf16/f16, u8/bool masks, int32 indices only)")
+        raise TypeError(f"unsupported dtype {t.dtype} (f32/bf16/f16, u8/bool masks, int32 indices, e4m3 weights only)")
     n = t.dim()
     if n > OMK_MAX_DIMS:
         raise ValueError("too many dims")
@@ -73,7 +74,8 @@ SelScanBwd = _S("OmkSelScanBwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm
 NormLinear = _S("OmkNormLinear", [(n, _t) for n in ("x", "residual", "z", "norm_weight", "weight", "bias", "lora_a", "lora_b",
                                                     "residual_out", "out", "conv_state", "conv_weight", "conv_bias")]
                 + [("group_size", C.c_int64), ("conv_offset", C.c_int64), ("eps", _f), ("lora_scale", _f),
-                   ("norm_before_gate", _i), ("conv_silu", _i), ("conv_state_indices", _t)])
+                   ("norm_before_gate", _i), ("conv_silu", _i), ("conv_state_indices", _t),
+                   ("weight_scale", _t)])   # ABI 11: per-row fp32 scale of an fp8 (e4m3) weight
 LoraAdd = _S("OmkLoraAdd", [(n, _t) for n in ("out", "h", "lora_b", "mask")] + [("scale", _f)])
 LoraUpBwd = _S("OmkLoraUpBwd", [(n, _t) for n in ("dy", "lora_b", "h", "dh", "dlora_b")])
 SsdFwd = _S("OmkSsdFwd", [(n, _t) for n in ("x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "initial_states", "out",

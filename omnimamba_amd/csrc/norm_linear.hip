@@ -43,6 +43,7 @@ struct NlArgs {
   void* cst; const void* ccw; const void* ccb; int64_t csb, csc, csl, ccws; int cc0, cc1, cS, cW, csilu;   // conv tail (see omk.h)
   const int* csi; int cpool;                                         // ABI 8: conv-state slot of sequence b (null: b), pool rows
   float eps, scale;
+  const float* wsc;                                                  // ABI 11: per-row scale of an fp8 (e4m3) weight stream (null otherwise)
 };
 
 // conv-state row of sequence b: its slot in the pool, or -1 for a padding row (negative or out-of-pool index; no state traffic, zeros
@@ -235,10 +236,16 @@ template <> __device__ __forceinline__ float raw_elem<bf16_t>(const u32x4& v, in
   return __builtin_bit_cast(float, b);
 }
 
-template <class TW, class TR, int NQ, int RMAX>
+// fp8 (e4m3) weight stream, ABI 11: sixteen codes per 16-byte vector, decoded at the multiply; the per-row scale is applied by the finish
+template <> __device__ __forceinline__ float raw_elem<fp8_t>(const u32x4& v, int i) { const uint32_t e = v[i >> 2]; return fp8e4m3_to_f32(e, i & 3); }
+
+//   TQ: type of the WEIGHT STREAM only (TW, or fp8_t with a per-row fp32 scale: 16 weights per load, RW = 16 / NQ rows per batch, the same
+//   64 registers of u per lane as bf16 at 4096 features); everything else of the call stays TW
+template <class TW, class TR, int NQ, int RMAX, class TQ = TW>
 __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) {
   constexpr int In = 1024 * NQ;
-  constexpr int VEC = 16 / sizeof(TW);
+  constexpr bool Q8 = std::is_same<TQ, fp8_t>::value;
+  constexpr int VEC = 16 / sizeof(TQ);
   constexpr int LOADS = 16;                                   // 16-byte loads in flight per lane
   constexpr int STEPS_ROW = In / (64 * VEC);                  // column steps of one row
   constexpr int UNE = STEPS_ROW;                              // a lane holds a whole row slice: one request per row
@@ -249,7 +256,7 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
   float* part = sn + In;                          // [waves][8] LoRA partials
   __shared__ float red[NL_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const TW* W = (const TW*)a.W;
+  const TQ* W = (const TQ*)a.W;
   const int nwaves = gridDim.x * (NL_THREADS / 64);
   const int wg = blockIdx.x * (NL_THREADS / 64) + wave;
   int row0 = wg;
@@ -257,7 +264,7 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
   // row j of the batch that starts at row r0_ (rows past the end re-read the last row: unconditional, never used)
 #define NLF_ISSUE_ROW(r0_, j_) do {                                                                  \
     const int rj_ = (r0_) + (j_) * nwaves, rc_ = rj_ < a.Out ? rj_ : a.Out - 1;                        \
-    const TW* wp_ = W + (int64_t)rc_ * a.Ws + lane * VEC;                                              \
+    const TQ* wp_ = W + (int64_t)rc_ * a.Ws + lane * VEC;                                              \
     _Pragma("unroll") for (int u = 0; u < UNE; u++) wr[j_][u] = OMK_NL_WLOAD(wp_ + u * 64 * VEC); \
   } while (0)
   // ---- preamble: a thread owns the 4-column groups tid, tid + 256, ...
@@ -371,6 +378,8 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
   const int cslot = conv_on ? nl_slot(a, 0) : 0;      // (one sequence: a uniform scalar load)
   TW* const cst = conv_on ? (TW*)a.cst + (int64_t)(cslot >= 0 ? cslot : 0) * a.csb : nullptr;   // (padding: row 0, read and not used)
   uint32_t q_lb[RMAX > 0 ? RMAX : 1], q_wt[4], q_hist[3], q_cb, q_bias = 0u;
+  uint32_t q_ws = 0u;                                                               // fp8 weights: the row's scale, one more raw dword
+  if constexpr (Q8) q_ws = *reinterpret_cast<const uint32_t*>(a.wsc + frow);
   {
     if constexpr (RMAX > 0) {
       const TW* lbp = (const TW*)a.lb + (int64_t)frow * a.lbs;
@@ -381,8 +390,8 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
     }
     if (a.bias) q_bias = rawld((const TW*)a.bias + frow);                           // (uniform; the projections of the model have none)
     const int convC = a.cc1 - a.cc0, c_ = frow - a.cc0, ch = c_ < 0 ? 0 : (c_ < convC ? c_ : convC - 1);
-    const TW* wr_ = conv_on ? (const TW*)a.ccw + (int64_t)ch * a.ccws : W;
-    const TW* cs = conv_on ? cst + (int64_t)ch * a.csc : W;
+    const TW* wr_ = conv_on ? (const TW*)a.ccw + (int64_t)ch * a.ccws : (const TW*)a.W;   // (no conv tail: any valid 16 bytes)
+    const TW* cs = conv_on ? cst + (int64_t)ch * a.csc : (const TW*)a.W;
     const int64_t csl = conv_on ? a.csl : 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int col = k - (4 - a.cW); q_wt[k] = rawld(wr_ + (col >= 0 ? col : 0)); }
@@ -403,7 +412,7 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
 #pragma unroll
       for (int u = 0; u < UNE; u++)
 #pragma unroll
-        for (int i = 0; i < VEC; i++) acc += raw_elem<TW>(wr[j][u], i) * ur[u][i];
+        for (int i = 0; i < VEC; i++) acc += raw_elem<TQ>(wr[j][u], i) * ur[u][i];
       OMK_SCHED_FENCE();   // the refill stays below the products (hoisted, it would need a second register set)
       NLF_ISSUE_ROW(rnext, j);
       OMK_SCHED_FENCE();
@@ -418,6 +427,7 @@ __global__ __launch_bounds__(NL_THREADS) void norm_linear_fast_kernel(NlArgs a) 
   const int row = wg + lane * nwaves;
   if (lane < slot && row < a.Out) {
     float vv = keep;
+    if constexpr (Q8) vv *= __builtin_bit_cast(float, q_ws);   // the scale of the fp8 row: once, in fp32, on the reduced sum
     if (RMAX > 0) {
       float d = 0.f;
 #pragma unroll
@@ -466,23 +476,40 @@ template <class TW> struct lds_u { using type = float; };
 template <> struct lds_u<bf16_t> { using type = bf16_t; };
 
 // GATE: the second input is the gate z (dtype TW) instead of a residual (dtype TR) -- never both in this kernel.
-template <class TW, class TR, int NQ, int RMAX, int NB, bool GATE>
+// TQ: type of the weight stream (TW, or fp8_t with a per-row scale, ABI 11).  With fp8 a 16-byte weight vector covers 16 columns = SUB
+// 16-byte pieces of u (4 of fp32, 2 of bf16): u is laid out in LDS so that the lanes of a wave read piece s of a column step from
+// CONSECUTIVE 16 bytes (position nl_u_pos below), and a batch is at most 8 and at most 64 / NB rows (the totals of a batch go through one
+// butterfly; 16 rows x 4 sequences of accumulators next to 64 registers of weights went to scratch memory).
+template <class TU, int VEC> __device__ __forceinline__ int nl_u_pos(int c) {   // LDS position of column c (a multiple of 4) of one sequence's u
+  constexpr int EPS = 16 / (int)sizeof(TU);                                       // elements of u per 16 bytes
+  if constexpr (VEC == EPS) return c;
+  else {   // column = 64 VEC step + VEC lane + EPS s + e  ->  64 VEC step + 64 EPS s + EPS lane + e
+    const int w = c & (64 * VEC - 1), ln = w / VEC, s_ = (w % VEC) / EPS, e = w % EPS;
+    return (c - w) + 64 * EPS * s_ + EPS * ln + e;
+  }
+}
+template <class TW, class TR, int NQ, int RMAX, int NB, bool GATE, class TQ = TW>
 __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlArgs a) {   // two waves per SIMD: <= 256 VGPRs
   using TU = typename lds_u<TW>::type;
   constexpr int In = 1024 * NQ;
-  constexpr int VEC = 16 / sizeof(TW);
-  constexpr int LOADS = 16;
+  constexpr bool Q8 = std::is_same<TQ, fp8_t>::value;
+  constexpr int VEC = 16 / sizeof(TQ);
+  constexpr int LOADS = Q8 && NQ == 1 ? 8 : 16;               // 16-byte loads in flight per lane (fp8, 1024 features: 8 rows, RW NB <= 64)
   constexpr int UNE = In / (64 * VEC);
   constexpr int RW = LOADS / UNE;
-  constexpr int CB = (8 / NQ) < NB ? (8 / NQ) : NB;           // sequences per preamble group
-  static_assert(UNE <= LOADS && RW * UNE == LOADS && NB % CB == 0, "row length");
+  constexpr int EPS = 16 / (int)sizeof(TU), SUB = VEC / EPS;  // u per 16 bytes; 16-byte pieces of u per weight vector (1 unless fp8)
+  // sequences per preamble group (fp8 weights under fp32 activations of 4096 features with LoRA: one -- with two the preamble needed
+  // 10 - 21 registers more than the 256 there are)
+  constexpr int CBQ = Q8 && NQ == 4 && RMAX > 0 && sizeof(TW) == 4 ? 1 : 8 / NQ;
+  constexpr int CB = CBQ < NB ? CBQ : NB;
+  static_assert(UNE <= LOADS && RW * UNE == LOADS && NB % CB == 0 && RW * NB <= 64 && SUB * EPS == VEC, "row length");
   OMK_DYN_SMEM(smem);
   TU* sn = (TU*)smem;                                         // [NB][In] u
   float* part = (float*)(smem + (size_t)NB * In * sizeof(TU));   // [waves][NB][8] LoRA partials
   float* red = part + (NL_THREADS / 64) * NB * 8;             // [waves][NB] sums of squares
   float* res = red + (NL_THREADS / 64) * NB;                  // [waves][64 row slots][NB] row results
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const TW* W = (const TW*)a.W;
+  const TQ* W = (const TQ*)a.W;
   const int nwaves = gridDim.x * (NL_THREADS / 64);
   const int wg = blockIdx.x * (NL_THREADS / 64) + wave;
   int row0 = wg;
@@ -490,7 +517,7 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
 #define NLB_ISSUE(r0_) do {                                                                          \
     _Pragma("unroll") for (int j = 0; j < RW; j++) {                                                   \
       const int rj_ = (r0_) + j * nwaves, rc_ = rj_ < a.Out ? rj_ : a.Out - 1;                         \
-      const TW* wp_ = W + (int64_t)rc_ * a.Ws + lane * VEC;                                            \
+      const TQ* wp_ = W + (int64_t)rc_ * a.Ws + lane * VEC;                                            \
       _Pragma("unroll") for (int u = 0; u < UNE; u++) wr[j][u] = OMK_NL_WLOAD(wp_ + u * 64 * VEC); \
     } } while (0)
   NLB_ISSUE(row0);
@@ -548,7 +575,7 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
           ssq += q * q;
           v[cur][bb][k][i] = q * n4[k][i] * ((GATE && a.nbg) ? g : 1.f);
         }
-        store_vec<TU, 4>(sn + (size_t)(b0 + bb) * In + c, v[cur][bb][k]);
+        store_vec<TU, 4>(sn + (size_t)(b0 + bb) * In + nl_u_pos<TU, VEC>(c), v[cur][bb][k]);
         if (sizeof(TU) == 2) {   // the LoRA input is the same rounded u the rows multiply
 #pragma unroll
           for (int i = 0; i < 4; i++) v[cur][bb][k][i] = to_f32(from_f32<TU>(v[cur][bb][k][i]));
@@ -606,25 +633,27 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
     // all NB reads of a column step are issued before the first multiply: one LDS round trip per step, not one per
     // sequence (a single wave per SIMD cannot hide them: 128 serialised reads were most of the out_proj call)
 #pragma unroll
-    for (int u = 0; u < UNE; u++) {
-      using URaw = typename std::conditional<sizeof(TU) == 4, f32x4, u32x4>::type;   // 16 bytes: VEC elements of TU
-      URaw uraw[NB];
+    for (int u = 0; u < UNE; u++)
 #pragma unroll
-      for (int b = 0; b < NB; b++)
-        uraw[b] = *reinterpret_cast<const URaw*>(sn + (size_t)b * In + u * 64 * VEC + lane * VEC);
-      OMK_SCHED_FENCE();
+      for (int s = 0; s < SUB; s++) {
+        using URaw = typename std::conditional<sizeof(TU) == 4, f32x4, u32x4>::type;   // 16 bytes: EPS elements of TU
+        URaw uraw[NB];
 #pragma unroll
-      for (int b = 0; b < NB; b++)
+        for (int b = 0; b < NB; b++)
+          uraw[b] = *reinterpret_cast<const URaw*>(sn + (size_t)b * In + u * 64 * VEC + s * 64 * EPS + lane * EPS);
+        OMK_SCHED_FENCE();
 #pragma unroll
-        for (int j = 0; j < RW; j++)
+        for (int b = 0; b < NB; b++)
 #pragma unroll
-          for (int i = 0; i < VEC; i++) {
-            float uvi;
-            if constexpr (sizeof(TU) == 4) uvi = uraw[b][i];
-            else uvi = raw_elem<bf16_t>(uraw[b], i);
-            acc[j][b] += raw_elem<TW>(wr[j][u], i) * uvi;
-          }
-    }
+          for (int j = 0; j < RW; j++)
+#pragma unroll
+            for (int i = 0; i < EPS; i++) {
+              float uvi;
+              if constexpr (sizeof(TU) == 4) uvi = uraw[b][i];
+              else uvi = raw_elem<bf16_t>(uraw[b], i);
+              acc[j][b] += raw_elem<TQ>(wr[j][u], s * EPS + i) * uvi;
+            }
+      }
     row0 += RW * nwaves;
     OMK_SCHED_FENCE();
     NLB_ISSUE(row0);
@@ -654,6 +683,8 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
       for (int r = 0; r < RMAX; r++) lbv[r] = to_f32(lbp[r < a.R ? r : 0]);
     }
     const float bias = a.bias ? to_f32(((const TW*)a.bias)[row]) : 0.f;
+    float wsc = 1.f;                                            // fp8 weights: the row's scale
+    if constexpr (Q8) wsc = a.wsc[row];
     const bool isconv = a.cst && row >= a.cc0 && row < a.cc1;
     float wt[4] = {0.f, 0.f, 0.f, 0.f}, cbias = 0.f;
     const int ch = row - a.cc0;
@@ -680,6 +711,7 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
 #pragma unroll
     for (int b = 0; b < NB; b++) {
       float vv = res[(wave * 64 + lane) * NB + b];
+      if constexpr (Q8) vv *= wsc;                              // once per row, in fp32, on the reduced sum
       if (RMAX > 0) {
         float d = 0.f;
 #pragma unroll
@@ -1023,7 +1055,15 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
   // up to eight sequences per call (norm_linear_batched_kernel); more than that goes to the separate ops
   if (a.B > 8) return fail(OMK_EUNSUPPORTED, "norm_linear: batch %d > 8 is served by the unfused ops", a.B);
   const int wdt = p->weight.dtype;
-  const int vec = wdt == OMK_F32 ? 4 : 8;
+  // ABI 11: an fp8 (e4m3) weight stream comes with its per-row scale, and a scale with nothing else
+  const bool q8 = wdt == OMK_F8E4M3;
+  OMK_REQUIRE(!q8 || present(p->weight_scale), "norm_linear: an fp8 (e4m3) weight needs weight_scale");
+  OMK_REQUIRE(q8 || !present(p->weight_scale), "norm_linear: weight_scale belongs to an fp8 (e4m3) weight");
+  if (q8) OMK_REQUIRE(p->weight_scale.dtype == OMK_F32 && p->weight_scale.ndim == 1 && p->weight_scale.shape[0] == a.Out && (a.Out == 1 || p->weight_scale.stride[0] == 1),
+                      "norm_linear: weight_scale must be contiguous fp32 (out)");
+  a.wsc = (const float*)p->weight_scale.data;
+  const int cdt = q8 ? p->x.dtype : wdt;   // the ONE dtype of the templated kernels: the weight's, or the activations' in front of an fp8 weight
+  const int vec = q8 ? 16 : (wdt == OMK_F32 ? 4 : 8);
   if (a.In % 1024 != 0 || a.In > 8192 || !aligned16(p->weight) || p->weight.stride[0] % vec != 0)
     return fail(OMK_EUNSUPPORTED, "norm_linear: in_features %d must be a multiple of 1024 (<= 8192) with 16-byte aligned weight rows", a.In);
   {
@@ -1061,15 +1101,19 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
   // the templated variant: one dtype for x, z, norm weight, weight, LoRA, bias and out; fp32 or that dtype for the residual
   {
     const int xdt = p->x.dtype;
-    auto same = [&](const OmkTensor& t) { return !present(t) || t.dtype == wdt; };
+    auto same = [&](const OmkTensor& t) { return !present(t) || t.dtype == cdt; };
     const int nq = a.In / 1024;
-    const bool resok = (!present(p->residual) || p->residual.dtype == OMK_F32 || p->residual.dtype == wdt) &&
+    const bool resok = (!present(p->residual) || p->residual.dtype == OMK_F32 || p->residual.dtype == cdt) &&
                        (!present(p->residual_out) || !present(p->residual) || p->residual_out.dtype == p->residual.dtype);
-    const int trdt = present(p->residual) ? p->residual.dtype : (present(p->residual_out) ? p->residual_out.dtype : wdt);
-    const bool fast = (wdt == OMK_F32 || wdt == OMK_BF16) && xdt == wdt && same(p->z) && same(p->norm_weight) && same(p->lora_a) &&
-                      same(p->bias) && p->out.dtype == wdt && present(p->norm_weight) && a.G == 1 && a.R <= 8 && resok &&
-                      (trdt == OMK_F32 || trdt == wdt) && a.In == 1024 * nq && (nq == 1 || nq == 2 || nq == 4) &&
+    const int trdt = present(p->residual) ? p->residual.dtype : (present(p->residual_out) ? p->residual_out.dtype : cdt);
+    const bool fast = (cdt == OMK_F32 || cdt == OMK_BF16) && xdt == cdt && same(p->z) && same(p->norm_weight) && same(p->lora_a) &&
+                      same(p->bias) && p->out.dtype == cdt && present(p->norm_weight) && a.G == 1 && a.R <= 8 && resok &&
+                      (trdt == OMK_F32 || trdt == cdt) && a.In == 1024 * nq && (nq == 1 || nq == 2 || nq == 4) &&
                       (!present(p->lora_b) || p->lora_b.stride[1] == 1);
+    // fp8 weights are served by the templated kernels or not at all (the run-time-dtype kernel does not know them)
+    if (q8 && !fast)
+      return fail(OMK_EUNSUPPORTED, "norm_linear: fp8 weights need the uniform-dtype kernel (activations / norm weight / LoRA / bias / out of one dtype, fp32 or "
+                                    "bf16; one norm group; LoRA rank <= 8; in_features 1024 / 2048 / 4096)");
     if (present(p->conv_state)) {
       OMK_REQUIRE(present(p->conv_weight) && p->conv_state.ndim == 3 && p->conv_weight.ndim == 2, "norm_linear: conv_state (B, C, S) needs conv_weight (C, W)");
       const int64_t Cc = p->conv_state.shape[1];
@@ -1080,8 +1124,8 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       OMK_REQUIRE(indices_ok(p->conv_state_indices, a.B), "norm_linear: conv_state_indices must be contiguous int32 (B)");
       a.csi = (const int*)p->conv_state_indices.data; a.cpool = (int)p->conv_state.shape[0];
       OMK_REQUIRE(p->conv_weight.shape[0] == Cc && p->conv_offset >= 0 && p->conv_offset + Cc <= a.Out, "norm_linear: conv channels must be rows [conv_offset, conv_offset + C) of the output");
-      const bool cok = fast && a.cW >= 2 && a.cW <= 4 && a.cS >= a.cW - 1 && a.cS <= 4 && p->conv_state.dtype == wdt && p->conv_weight.dtype == wdt &&
-                       p->conv_weight.stride[1] == 1 && (!present(p->conv_bias) || (p->conv_bias.dtype == wdt && is_contig_last(p->conv_bias) && numel(p->conv_bias) == Cc));
+      const bool cok = fast && a.cW >= 2 && a.cW <= 4 && a.cS >= a.cW - 1 && a.cS <= 4 && p->conv_state.dtype == cdt && p->conv_weight.dtype == cdt &&
+                       p->conv_weight.stride[1] == 1 && (!present(p->conv_bias) || (p->conv_bias.dtype == cdt && is_contig_last(p->conv_bias) && numel(p->conv_bias) == Cc));
       if (!cok) return fail(OMK_EUNSUPPORTED, "norm_linear: the conv tail needs the uniform-dtype kernel (W 2..4, state length W-1..4)");
       a.cst = p->conv_state.data; a.ccw = p->conv_weight.data; a.ccb = p->conv_bias.data;
       a.csb = p->conv_state.stride[0]; a.csc = p->conv_state.stride[1]; a.csl = p->conv_state.stride[2]; a.ccws = p->conv_weight.stride[0];
@@ -1090,8 +1134,9 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
     if (fast && a.B > 1) {
       // two to eight sequences: u for all of them in LDS; one workgroup per CU when that takes more than half of it
       const int nb = a.B <= 2 ? 2 : (a.B <= 4 ? 4 : 8);
-      const int vecw = wdt == OMK_F32 ? 4 : 8, steps_row = a.In / (64 * vecw), rw = 16 / steps_row;
-      const size_t bsmem = (size_t)nb * a.In * (wdt == OMK_F32 ? 4 : 2) + (size_t)(NL_THREADS / 64) * nb * (9 + 64) * 4;
+      const int vecw = q8 ? 16 : (wdt == OMK_F32 ? 4 : 8), steps_row = a.In / (64 * vecw);
+      const int rw = q8 && steps_row == 1 ? 8 : 16 / steps_row;   // (fp8, 1024 features: batches of 8 rows, as in the kernel)
+      const size_t bsmem = (size_t)nb * a.In * (cdt == OMK_F32 ? 4 : 2) + (size_t)(NL_THREADS / 64) * nb * (9 + 64) * 4;
       // (these two limits belong to the VECTOR form below; the matrix-pipe form walks its tiles persistently and sizes its own LDS -- the
       // checks are applied behind its dispatch: advisor finding, round 5)
       const bool vec_lds_ok = bsmem <= 150 * 1024;
@@ -1113,7 +1158,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       // with LoRA, rows of up to 2048 features: 29.7 against 31.5 us for the 1.3B in_proj; behind it at two sequences (28.8 / 19.5 us) and
       // without LoRA (23.9 / 19.7 us) -- profiles/r05_decode_projections.txt.  (4096 features: 32 loads per lane and tile, no room for two tiles.)
       const bool f32_ok = wdt == OMK_F32 && nq <= 2 && nb == 8 && a.R > 0;
-      if (lora_rows16 && (wdt == OMK_BF16 || f32_ok)) {
+      if (!q8 && lora_rows16 && (wdt == OMK_BF16 || f32_ok)) {   // (fp8 weights: the vector form below)
         // tiles of 8 rows when there are fewer 16-row tiles than workgroups (out_proj of the 1.3B model: 11.1 -> 10.1 us at eight sequences,
         // 8.4 -> 7.3 us at two; with several tiles per workgroup 8 rows are behind: in_proj 16.2 -> 17.7 us)
         const int wgs = test_hook("OMK_NL_MFMA_WGS", cu_count());   // (tests: several tiles per workgroup on small matrices)
@@ -1145,13 +1190,17 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       if (!vec_lds_ok) return fail(OMK_EUNSUPPORTED, "norm_linear: %d sequences x %d features do not fit the LDS", a.B, a.In);
       if (!vec_rows_ok) return fail(OMK_EUNSUPPORTED, "norm_linear: %d output rows are too many for the batched kernel", a.Out);
 #define NLB_G(TW_, TR_, NQ_, RM_, NB_, G_) do { \
-        if (OMK_SET_MAX_DYN_SMEM((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), bsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", bsmem); \
-        OMK_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), bgrid, bblock, bsmem, stream, a); } while (0)
+        if (q8) { \
+          if (OMK_SET_MAX_DYN_SMEM((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_, fp8_t>), bsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", bsmem); \
+          OMK_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_, fp8_t>), bgrid, bblock, bsmem, stream, a); \
+        } else { \
+          if (OMK_SET_MAX_DYN_SMEM((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), bsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", bsmem); \
+          OMK_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), bgrid, bblock, bsmem, stream, a); } } while (0)
 #define NLB_GO(TW_, TR_, NQ_, RM_, NB_) do { if (gate) NLB_G(TW_, TR_, NQ_, RM_, NB_, true); else NLB_G(TW_, TR_, NQ_, RM_, NB_, false); } while (0)
 #define NLB_B(TW_, TR_, NQ_, RM_) do { if (nb == 2) NLB_GO(TW_, TR_, NQ_, RM_, 2); else if (nb == 4) NLB_GO(TW_, TR_, NQ_, RM_, 4); else NLB_GO(TW_, TR_, NQ_, RM_, 8); } while (0)
 #define NLB_R(TW_, TR_, NQ_) do { if (a.R > 0) NLB_B(TW_, TR_, NQ_, 8); else NLB_B(TW_, TR_, NQ_, 0); } while (0)
 #define NLB_Q(TW_, TR_) do { if (nq == 1) NLB_R(TW_, TR_, 1); else if (nq == 2) NLB_R(TW_, TR_, 2); else NLB_R(TW_, TR_, 4); } while (0)
-      if (wdt == OMK_F32) NLB_Q(float, float);
+      if (cdt == OMK_F32) NLB_Q(float, float);
       else if (trdt == OMK_F32) NLB_Q(bf16_t, float);
       else NLB_Q(bf16_t, bf16_t);
 #undef NLB_Q
@@ -1163,7 +1212,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
     }
     if (a.B > 1) return fail(OMK_EUNSUPPORTED, "norm_linear: batch %d needs the uniform-dtype kernel (one dtype, in_features 1024 / 2048 / 4096)", a.B);
     if (fast) {
-      const int vecw = wdt == OMK_F32 ? 4 : 8;
+      const int vecw = q8 ? 16 : (wdt == OMK_F32 ? 4 : 8);
       const int steps_row = a.In / (64 * vecw), rw = 16 / steps_row;   // rows per batch (16 loads of 16 bytes per lane)
       // waves: every wave takes k full batches of rw rows (k as small as two workgroups per CU allow)
       const int maxw = 2 * cu_count() * (NL_THREADS / 64);   // two workgroups per CU
@@ -1174,11 +1223,15 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
         dim3 fgrid((unsigned)((nw_ + NL_THREADS / 64 - 1) / (NL_THREADS / 64))), fblock(NL_THREADS);
         const size_t fsmem = ((size_t)a.In + 8 * (NL_THREADS / 64)) * 4;
 #define NLF_GO(TW_, TR_, NQ_, RM_) do { \
-          if (OMK_SET_MAX_DYN_SMEM((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), fsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", fsmem); \
-          OMK_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), fgrid, fblock, fsmem, stream, a); } while (0)
+          if (q8) { \
+            if (OMK_SET_MAX_DYN_SMEM((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_, fp8_t>), fsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", fsmem); \
+            OMK_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_, fp8_t>), fgrid, fblock, fsmem, stream, a); \
+          } else { \
+            if (OMK_SET_MAX_DYN_SMEM((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), fsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", fsmem); \
+            OMK_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), fgrid, fblock, fsmem, stream, a); } } while (0)
 #define NLF_R(TW_, TR_, NQ_) do { if (a.R > 0) NLF_GO(TW_, TR_, NQ_, 8); else NLF_GO(TW_, TR_, NQ_, 0); } while (0)
 #define NLF_Q(TW_, TR_) do { if (nq == 1) NLF_R(TW_, TR_, 1); else if (nq == 2) NLF_R(TW_, TR_, 2); else NLF_R(TW_, TR_, 4); } while (0)
-        if (wdt == OMK_F32) NLF_Q(float, float);
+        if (cdt == OMK_F32) NLF_Q(float, float);
         else if (trdt == OMK_F32) NLF_Q(bf16_t, float);
         else NLF_Q(bf16_t, bf16_t);
 #undef NLF_Q
@@ -1187,6 +1240,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
         return finish_launch("norm_linear");
       }
     }
+    if (q8) return fail(OMK_EUNSUPPORTED, "norm_linear: %d output rows are too many for the fp8 kernel", a.Out);
   }
   if (present(p->conv_state)) return fail(OMK_EUNSUPPORTED, "norm_linear: the conv tail needs the uniform-dtype kernel");
   // two workgroups per CU; small matrices get one wave per row pair

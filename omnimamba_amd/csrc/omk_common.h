@@ -35,7 +35,7 @@ inline bool is_dense(const OmkTensor& t) {
   }
   return true;
 }
-inline size_t dtype_size(int dt) { return (dt == OMK_F32 || dt == OMK_I32) ? 4 : dt == OMK_U8 ? 1 : 2; }
+inline size_t dtype_size(int dt) { return (dt == OMK_F32 || dt == OMK_I32) ? 4 : (dt == OMK_U8 || dt == OMK_F8E4M3) ? 1 : 2; }
 inline bool aligned16(const OmkTensor& t) { return ((uintptr_t)t.data & 15) == 0; }
 // ABI 8 slot indices (state_batch_indices / conv_state_indices): absent, or contiguous int32 (B).  The values are never read on the host.
 inline bool indices_ok(const OmkTensor& t, int64_t B) {
@@ -80,6 +80,7 @@ inline int test_hook(const char* name, int dflt) {
 // ---- storage types --------------------------------------------------------------------------------------
 struct bf16_t { uint16_t v; };
 struct f16_t { _Float16 v; };
+struct fp8_t { uint8_t v; };   // OCP e4m3fn code (OMK_F8E4M3): a weight-stream type only, decoded by fp8e4m3_to_f32 at the multiply
 
 template <class T> struct dtype_of;
 template <> struct dtype_of<float> { static constexpr int value = OMK_F32; };

@@ -77,6 +77,24 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
 #endif
 }
 
+// ---- OCP e4m3fn -> f32: byte i (0 .. 3) of a dword of four codes (exact: every code is an fp32 value) ------------------
+// bias 7, 3 mantissa bits, subnormals m * 2^-9, codes 0x7F / 0xFF are NaN, no infinities (NOT MI300's fnuz form, whose normal codes
+// are worth half as much).  gfx950: v_cvt_pk_f32_fp8 converts a pair of bytes per instruction (word_sel picks the upper half), so
+// the two elements of a pair share one conversion once the caller's loop over i is unrolled.
+__device__ __forceinline__ float fp8e4m3_to_f32(uint32_t word, int i) {
+#ifdef OMK_EMU
+  const uint32_t b = (word >> (8 * i)) & 0xffu, e = (b >> 3) & 15u, m = b & 7u;
+  float f;
+  if (e == 15u && m == 7u) f = NAN;
+  else if (e == 0u) f = ldexpf((float)m, -9);
+  else f = ldexpf((float)(8u + m), (int)e - 10);
+  return (b & 0x80u) ? -f : f;
+#else
+  const f32x2 p = (i & 2) ? __builtin_amdgcn_cvt_pk_f32_fp8((int)word, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)word, false);
+  return (i & 1) ? p[1] : p[0];
+#endif
+}
+
 // c + a.lo * b.lo + a.hi * b.hi on packed bf16 pairs (v_dot2c_f32_bf16 on gfx950)
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
 #ifdef OMK_EMU

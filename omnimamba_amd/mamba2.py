@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from .causal_conv1d import causal_conv1d_fn, causal_conv1d_update
 from .layernorm_gated import RMSNorm as RMSNormGated
 from . import norm_linear as NL
+from .quant import decode_weights
 from .linear import linear
 from .selective_state_update import selective_state_extend, selective_state_update
 from .ssd_combined import mamba_chunk_scan_combined, mamba_split_conv1d_scan_combined
@@ -323,11 +324,16 @@ class Mamba2(nn.Module):
                                    C.view(batch, self.ngroups, N), D_e, z=z.view(batch, H, P) if not self.rmsnorm else None,
                                    dt_bias=dt_bias_e, dt_softplus=True, state_batch_indices=state_indices)
         y = y.reshape(batch, H * P)
-        if (self.rmsnorm and d_mlp == 0 and type(self.out_proj) is nn.Linear and self.norm.bias is None
-                and NL.applies(y, self.out_proj.weight, self.norm.weight, z, self.out_proj.bias)):
-            # gated RMSNorm + out_proj in one launch (weights streamed once)
-            return NL.norm_linear(y, self.out_proj.weight, self.out_proj.bias, norm_weight=self.norm.weight, eps=self.norm.eps,
-                                  z=z, group_size=self.norm.group_size, norm_before_gate=self.norm.norm_before_gate)
+        if self.rmsnorm and d_mlp == 0 and type(self.out_proj) is nn.Linear and self.norm.bias is None:
+            # gated RMSNorm + out_proj in one launch (weights streamed once) -- from the e4m3 copy of the weight when there is a valid one
+            # (quant.quantize_decode_weights) and the fp8 kernel takes the call, else from the master weight
+            qw = decode_weights(self.out_proj)
+            if qw is not None and NL.applies(y, qw[0], self.norm.weight, self.out_proj.bias, weight_scale=qw[1], group_size=self.norm.group_size, z=z):
+                return NL.norm_linear(y, qw[0], self.out_proj.bias, norm_weight=self.norm.weight, eps=self.norm.eps, z=z,
+                                      group_size=self.norm.group_size, norm_before_gate=self.norm.norm_before_gate, weight_scale=qw[1])
+            if NL.applies(y, self.out_proj.weight, self.norm.weight, z, self.out_proj.bias):
+                return NL.norm_linear(y, self.out_proj.weight, self.out_proj.bias, norm_weight=self.norm.weight, eps=self.norm.eps,
+                                      z=z, group_size=self.norm.group_size, norm_before_gate=self.norm.norm_before_gate)
         if self.rmsnorm:
             y = self.norm(y, z)
         if d_mlp > 0:

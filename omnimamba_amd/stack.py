@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from . import lora_add as LA
 from . import lora_ext as LE
 from . import norm_linear as NL
+from .quant import decode_weights
 from .generation import GenerationMixin
 from .layer_norm import RMSNorm, layer_norm_fn
 from .linear import _WGradFn, linear
@@ -236,11 +237,18 @@ class ResidualBlock(nn.Module):
             return None
         if lora and (lora["lora_a"].shape[0] > 8 and x2.shape[0] > 1):
             return None
-        if not NL.applies(x2, ip.weight, self.norm.weight, lora.get("lora_a"), lora.get("lora_b"), ip.bias):
+        # the e4m3 copy of the weight (quant.quantize_decode_weights), when there is a valid one and the fp8 kernel takes the call;
+        # otherwise the master weight, exactly as without a copy
+        ro_dtype = torch.float32 if (self.residual_in_fp32 or (residual is not None and residual.dtype == torch.float32)) else x2.dtype
+        w, q8 = ip.weight, {}
+        qw = decode_weights(ip)
+        if qw is not None and NL.applies(x2, qw[0], self.norm.weight, lora.get("lora_b"), ip.bias, weight_scale=qw[1], lora_a=lora.get("lora_a"),
+                                         residual=None if residual is None else residual.squeeze(1), residual_out_dtype=ro_dtype):
+            w, q8 = qw[0], dict(weight_scale=qw[1])
+        elif not NL.applies(x2, ip.weight, self.norm.weight, lora.get("lora_a"), lora.get("lora_b"), ip.bias):
             return None
         if x2.shape[0] > 1 and residual is not None and residual.dtype not in (torch.float32, x2.dtype):
             return None
-        ro_dtype = torch.float32 if (self.residual_in_fp32 or (residual is not None and residual.dtype == torch.float32)) else x2.dtype
         conv_state, ssm_state = self.mixer._get_states_from_cache(inference_params, x2.shape[0])
         slots = getattr(inference_params, "state_indices", None)
         res2 = None if residual is None else residual.squeeze(1)
@@ -248,12 +256,12 @@ class ResidualBlock(nn.Module):
         cw = m.conv1d.weight.squeeze(1)
         d_mlp = (ip.weight.shape[0] - 2 * m.d_ssm - 2 * m.ngroups * m.d_state - m.nheads) // 2
         if (m.activation in ("silu", "swish") and os.environ.get("OMK_DECODE_CONV_SEPARATE") != "1"
-                and NL.conv_tail_applies(x2, ip.weight, self.norm.weight, conv_state, cw, m.conv1d.bias, lora.get("lora_a"), ip.bias, res2)):
+                and NL.conv_tail_applies(x2, w, self.norm.weight, conv_state, cw, m.conv1d.bias, lora.get("lora_a"), ip.bias, res2, **q8)):
             # the convolution of the new xBC inputs rides on the in_proj launch (one launch less per layer-step)
             conv = dict(conv_state=conv_state, conv_weight=cw, conv_bias=m.conv1d.bias, conv_offset=2 * d_mlp + m.d_ssm,
                         conv_state_indices=slots)
-        zxbcdt, new_res = NL.norm_linear(x2, ip.weight, ip.bias, norm_weight=self.norm.weight, eps=self.norm.eps,
-                                         residual=res2, residual_out_dtype=ro_dtype, **lora, **conv)
+        zxbcdt, new_res = NL.norm_linear(x2, w, ip.bias, norm_weight=self.norm.weight, eps=self.norm.eps,
+                                         residual=res2, residual_out_dtype=ro_dtype, **lora, **conv, **q8)
         out = self.mixer.step_from_zxbcdt(zxbcdt, conv_state, ssm_state, conv_done=bool(conv), state_indices=slots)
         return out.unsqueeze(1), new_res.unsqueeze(1)
 

@@ -21,8 +21,14 @@ def bench_decode(args, dev):
     (the reference inference scripts never cast the model: scripts/inference_t2i.py:21-26)."""
     torch.manual_seed(0)
     cfg = StackConfig.omnimamba_1_3b()
-    wdt = torch.bfloat16 if args.weights == "bf16" else torch.float32   # the reference keeps fp32; bf16 = a model cast by the user
+    # the reference keeps fp32; bf16 = a model cast by the user; fp8 = bf16 activations with e4m3 in_proj / out_proj in the fused step
+    # (omnimamba_amd.quant), --weights f32 --quant fp8 = fp32 activations with them
+    quant = "fp8" if args.weights == "fp8" else args.quant
+    wdt = torch.bfloat16 if args.weights in ("bf16", "fp8") else torch.float32
     model = OmniMambaLM(cfg, device=dev, dtype=wdt).eval()
+    if quant == "fp8":
+        from omnimamba_amd.quant import quantize_decode_weights
+        quantize_decode_weights(model)
     B, P, new = args.batch, 72, 256
     ids = torch.zeros(B, P, dtype=torch.long, device=dev)
     emb = torch.randn(B, P, cfg.d_model, device=dev, dtype=wdt) * 0.02 + model.backbone.pos_embed[:, :P].to(wdt)
@@ -37,11 +43,18 @@ def bench_decode(args, dev):
         assert seq.shape == (B, P + new)
         out["graph" if cg else "eager"] = dt
     n_param = sum(p.numel() for p in model.parameters())
+    n_bytes = n_param * (2 if wdt == torch.bfloat16 else 4)
+    if quant == "fp8":   # the step streams the e4m3 codes and row scales of the projections instead of their master weights
+        from omnimamba_amd.quant import decode_weights
+        for m in model.modules():
+            qw = decode_weights(m) if isinstance(m, torch.nn.Linear) else None
+            if qw is not None:
+                n_bytes += qw[0].numel() + 4 * qw[1].numel() - m.weight.numel() * m.weight.element_size()
     ms_tok = out["graph"] / new * 1e3
     print(json.dumps({"workload": "OmniMamba-1.3B T2I decode (configs[2])", "batch": B, "prompt": P, "new_tokens": new,
                       "ms_per_token": round(ms_tok, 3), "tokens_per_s": round(B * new / out["graph"], 1),
-                      "weights_GBs": round(n_param * (2 if wdt == torch.bfloat16 else 4) / (ms_tok * 1e-3) / 1e9, 1), "params": n_param,
-                      "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
+                      "weights_GBs": round(n_bytes / (ms_tok * 1e-3) / 1e9, 1), "params": n_param,
+                      "dtype": "bf16" if wdt == torch.bfloat16 else "f32", "decode_projections": "fp8_e4m3" if quant == "fp8" else None,
                       "eager_ms_per_token": round(out["eager"] / new * 1e3, 3) if "eager" in out else None}), flush=True)
 
 
@@ -160,12 +173,17 @@ def bench_decode_mmu_batch(args, dev):
     --prefill-batch / --prefill-bucket: the ragged-prefill options of decode_ragged.  --reps N: the ragged run N times (every time is
     printed: the spread is the point).  One more run under _AdmissionClock gives the time spent in admission (prefill + state copy)
     and the time to the first token of the first and of the last request of the opening burst; that run synchronises around every
-    admission and is not one of the timed ones.  --no-sequential: skip the sequential baseline."""
+    admission and is not one of the timed ones.  --no-sequential: skip the sequential baseline.
+    --weights fp8: the bf16 model alone with e4m3 in_proj / out_proj in the fused step; --quant fp8: every dtype of --dtypes with them."""
     cfg = StackConfig.omnimamba_1_3b()
     opts = dict(prefill_batch=args.prefill_batch, prefill_bucket=args.prefill_bucket)
-    for wdt in [dict(f32=torch.float32, bf16=torch.bfloat16)[d] for d in args.dtypes.split(",")]:
+    quant = "fp8" if args.weights == "fp8" else args.quant
+    for wdt in [dict(f32=torch.float32, bf16=torch.bfloat16)[d] for d in ("bf16" if args.weights == "fp8" else args.dtypes).split(",")]:
         torch.manual_seed(0)
         model = OmniMambaPath(cfg, stage="inference", device=dev, dtype=wdt)
+        if quant == "fp8":
+            from omnimamba_amd.quant import quantize_decode_weights
+            quantize_decode_weights(model)
         feats, qs, lens, new = _mmu_batch_workload(cfg, dev)
         feats = [f.to(wdt) for f in feats]
         n_tok = sum(new)
@@ -194,6 +212,7 @@ def bench_decode_mmu_batch(args, dev):
         assert got == [4 + q.shape[1] + n for q, n in zip(qs, new)], got
         same = None if seq is None else sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
         print(json.dumps({"workload": "OmniMamba-1.3B MMU continuous batching", "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
+                          "decode_projections": "fp8_e4m3" if quant == "fp8" else None,
                           "requests": len(qs), "generated_tokens": n_tok, "max_batch": args.max_batch, **opts,
                           "sequential_s": None if t_seq is None else round(t_seq, 3), "ragged_s": round(t_rag, 3),
                           "ragged_s_all": [round(t, 3) for t in t_rags],
@@ -410,7 +429,10 @@ def main():
     ap.add_argument("--tasks", default="t2i,mmu", help="t2i,mmu (stage 2) or mmu (stage-1 MMU pretrain, BASELINE configs[3])")
     ap.add_argument("--eager-too", action="store_true")
     ap.add_argument("--task", default="t2i", choices=["t2i", "mmu"], help="decode: T2I (configs[2]) or the MMU generation of scripts/inference_mmu.py")
-    ap.add_argument("--weights", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--weights", choices=["f32", "bf16", "fp8"], default="f32",
+                    help="decode / decode_mmu_batch: fp8 = bf16 activations with e4m3 in_proj / out_proj in the fused decode step")
+    ap.add_argument("--quant", choices=["none", "fp8"], default="none",
+                    help="decode / decode_mmu_batch: e4m3 in_proj / out_proj under the chosen --weights / --dtypes (f32: fp32 activations)")
     args = ap.parse_args()
     rank, local, world = init_distributed()
     dev = torch.device("cuda", local)
