@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 11
+#define OMK_ABI_VERSION 12
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
@@ -274,8 +274,9 @@ int omk_selective_scan_bwd(const OmkSelScanBwd* p, omk_stream stream);   /* L-co
  * The codes are converted at the multiply and the scale is applied once per row, in fp32, behind the wave reduction; no dequantised copy
  * of the matrix exists.  Activations, norm weight, LoRA factors, bias, conv tensors and the output keep ONE dtype (fp32 or bf16, the dtype
  * of x; the residual fp32 or that dtype).  Served by the uniform-dtype kernels only -- one norm group, LoRA rank <= 8, in_features 1024 /
- * 2048 / 4096, B <= 8 (two to eight sequences: the vector form), weight rows 16-byte aligned (stride(0) % 16 == 0); anything else
- * returns OMK_EUNSUPPORTED, never the run-time-dtype kernel.  weight_scale without an fp8 weight, an fp8 weight without weight_scale, or a
+ * 2048 / 4096, B <= 8, weight rows 16-byte aligned (stride(0) % 16 == 0); anything else returns OMK_EUNSUPPORTED, never the
+ * run-time-dtype kernel.  Two to eight sequences: under bf16 activations the matrix form (ABI 12: the codes become bf16 operands of
+ * v_mfma_f32_16x16x32_bf16 as they land -- exact -- under the conditions of a bf16 weight), under fp32 activations the vector form.  weight_scale without an fp8 weight, an fp8 weight without weight_scale, or a
  * scale that is not contiguous fp32 (out): OMK_EINVAL.                                                                */
 typedef struct {
   OmkTensor x;             /* (B, in) */
@@ -310,6 +311,13 @@ typedef struct {
   OmkTensor weight_scale;
 } OmkNormLinear;
 int omk_norm_linear(const OmkNormLinear* p, omk_stream stream);
+/* ABI 12: which kernel omk_norm_linear runs for this call (nothing is launched; it is the launch's own decision, made by the same code):
+ * GENERIC = one sequence, run-time dtypes; FAST = one sequence, uniform dtype; BATCHED = two to eight sequences on the vector pipe;
+ * MATRIX = two to eight sequences on the matrix pipe (bf16 weights; fp8 weights under bf16 activations; fp32 weights at eight sequences
+ * with LoRA and <= 2048 features).  < 0: the omk_status with which omk_norm_linear would refuse the call.  A call with no sequence or no
+ * output row launches nothing and reports GENERIC. */
+enum { OMK_NL_FORM_GENERIC = 0, OMK_NL_FORM_FAST = 1, OMK_NL_FORM_BATCHED = 2, OMK_NL_FORM_MATRIX = 3 };
+int omk_norm_linear_form(const OmkNormLinear* p);
 
 /* ---- task LoRA of a projection: out += scale * h lora_b^T, in place ------------------------------------------
  * reference models/stage2/lora.py:263-279 (result += lora_B(lora_A(dropout(x))) * scaling) at training / prefill token counts.

@@ -11,9 +11,10 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 11
+OMK_ABI_VERSION = 12
 OMK_MAX_DIMS = 5
 OMK_EUNSUPPORTED = -4   # omk_status: the kernel does not take this call (the caller may have another way)
+NL_FORM_GENERIC, NL_FORM_FAST, NL_FORM_BATCHED, NL_FORM_MATRIX = 0, 1, 2, 3   # omk_norm_linear_form (ABI 12)
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2, torch.uint8: 3, torch.bool: 3, torch.int32: 4,   # 3 = OMK_U8: masks only; 4 = OMK_I32: slot indices, per-row lengths
        torch.float8_e4m3fn: 5}                                                                                # 5 = OMK_F8E4M3: the weight of omk_norm_linear only (ABI 11)
 
@@ -104,7 +105,7 @@ SYMBOLS = [
     "omk_add_norm_fwd", "omk_add_norm_bwd_workspace_bytes", "omk_add_norm_bwd",
     "omk_norm_gated_fwd", "omk_norm_gated_bwd_workspace_bytes", "omk_norm_gated_bwd",
     "omk_causal_conv1d_fwd", "omk_causal_conv1d_bwd_workspace_bytes", "omk_causal_conv1d_bwd", "omk_causal_conv1d_update",
-    "omk_selective_state_update", "omk_selective_state_extend", "omk_norm_linear", "omk_lora_add", "omk_lora_up_bwd",
+    "omk_selective_state_update", "omk_selective_state_extend", "omk_norm_linear", "omk_norm_linear_form", "omk_lora_add", "omk_lora_up_bwd",
     "omk_selective_scan_fwd", "omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_selective_scan_bwd_workspace_bytes", "omk_selective_scan_bwd",
     "omk_ssd_scan_fwd_workspace_bytes", "omk_ssd_scan_fwd_window_states_bytes", "omk_ssd_scan_fwd", "omk_ssd_scan_bwd_workspace_bytes", "omk_ssd_scan_bwd",
     "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample",
@@ -124,7 +125,7 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if s.endswith("_workspace_bytes") or s.endswith("_window_states_bytes"):
             fn.restype = C.c_size_t
             fn.argtypes = [C.c_void_p]
-        elif s in ("omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form"):
+        elif s in ("omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_norm_linear_form"):
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p]
         elif s == "omk_lora_up_bwd_parts":

@@ -774,15 +774,26 @@ __global__ __launch_bounds__(NL_THREADS, 2) void norm_linear_batched_kernel(NlAr
 // ROWS = 16 or 8 rows per tile: with 8 the lanes i >= 8 of a fragment repeat the rows of the lanes i - 8 (same addresses: no more HBM
 // traffic, twice the matrix instructions per byte, which are free here) -- twice as many units of work, for matrices with few tiles per CU
 // (out_proj of the 1.3B model: 128 tiles of 16 rows on 256 CUs; in_proj: 532 tiles = 2 or 3 per workgroup).
-template <class TW, class TR, int NQ, int RMAX, int NB, bool GATE, int NT, int ROWS>
+// TQ: type of the WEIGHT STREAM (TW, or fp8_t under bf16 activations with a per-row fp32 scale, ABI 12).  A landed 16-byte vector then holds
+// 16 features of its row: lane (i, g) owns the features [64 s + 16 g, + 16), converts the codes to bf16 (exact) -- two A fragments -- and
+// meets them with two ds_read_b128 of the same features of u in two matrix instructions.  Half the loads per tile, so the weights of FOUR
+// tiles are in flight per workgroup instead of two (the same bytes; the finish operands stay two tiles ahead: two sets, taken in turn); the
+// row's scale travels with the finish operands and multiplies the reduced sum once.  The LoRA tile, u, the products and the sums are what
+// they are for bf16 weights.  (Eight sequences of 4096 features with an fp32 residual keep two tiles: 96 registers of raw inputs next to
+// four tiles of weights did not fit -- the bf16 twin of that one, not a shape of the model, spills with two.)
+template <class TW, class TR, int NQ, int RMAX, int NB, bool GATE, int NT, int ROWS, class TQ = TW>
 __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   using TU = typename lds_u<TW>::type;
-  constexpr int In = 1024 * NQ, VEC = 16 / sizeof(TW), NWV = NT / 64;
+  constexpr bool Q8 = std::is_same<TQ, fp8_t>::value;
+  constexpr int In = 1024 * NQ, VEC = 16 / sizeof(TW), VECQ = 16 / sizeof(TQ), NWV = NT / 64;
   constexpr int NQT = In / (4 * NT);                                        // 4-element pieces per thread and sequence
   constexpr int US = In + 16 / (int)sizeof(TU);
-  constexpr int KL = 4 * VEC, KPW = In / NWV, NLD = KPW / KL;               // features per wave load, per wave; loads per lane and tile
+  constexpr int KL = 4 * VECQ, KPW = In / NWV, NLD = KPW / KL;              // features per wave load, per wave; loads per lane and tile
+  constexpr int KLA = 4 * VEC, NLDA = KPW / KLA;                            // the same for the LoRA A rows (always TW)
+  constexpr int NSET = Q8 && !(NQ == 4 && NB == 8 && !GATE && sizeof(TR) == 4) ? 4 : 2;   // tiles of weights in flight per workgroup
   constexpr bool W32 = sizeof(TW) == 4;                                     // fp32 weights: four v_mfma_f32_16x16x4_f32 per 16-byte vector
-  static_assert(NQT >= 1 && NQT * 4 * NT == In && 16 * NB <= NT && NLD <= 16 && RMAX <= 8 && (ROWS == 8 || ROWS == 16), "shape");
+  static_assert(NQT >= 1 && NQT * 4 * NT == In && 16 * NB <= NT && NLD <= 16 && NLDA <= 16 && RMAX <= 8 && (ROWS == 8 || ROWS == 16), "shape");
+  static_assert(!Q8 || std::is_same<TW, bf16_t>::value, "an fp8 weight stream meets bf16 activations");
   OMK_DYN_SMEM(smem);
   TU* sn = (TU*)smem;                                            // [NB][US] u
   float* part = (float*)(smem + (size_t)NB * US * sizeof(TU));   // [waves][NB][8] LoRA partials
@@ -825,14 +836,14 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   static_assert(RMAX == 0 || RMAX == 8, "LoRA B rows of 16 bytes");
   // (raw 16-bit values from clamped, always valid addresses: no branch and no conversion between two loads -- with the selects and
   // conversions next to the loads every one of the ~12 small loads of a thread became its own branch + s_waitcnt vmcnt(0), ~4 us per call)
-  struct Fin { uint32_t lbq[LBR]; uint32_t hist[3], wt[4], cbias, bias; };   // (one register per value: 16-bit members get packed -- a wait)
+  struct Fin { uint32_t lbq[LBR]; uint32_t hist[3], wt[4], cbias, bias, ws; };   // (one register per value: 16-bit members get packed -- a wait)
   const bool conv_on = a.cst != nullptr;
   const int convC = a.cc1 - a.cc0;
   // conv-state slot of the sequence this thread finishes, loaded once (-1: padding sequence -- row 0 is read and not used)
   const int fslot = conv_on ? nl_slot(a, fb < a.B ? fb : a.B - 1) : 0;
   auto load_w = [&](u32x4 (&w)[NLD], int t) {
     const int rt = ROWS * t + (t16 & (ROWS - 1));
-    const TW* wp = (const TW*)a.W + (int64_t)(rt < a.Out ? rt : a.Out - 1) * a.Ws + wave * KPW + VEC * g16;
+    const TQ* wp = (const TQ*)a.W + (int64_t)(rt < a.Out ? rt : a.Out - 1) * a.Ws + wave * KPW + VECQ * g16;
 #pragma unroll
     for (int s = 0; s < NLD; s++) w[s] = OMK_NL_WLOAD(wp + KL * s);
   };
@@ -842,6 +853,8 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   };
   auto load_fin = [&](Fin& f, int t) {   // (no branch in here: without the conv tail the taps and the state read a valid dummy address)
     const int fr = ROWS * t + fi, frow = fr < a.Out ? fr : a.Out - 1, fbc = fb < a.B ? fb : a.B - 1;
+    if constexpr (Q8) f.ws = *reinterpret_cast<const uint32_t*>(a.wsc + frow);   // the row's scale: one more raw dword, never read in the finish
+    else f.ws = 0u;
     if constexpr (RMAX > 0) {   // the LoRA B row as stored, RMAX values = 16 / 32 bytes (the launcher checks R == RMAX and the alignment)
       const u32x4* lq = reinterpret_cast<const u32x4*>((const TW*)a.lb + (int64_t)frow * a.lbs);
 #pragma unroll
@@ -862,25 +875,29 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   };
   // (order of the requests = order of their return: everything small in front of the weights, so that neither the preamble nor the LoRA
   // tile nor the finish of the first tile waits for the second tile's weights to land)
-  u32x4 wA[NLD], wB[NLD];
+  u32x4 wA[NLD], wB[NLD], wC[NSET == 4 ? NLD : 1], wD[NSET == 4 ? NLD : 1];   // (the third and fourth set: fp8 only)
   Fin fA, fB;
   const int tfirst = (int)blockIdx.x;
   load_fin(fA, tfirst);
   if (tfirst + gstep < ntile) load_fin(fB, tfirst + gstep);
   // LoRA A rows: eight loads per lane at a time (NLD = 16: two halves, each requested when the registers of the one before are free)
-  constexpr int NLH = NLD < 8 ? NLD : 8;
+  constexpr int NLH = NLDA < 8 ? NLDA : 8;
   u32x4 wl[RMAX > 0 ? NLH : 1];
-  constexpr bool LORA_EARLY = RMAX > 0 && NLD <= 8 && !W32;   // (next to the preamble's registers only when everything fits 256)
+  constexpr bool LORA_EARLY = RMAX > 0 && NLDA <= 8 && !W32;   // (next to the preamble's registers only when everything fits 256)
   auto load_lora = [&](int s0) {
     const int r8 = t16 & 7;
     const TW* lap = (const TW*)a.la + (int64_t)(r8 < a.R ? r8 : 0) * a.las + wave * KPW + VEC * g16;
 #pragma unroll
-    for (int s = 0; s < NLH; s++) wl[s] = *reinterpret_cast<const u32x4*>(lap + KL * (s0 + s));
+    for (int s = 0; s < NLH; s++) wl[s] = *reinterpret_cast<const u32x4*>(lap + KLA * (s0 + s));
   };
   if constexpr (LORA_EARLY) load_lora(0);
   OMK_SCHED_FENCE();
   load_w(wA, tfirst);
   if (tfirst + gstep < ntile) load_w(wB, tfirst + gstep);
+  if constexpr (NSET == 4) {
+    if (tfirst + 2 * gstep < ntile) load_w(wC, tfirst + 2 * gstep);
+    if (tfirst + 3 * gstep < ntile) load_w(wD, tfirst + 3 * gstep);
+  }
   OMK_SCHED_FENCE();
   // ---- preamble: u = (x + residual | x silu(z)) * w of every sequence into LDS, sums of squares per wave
   auto un16 = [](uint32_t r, int i) -> float {   // element i (0 / 1) of a packed pair of TW
@@ -924,17 +941,28 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   // __builtin_bit_cast(float, wv[e]) reads element 0 for every e with this compiler.)
   auto mma = [&](const u32x4& wv, int s_, f32x4 (&ac)[2]) {
     if constexpr (W32) {
-      const f32x4 uv = *reinterpret_cast<const f32x4*>(up + KL * s_), wf = __builtin_bit_cast(f32x4, wv);
+      const f32x4 uv = *reinterpret_cast<const f32x4*>(up + KLA * s_), wf = __builtin_bit_cast(f32x4, wv);
 #pragma unroll
       for (int e = 0; e < 4; e++) ac[e & 1] = mfma16x16x4_f32(wf[e], uv[e], ac[e & 1]);
     } else {
-      ac[s_ & 1] = mfma16x16x32_bf16(as_s16x8(wv), as_s16x8(ld16(up + KL * s_)), ac[s_ & 1]);
+      ac[s_ & 1] = mfma16x16x32_bf16(as_s16x8(wv), as_s16x8(ld16(up + KLA * s_)), ac[s_ & 1]);
     }
+  };
+  // the same for a landed vector of 16 fp8 codes: features [0, 8) of the lane's 16 in the first instruction, [8, 16) in the second, on both
+  // operands (a sum over k: which feature sits in which slot is free as long as A and B agree)
+  const TU* upq = sn + (size_t)(t16 & (NB - 1)) * US + wave * KPW + VECQ * g16;
+  auto mmaq = [&](const u32x4& wv, int s_, f32x4 (&ac)[2]) {
+    uint32_t h[8];
+#pragma unroll
+    for (int e = 0; e < 4; e++) { const uint32_t wq = wv[e]; fp8e4m3x4_to_bf16x2(wq, h[2 * e], h[2 * e + 1]); }
+    const u32x4 a0 = {h[0], h[1], h[2], h[3]}, a1 = {h[4], h[5], h[6], h[7]};
+    ac[0] = mfma16x16x32_bf16(as_s16x8(a0), as_s16x8(ld16(upq + KL * s_)), ac[0]);
+    ac[1] = mfma16x16x32_bf16(as_s16x8(a1), as_s16x8(ld16(upq + KL * s_ + 8)), ac[1]);
   };
   if constexpr (RMAX > 0) {   // h[rank][sequence] of this wave's slice: ranks 4 g + r (g < 2), sequence lane & 15
     f32x4 hacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-    for (int s0 = 0; s0 < NLD; s0 += NLH) {
+    for (int s0 = 0; s0 < NLDA; s0 += NLH) {
       if (s0 > 0) load_lora(s0);
 #pragma unroll
       for (int s = 0; s < NLH; s++) mma(wl[s], s0 + s, hacc);
@@ -965,10 +993,18 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
   auto tile_step = [&](u32x4 (&w)[NLD], Fin& f, int t, int par) {
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-    for (int s = 0; s < NLD; s++) mma(w[s], s, acc);
+    for (int s = 0; s < NLD; s++) {
+      if constexpr (Q8) mmaq(w[s], s, acc);
+      else mma(w[s], s, acc);
+    }
     const Fin fc = f;
-    const int tn = t + 2 * gstep;
-    if (tn < ntile) { load_w(w, tn); load_fin(f, tn); }
+    const int tn = t + NSET * gstep;
+    if constexpr (NSET == 2) {
+      if (tn < ntile) { load_w(w, tn); load_fin(f, tn); }
+    } else {   // (the finish operands of the tile two steps on in front of the weights of the tile four steps on: they are needed first)
+      if (t + 2 * gstep < ntile) load_fin(f, t + 2 * gstep);
+      if (tn < ntile) load_w(w, tn);
+    }
     float* rs = res + par * (NWV * ROWS * NB);
     if (t16 < NB && 4 * g16 < ROWS) {
 #pragma unroll
@@ -986,6 +1022,7 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
       float vv = 0.f;
 #pragma unroll
       for (int w2 = 0; w2 < NWV; w2++) vv += rs[(w2 * ROWS + fi) * NB + fb];
+      if constexpr (Q8) vv *= __builtin_bit_cast(float, fc.ws);   // the scale of the fp8 row: once, in fp32, on the reduced sum
       if constexpr (RMAX > 0) {
         float d = 0.f;
 #pragma unroll
@@ -1018,9 +1055,13 @@ __global__ __launch_bounds__(NT, 1) void norm_linear_mfma_kernel(NlArgs a) {
       ((TW*)a.out)[(int64_t)fb * a.os + frow] = from_f32<TW>(vv);
     }
   };
-  for (int t = tfirst; t < ntile; t += 2 * gstep) {
+  for (int t = tfirst; t < ntile; t += NSET * gstep) {
     tile_step(wA, fA, t, 0);
     if (t + gstep < ntile) tile_step(wB, fB, t + gstep, 1);
+    if constexpr (NSET == 4) {
+      if (t + 2 * gstep < ntile) tile_step(wC, fA, t + 2 * gstep, 0);
+      if (t + 3 * gstep < ntile) tile_step(wD, fB, t + 3 * gstep, 1);
+    }
   }
 }
 
@@ -1043,15 +1084,31 @@ static int cu_count() {
 
 using namespace omk;
 
-extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
+// ---------------------------------------------------------------------------------------------------------
+// THE selector: every check of a call, its kernel arguments and which of the four kernels takes it -- omk_norm_linear launches what this
+// says, omk_norm_linear_form reports it.  Returns OMK_NL_FORM_* or the negative omk_status of a call that is refused; launches nothing.
+namespace {
+struct NlPlan {
+  NlArgs a;
+  bool empty;                       // no sequence or no output row: nothing to launch
+  int wdt, cdt, trdt, nq, nb;       // weight dtype; the one dtype of the templated kernels; residual dtype; In / 1024; sequences rounded up (2 / 4 / 8)
+  bool q8, gate;
+  int rows;                         // matrix form: rows per tile (8 / 16)
+  unsigned grid;                    // workgroups
+  size_t smem;                      // dynamic LDS
+};
+}  // namespace
+
+static int nl_plan(const OmkNormLinear* p, NlPlan& pl) {
   OMK_REQUIRE(p && present(p->x) && present(p->weight) && present(p->out), "norm_linear: x, weight, out required");
   OMK_REQUIRE(p->x.ndim == 2 && p->out.ndim == 2 && p->weight.ndim == 2, "norm_linear: x (B, in), weight (out, in), out (B, out)");
-  NlArgs a = {};
+  pl = NlPlan{};
+  NlArgs& a = pl.a;
   a.B = (int)p->x.shape[0]; a.In = (int)p->x.shape[1]; a.Out = (int)p->weight.shape[0];
   OMK_REQUIRE(p->weight.shape[1] == a.In && p->out.shape[0] == a.B && p->out.shape[1] == a.Out, "norm_linear: shape mismatch");
   OMK_REQUIRE(p->x.stride[1] == 1 && p->out.stride[1] == 1 && p->weight.stride[1] == 1, "norm_linear: last dims must be contiguous");
   OMK_REQUIRE(!present(p->conv_state_indices) || present(p->conv_state), "norm_linear: conv_state_indices need conv_state");
-  if (a.B == 0 || a.Out == 0) return OMK_OK;
+  if (a.B == 0 || a.Out == 0) { pl.empty = true; return OMK_NL_FORM_GENERIC; }
   // up to eight sequences per call (norm_linear_batched_kernel); more than that goes to the separate ops
   if (a.B > 8) return fail(OMK_EUNSUPPORTED, "norm_linear: batch %d > 8 is served by the unfused ops", a.B);
   const int wdt = p->weight.dtype;
@@ -1062,6 +1119,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
   if (q8) OMK_REQUIRE(p->weight_scale.dtype == OMK_F32 && p->weight_scale.ndim == 1 && p->weight_scale.shape[0] == a.Out && (a.Out == 1 || p->weight_scale.stride[0] == 1),
                       "norm_linear: weight_scale must be contiguous fp32 (out)");
   a.wsc = (const float*)p->weight_scale.data;
+  pl.wdt = wdt; pl.q8 = q8;
   const int cdt = q8 ? p->x.dtype : wdt;   // the ONE dtype of the templated kernels: the weight's, or the activations' in front of an fp8 weight
   const int vec = q8 ? 16 : (wdt == OMK_F32 ? 4 : 8);
   if (a.In % 1024 != 0 || a.In > 8192 || !aligned16(p->weight) || p->weight.stride[0] % vec != 0)
@@ -1096,7 +1154,6 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
   a.ros = present(p->residual_out) ? p->residual_out.stride[0] : 0; a.os = p->out.stride[0]; a.Ws = p->weight.stride[0];
   a.xdt = p->x.dtype; a.rdt = p->residual.dtype; a.rodt = p->residual_out.dtype; a.nwdt = p->norm_weight.dtype; a.bdt = p->bias.dtype; a.odt = p->out.dtype;
   a.nbg = p->norm_before_gate; a.eps = p->eps; a.scale = p->lora_scale;
-  const size_t smem = ((size_t)a.In + (size_t)NL_MAXR * (NL_THREADS / 64)) * 4;
   if (a.G > 8 || (a.G > 1 && a.R > 0)) return fail(OMK_EUNSUPPORTED, "norm_linear: more than 8 norm groups, or grouped norm together with LoRA");
   // the templated variant: one dtype for x, z, norm weight, weight, LoRA, bias and out; fp32 or that dtype for the residual
   {
@@ -1106,6 +1163,7 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
     const bool resok = (!present(p->residual) || p->residual.dtype == OMK_F32 || p->residual.dtype == cdt) &&
                        (!present(p->residual_out) || !present(p->residual) || p->residual_out.dtype == p->residual.dtype);
     const int trdt = present(p->residual) ? p->residual.dtype : (present(p->residual_out) ? p->residual_out.dtype : cdt);
+    pl.cdt = cdt; pl.trdt = trdt; pl.nq = nq;
     const bool fast = (cdt == OMK_F32 || cdt == OMK_BF16) && xdt == cdt && same(p->z) && same(p->norm_weight) && same(p->lora_a) &&
                       same(p->bias) && p->out.dtype == cdt && present(p->norm_weight) && a.G == 1 && a.R <= 8 && resok &&
                       (trdt == OMK_F32 || trdt == cdt) && a.In == 1024 * nq && (nq == 1 || nq == 2 || nq == 4) &&
@@ -1146,69 +1204,37 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       const int nw_ = (a.Out + rw * k - 1) / (rw * k);
       a.nbatch = k;
       const bool vec_rows_ok = k * rw <= 64;
-      dim3 bgrid((unsigned)((nw_ + NL_THREADS / 64 - 1) / (NL_THREADS / 64))), bblock(NL_THREADS);
       const bool gate = present(p->z);
+      pl.nb = nb; pl.gate = gate;
       if (gate && present(p->residual)) return fail(OMK_EUNSUPPORTED, "norm_linear: residual and gate together are served by the batch-1 kernel only");
       // 16-bit weights: the matrix-pipe form, a workgroup per tile of 16 rows
       // B rows of the LoRA read as 16-byte loads
       // (both matrices: load_lora reads the A rows as 16-byte vectors too -- advisor finding, round 5)
-      const bool lora_rows16 = a.R == 0 || (a.R == 8 && (a.lbs * (wdt == OMK_F32 ? 4 : 2)) % 16 == 0 && (reinterpret_cast<uintptr_t>(a.lb) & 15) == 0 &&
-                                            (a.las * (wdt == OMK_F32 ? 4 : 2)) % 16 == 0 && (reinterpret_cast<uintptr_t>(a.la) & 15) == 0);
+      const bool lora_rows16 = a.R == 0 || (a.R == 8 && (a.lbs * (cdt == OMK_F32 ? 4 : 2)) % 16 == 0 && (reinterpret_cast<uintptr_t>(a.lb) & 15) == 0 &&
+                                            (a.las * (cdt == OMK_F32 ? 4 : 2)) % 16 == 0 && (reinterpret_cast<uintptr_t>(a.la) & 15) == 0);
       // fp32 weights (four v_mfma_f32_16x16x4_f32 per 16-byte vector): only where it was measured ahead of the vector form -- eight sequences
       // with LoRA, rows of up to 2048 features: 29.7 against 31.5 us for the 1.3B in_proj; behind it at two sequences (28.8 / 19.5 us) and
       // without LoRA (23.9 / 19.7 us) -- profiles/r05_decode_projections.txt.  (4096 features: 32 loads per lane and tile, no room for two tiles.)
       const bool f32_ok = wdt == OMK_F32 && nq <= 2 && nb == 8 && a.R > 0;
-      if (!q8 && lora_rows16 && (wdt == OMK_BF16 || f32_ok)) {   // (fp8 weights: the vector form below)
+      // fp8 weights under bf16 activations (ABI 12): the same form, the codes converted to bf16 operands as they land -- measured ahead of the
+      // vector form at every shape class (profiles/fp8_decode_matrix.txt).  Under fp32 activations they stay on the vector form.
+      const bool q8_ok = q8 && cdt == OMK_BF16;
+      if (lora_rows16 && (q8 ? q8_ok : (wdt == OMK_BF16 || f32_ok))) {
         // tiles of 8 rows when there are fewer 16-row tiles than workgroups (out_proj of the 1.3B model: 11.1 -> 10.1 us at eight sequences,
         // 8.4 -> 7.3 us at two; with several tiles per workgroup 8 rows are behind: in_proj 16.2 -> 17.7 us)
         const int wgs = test_hook("OMK_NL_MFMA_WGS", cu_count());   // (tests: several tiles per workgroup on small matrices)
         const int rows = (a.Out + 15) / 16 < wgs ? 8 : 16;
-        const int nwv = nq == 1 ? 4 : 8, ntile = (a.Out + rows - 1) / rows, ub = wdt == OMK_F32 ? 4 : 2;
-        const size_t msmem = (size_t)nb * (a.In + 16 / ub) * ub + (size_t)nwv * nb * (9 + 2 * 16) * 4 + (size_t)nb * 9 * 4;
-        dim3 mgrid((unsigned)(ntile < wgs ? ntile : wgs));
-#define NLM_G(TW_, TR_, NQ_, RM_, NB_, G_) do { constexpr int NT_ = NQ_ == 1 ? 256 : 512; \
-          if (rows == 8) { \
-            if (OMK_SET_MAX_DYN_SMEM((norm_linear_mfma_kernel<TW_, TR_, NQ_, RM_, NB_, G_, NT_, 8>), msmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", msmem); \
-            OMK_LAUNCH((norm_linear_mfma_kernel<TW_, TR_, NQ_, RM_, NB_, G_, NT_, 8>), mgrid, dim3(NT_), msmem, stream, a); \
-          } else { \
-            if (OMK_SET_MAX_DYN_SMEM((norm_linear_mfma_kernel<TW_, TR_, NQ_, RM_, NB_, G_, NT_, 16>), msmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", msmem); \
-            OMK_LAUNCH((norm_linear_mfma_kernel<TW_, TR_, NQ_, RM_, NB_, G_, NT_, 16>), mgrid, dim3(NT_), msmem, stream, a); } } while (0)
-#define NLM_GO(TW_, TR_, NQ_, RM_, NB_) do { if (gate) NLM_G(TW_, TR_, NQ_, RM_, NB_, true); else NLM_G(TW_, TR_, NQ_, RM_, NB_, false); } while (0)
-#define NLM_B(TW_, TR_, NQ_, RM_) do { if (nb == 2) NLM_GO(TW_, TR_, NQ_, RM_, 2); else if (nb == 4) NLM_GO(TW_, TR_, NQ_, RM_, 4); else NLM_GO(TW_, TR_, NQ_, RM_, 8); } while (0)
-#define NLM_R(TW_, TR_, NQ_) do { if (a.R > 0) NLM_B(TW_, TR_, NQ_, 8); else NLM_B(TW_, TR_, NQ_, 0); } while (0)
-#define NLM_Q(TW_, TR_) do { if (nq == 1) NLM_R(TW_, TR_, 1); else if (nq == 2) NLM_R(TW_, TR_, 2); else NLM_R(TW_, TR_, 4); } while (0)
-#define NLM_Q2(TW_, TR_) do { if (nq == 1) NLM_R(TW_, TR_, 1); else NLM_R(TW_, TR_, 2); } while (0)
-        if (wdt == OMK_F32) NLM_Q2(float, float); else if (trdt == OMK_F32) NLM_Q(bf16_t, float); else NLM_Q(bf16_t, bf16_t);
-#undef NLM_Q2
-#undef NLM_Q
-#undef NLM_R
-#undef NLM_B
-#undef NLM_GO
-#undef NLM_G
-        return finish_launch("norm_linear");
+        const int nwv = nq == 1 ? 4 : 8, ntile = (a.Out + rows - 1) / rows, ub = cdt == OMK_F32 ? 4 : 2;
+        pl.smem = (size_t)nb * (a.In + 16 / ub) * ub + (size_t)nwv * nb * (9 + 2 * 16) * 4 + (size_t)nb * 9 * 4;
+        pl.rows = rows;
+        pl.grid = (unsigned)(ntile < wgs ? ntile : wgs);
+        return OMK_NL_FORM_MATRIX;
       }
       if (!vec_lds_ok) return fail(OMK_EUNSUPPORTED, "norm_linear: %d sequences x %d features do not fit the LDS", a.B, a.In);
       if (!vec_rows_ok) return fail(OMK_EUNSUPPORTED, "norm_linear: %d output rows are too many for the batched kernel", a.Out);
-#define NLB_G(TW_, TR_, NQ_, RM_, NB_, G_) do { \
-        if (q8) { \
-          if (OMK_SET_MAX_DYN_SMEM((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_, fp8_t>), bsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", bsmem); \
-          OMK_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_, fp8_t>), bgrid, bblock, bsmem, stream, a); \
-        } else { \
-          if (OMK_SET_MAX_DYN_SMEM((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), bsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", bsmem); \
-          OMK_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), bgrid, bblock, bsmem, stream, a); } } while (0)
-#define NLB_GO(TW_, TR_, NQ_, RM_, NB_) do { if (gate) NLB_G(TW_, TR_, NQ_, RM_, NB_, true); else NLB_G(TW_, TR_, NQ_, RM_, NB_, false); } while (0)
-#define NLB_B(TW_, TR_, NQ_, RM_) do { if (nb == 2) NLB_GO(TW_, TR_, NQ_, RM_, 2); else if (nb == 4) NLB_GO(TW_, TR_, NQ_, RM_, 4); else NLB_GO(TW_, TR_, NQ_, RM_, 8); } while (0)
-#define NLB_R(TW_, TR_, NQ_) do { if (a.R > 0) NLB_B(TW_, TR_, NQ_, 8); else NLB_B(TW_, TR_, NQ_, 0); } while (0)
-#define NLB_Q(TW_, TR_) do { if (nq == 1) NLB_R(TW_, TR_, 1); else if (nq == 2) NLB_R(TW_, TR_, 2); else NLB_R(TW_, TR_, 4); } while (0)
-      if (cdt == OMK_F32) NLB_Q(float, float);
-      else if (trdt == OMK_F32) NLB_Q(bf16_t, float);
-      else NLB_Q(bf16_t, bf16_t);
-#undef NLB_Q
-#undef NLB_R
-#undef NLB_B
-#undef NLB_GO
-#undef NLB_G
-      return finish_launch("norm_linear");
+      pl.smem = bsmem;
+      pl.grid = (unsigned)((nw_ + NL_THREADS / 64 - 1) / (NL_THREADS / 64));
+      return OMK_NL_FORM_BATCHED;
     }
     if (a.B > 1) return fail(OMK_EUNSUPPORTED, "norm_linear: batch %d needs the uniform-dtype kernel (one dtype, in_features 1024 / 2048 / 4096)", a.B);
     if (fast) {
@@ -1220,24 +1246,9 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
       const int nw_ = (a.Out + rw * k - 1) / (rw * k);
       a.nbatch = k;
       if (k * rw <= 64) {
-        dim3 fgrid((unsigned)((nw_ + NL_THREADS / 64 - 1) / (NL_THREADS / 64))), fblock(NL_THREADS);
-        const size_t fsmem = ((size_t)a.In + 8 * (NL_THREADS / 64)) * 4;
-#define NLF_GO(TW_, TR_, NQ_, RM_) do { \
-          if (q8) { \
-            if (OMK_SET_MAX_DYN_SMEM((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_, fp8_t>), fsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", fsmem); \
-            OMK_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_, fp8_t>), fgrid, fblock, fsmem, stream, a); \
-          } else { \
-            if (OMK_SET_MAX_DYN_SMEM((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), fsmem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", fsmem); \
-            OMK_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), fgrid, fblock, fsmem, stream, a); } } while (0)
-#define NLF_R(TW_, TR_, NQ_) do { if (a.R > 0) NLF_GO(TW_, TR_, NQ_, 8); else NLF_GO(TW_, TR_, NQ_, 0); } while (0)
-#define NLF_Q(TW_, TR_) do { if (nq == 1) NLF_R(TW_, TR_, 1); else if (nq == 2) NLF_R(TW_, TR_, 2); else NLF_R(TW_, TR_, 4); } while (0)
-        if (cdt == OMK_F32) NLF_Q(float, float);
-        else if (trdt == OMK_F32) NLF_Q(bf16_t, float);
-        else NLF_Q(bf16_t, bf16_t);
-#undef NLF_Q
-#undef NLF_R
-#undef NLF_GO
-        return finish_launch("norm_linear");
+        pl.grid = (unsigned)((nw_ + NL_THREADS / 64 - 1) / (NL_THREADS / 64));
+        pl.smem = ((size_t)a.In + 8 * (NL_THREADS / 64)) * 4;
+        return OMK_NL_FORM_FAST;
       }
     }
     if (q8) return fail(OMK_EUNSUPPORTED, "norm_linear: %d output rows are too many for the fp8 kernel", a.Out);
@@ -1246,12 +1257,87 @@ extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
   // two workgroups per CU; small matrices get one wave per row pair
   const int ncu = 2 * cu_count();
   const int want = (a.Out + 7) / 8;   // workgroups if every wave took exactly one row pair
-  dim3 grid((unsigned)(want < ncu ? want : ncu)), block(NL_THREADS);
-#define NL_GO(TW_, NB_) do { if (OMK_SET_MAX_DYN_SMEM((norm_linear_kernel<TW_>), smem)) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", smem); \
-    OMK_LAUNCH((norm_linear_kernel<TW_>), grid, block, smem, stream, a); } while (0)
-#define NL_NB(TW_) NL_GO(TW_, 1)
-  if (wdt == OMK_F32) NL_NB(float); else if (wdt == OMK_BF16) NL_NB(bf16_t); else NL_NB(f16_t);
-#undef NL_NB
-#undef NL_GO
+  pl.grid = (unsigned)(want < ncu ? want : ncu);
+  pl.smem = ((size_t)a.In + (size_t)NL_MAXR * (NL_THREADS / 64)) * 4;
+  return OMK_NL_FORM_GENERIC;
+}
+
+extern "C" int omk_norm_linear_form(const OmkNormLinear* p) {
+  NlPlan pl;
+  return nl_plan(p, pl);
+}
+
+// one launch: the dynamic LDS limit raised, then the kernel
+#define NL_LAUNCH(K_, grid_, block_, smem_) do { \
+    if (OMK_SET_MAX_DYN_SMEM((K_), (smem_))) return fail(OMK_ELAUNCH, "norm_linear: cannot raise dynamic LDS to %zu", (size_t)(smem_)); \
+    OMK_LAUNCH((K_), dim3(grid_), dim3(block_), (smem_), stream, a); } while (0)
+
+extern "C" int omk_norm_linear(const OmkNormLinear* p, omk_stream stream) {
+  NlPlan pl;
+  const int form = nl_plan(p, pl);
+  if (form < 0) return form;
+  if (pl.empty) return OMK_OK;
+  const NlArgs& a = pl.a;
+  const int wdt = pl.wdt, cdt = pl.cdt, trdt = pl.trdt, nq = pl.nq, nb = pl.nb, rows = pl.rows;
+  const bool q8 = pl.q8, gate = pl.gate;
+  if (form == OMK_NL_FORM_MATRIX) {
+#define NLM_G(TW_, TR_, NQ_, RM_, NB_, G_, TQ_) do { constexpr int NT_ = NQ_ == 1 ? 256 : 512; \
+      if (rows == 8) NL_LAUNCH((norm_linear_mfma_kernel<TW_, TR_, NQ_, RM_, NB_, G_, NT_, 8, TQ_>), pl.grid, NT_, pl.smem); \
+      else NL_LAUNCH((norm_linear_mfma_kernel<TW_, TR_, NQ_, RM_, NB_, G_, NT_, 16, TQ_>), pl.grid, NT_, pl.smem); } while (0)
+#define NLM_GO(TW_, TR_, NQ_, RM_, NB_, TQ_) do { if (gate) NLM_G(TW_, TR_, NQ_, RM_, NB_, true, TQ_); else NLM_G(TW_, TR_, NQ_, RM_, NB_, false, TQ_); } while (0)
+    // (fp8 with a gate: the residual type is not looked at -- one instantiation for both)
+#define NLM_GO8(TR_, NQ_, RM_, NB_) do { if (gate) NLM_G(bf16_t, bf16_t, NQ_, RM_, NB_, true, fp8_t); else NLM_G(bf16_t, TR_, NQ_, RM_, NB_, false, fp8_t); } while (0)
+#define NLM_B(TW_, TR_, NQ_, RM_) do { \
+      if (q8) { if (nb == 2) NLM_GO8(TR_, NQ_, RM_, 2); else if (nb == 4) NLM_GO8(TR_, NQ_, RM_, 4); else NLM_GO8(TR_, NQ_, RM_, 8); } \
+      else if (nb == 2) NLM_GO(TW_, TR_, NQ_, RM_, 2, TW_); else if (nb == 4) NLM_GO(TW_, TR_, NQ_, RM_, 4, TW_); else NLM_GO(TW_, TR_, NQ_, RM_, 8, TW_); } while (0)
+#define NLM_R(TW_, TR_, NQ_) do { if (a.R > 0) NLM_B(TW_, TR_, NQ_, 8); else NLM_B(TW_, TR_, NQ_, 0); } while (0)
+#define NLM_Q(TW_, TR_) do { if (nq == 1) NLM_R(TW_, TR_, 1); else if (nq == 2) NLM_R(TW_, TR_, 2); else NLM_R(TW_, TR_, 4); } while (0)
+#define NLM_Q2(TW_, TR_) do { if (nq == 1) NLM_R(TW_, TR_, 1); else NLM_R(TW_, TR_, 2); } while (0)
+    if (cdt == OMK_F32) NLM_Q2(float, float); else if (trdt == OMK_F32) NLM_Q(bf16_t, float); else NLM_Q(bf16_t, bf16_t);
+#undef NLM_Q2
+#undef NLM_Q
+#undef NLM_R
+#undef NLM_B
+#undef NLM_GO8
+#undef NLM_GO
+#undef NLM_G
+    return finish_launch("norm_linear");
+  }
+  if (form == OMK_NL_FORM_BATCHED) {
+#define NLB_G(TW_, TR_, NQ_, RM_, NB_, G_) do { \
+      if (q8) NL_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_, fp8_t>), pl.grid, NL_THREADS, pl.smem); \
+      else NL_LAUNCH((norm_linear_batched_kernel<TW_, TR_, NQ_, RM_, NB_, G_>), pl.grid, NL_THREADS, pl.smem); } while (0)
+#define NLB_GO(TW_, TR_, NQ_, RM_, NB_) do { if (gate) NLB_G(TW_, TR_, NQ_, RM_, NB_, true); else NLB_G(TW_, TR_, NQ_, RM_, NB_, false); } while (0)
+#define NLB_B(TW_, TR_, NQ_, RM_) do { if (nb == 2) NLB_GO(TW_, TR_, NQ_, RM_, 2); else if (nb == 4) NLB_GO(TW_, TR_, NQ_, RM_, 4); else NLB_GO(TW_, TR_, NQ_, RM_, 8); } while (0)
+#define NLB_R(TW_, TR_, NQ_) do { if (a.R > 0) NLB_B(TW_, TR_, NQ_, 8); else NLB_B(TW_, TR_, NQ_, 0); } while (0)
+#define NLB_Q(TW_, TR_) do { if (nq == 1) NLB_R(TW_, TR_, 1); else if (nq == 2) NLB_R(TW_, TR_, 2); else NLB_R(TW_, TR_, 4); } while (0)
+    if (cdt == OMK_F32) NLB_Q(float, float);
+    else if (trdt == OMK_F32) NLB_Q(bf16_t, float);
+    else NLB_Q(bf16_t, bf16_t);
+#undef NLB_Q
+#undef NLB_R
+#undef NLB_B
+#undef NLB_GO
+#undef NLB_G
+    return finish_launch("norm_linear");
+  }
+  if (form == OMK_NL_FORM_FAST) {
+#define NLF_GO(TW_, TR_, NQ_, RM_) do { \
+      if (q8) NL_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_, fp8_t>), pl.grid, NL_THREADS, pl.smem); \
+      else NL_LAUNCH((norm_linear_fast_kernel<TW_, TR_, NQ_, RM_>), pl.grid, NL_THREADS, pl.smem); } while (0)
+#define NLF_R(TW_, TR_, NQ_) do { if (a.R > 0) NLF_GO(TW_, TR_, NQ_, 8); else NLF_GO(TW_, TR_, NQ_, 0); } while (0)
+#define NLF_Q(TW_, TR_) do { if (nq == 1) NLF_R(TW_, TR_, 1); else if (nq == 2) NLF_R(TW_, TR_, 2); else NLF_R(TW_, TR_, 4); } while (0)
+    if (cdt == OMK_F32) NLF_Q(float, float);
+    else if (trdt == OMK_F32) NLF_Q(bf16_t, float);
+    else NLF_Q(bf16_t, bf16_t);
+#undef NLF_Q
+#undef NLF_R
+#undef NLF_GO
+    return finish_launch("norm_linear");
+  }
+  if (wdt == OMK_F32) NL_LAUNCH((norm_linear_kernel<float>), pl.grid, NL_THREADS, pl.smem);
+  else if (wdt == OMK_BF16) NL_LAUNCH((norm_linear_kernel<bf16_t>), pl.grid, NL_THREADS, pl.smem);
+  else NL_LAUNCH((norm_linear_kernel<f16_t>), pl.grid, NL_THREADS, pl.smem);
   return finish_launch("norm_linear");
 }
+#undef NL_LAUNCH

@@ -95,6 +95,35 @@ __device__ __forceinline__ float fp8e4m3_to_f32(uint32_t word, int i) {
 #endif
 }
 
+// ---- OCP e4m3fn -> bf16: a dword of four codes -> two packed bf16 pairs (lo = codes 0 | 1, hi = codes 2 | 3; the lower code in the lower
+// half).  Exact as well: 3 mantissa bits into 7, the subnormals m * 2^-9 are bf16 normals; the NaN codes give a quiet NaN.  gfx950: one
+// v_cvt_scalef32_pk_bf16_fp8 per pair with the scale 1.0 (OMK_FP8_BF16_DIRECT=0 at compile time: v_cvt_pk_f32_fp8 + v_cvt_pk_bf16_f32, the A/B).
+#ifndef OMK_FP8_BF16_DIRECT
+#define OMK_FP8_BF16_DIRECT 1
+#endif
+__device__ __forceinline__ void fp8e4m3x4_to_bf16x2(uint32_t word, uint32_t& lo, uint32_t& hi) {
+#ifdef OMK_EMU
+  uint32_t h[4];
+  for (int i = 0; i < 4; i++) {
+    const uint32_t b = (word >> (8 * i)) & 0xffu, s = (b & 0x80u) << 8, e = (b >> 3) & 15u, m = b & 7u;
+    if (e == 15u && m == 7u) h[i] = s | 0x7fc0u;                              // NaN
+    else if (e != 0u) h[i] = s | ((e + 120u) << 7) | (m << 4);                 // (1 + m / 8) * 2^(e - 7): exponent e - 7 + 127
+    else if (m >= 4u) h[i] = s | (120u << 7) | ((m - 4u) << 5);                // m * 2^-9 = (1 + (m - 4) / 4) * 2^-7
+    else if (m >= 2u) h[i] = s | (119u << 7) | ((m - 2u) << 6);                //          = (1 + (m - 2) / 2) * 2^-8
+    else h[i] = s | (m ? (118u << 7) : 0u);                                    //          = 2^-9, or a signed zero
+  }
+  lo = h[0] | (h[1] << 16);
+  hi = h[2] | (h[3] << 16);
+#elif OMK_FP8_BF16_DIRECT
+  lo = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(word, 1.0f, false));
+  hi = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(word, 1.0f, true));
+#else
+  const f32x2 p0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)word, false), p1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)word, true);
+  lo = pack_bf16x2(p0[0], p0[1]);
+  hi = pack_bf16x2(p1[0], p1[1]);
+#endif
+}
+
 // c + a.lo * b.lo + a.hi * b.hi on packed bf16 pairs (v_dot2c_f32_bf16 on gfx950)
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
 #ifdef OMK_EMU

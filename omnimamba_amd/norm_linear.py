@@ -7,7 +7,8 @@ autograd); one to eight sequences per call.  Callers fall back to the unfused op
 
 Weight-only fp8 (ABI 11): `weight` may be a `torch.float8_e4m3fn` matrix with `weight_scale`, one fp32 scale per output row
 (`omnimamba_amd.quant.quantize_rows_e4m3`): out = rstd * (scale[row] * sum_i decode(W[row, i]) u_i + LoRA term).  Half the bytes of a
-bf16 weight stream, a quarter of an fp32 one; everything else of the call keeps the dtype of `x` (fp32 or bf16).
+bf16 weight stream, a quarter of an fp32 one; everything else of the call keeps the dtype of `x` (fp32 or bf16).  At two to eight sequences
+under bf16 activations the codes run on the matrix pipe like a bf16 weight (ABI 12); `form(...)` tells which kernel a call takes.
 """
 from __future__ import annotations
 
@@ -17,6 +18,10 @@ from . import _capi as K
 from ._lib import get_lib, require_device, slot_indices
 
 MAX_BATCH = 8     # sequences per call; larger decode batches take the separate ops
+# what `form` answers (omk_norm_linear_form): one sequence with run-time dtypes / one sequence, uniform dtype / two to eight sequences on the
+# vector pipe / two to eight sequences on the matrix pipe; a negative value is the omk_status of a call the library refuses
+GENERIC, FAST, BATCHED, MATRIX = K.NL_FORM_GENERIC, K.NL_FORM_FAST, K.NL_FORM_BATCHED, K.NL_FORM_MATRIX
+FORM_NAMES = {GENERIC: "generic", FAST: "fast", BATCHED: "batched", MATRIX: "matrix"}
 
 
 def _uniform(weight, *others) -> bool:
@@ -102,6 +107,27 @@ def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=No
     with any number of rows; a negative index marks a padding sequence -- its conv state is neither read nor written and its conv
     columns of out are zeros.  The values are never read on the host.
     weight_scale (out,) fp32: the per-row scale of a `float8_e4m3fn` weight (required with one, refused without)."""
+    lib, p, x, out, ro = _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, group_size, norm_before_gate, lora_a, lora_b,
+                                 lora_scale, out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale)
+    K.run(lib, "omk_norm_linear", p, x)
+    return out if ro is None else (out, ro)
+
+
+def form(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=None, residual_out_dtype=None, z=None,
+         group_size=None, norm_before_gate=False, lora_a=None, lora_b=None, lora_scale=0.0, out_dtype=None,
+         conv_state=None, conv_weight=None, conv_bias=None, conv_offset=0, conv_silu=True, conv_state_indices=None,
+         weight_scale=None) -> int:
+    """Which kernel `norm_linear` runs for these arguments: GENERIC, FAST, BATCHED or MATRIX, or the negative omk_status with which the
+    library refuses the call.  The launch's own decision (omk_norm_linear_form); nothing is launched."""
+    import ctypes
+    lib, p, _, _, _ = _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, group_size, norm_before_gate, lora_a, lora_b,
+                              lora_scale, out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale)
+    return int(lib.omk_norm_linear_form(ctypes.byref(p)))
+
+
+def _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, group_size, norm_before_gate, lora_a, lora_b, lora_scale,
+            out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale):
+    """The call's descriptor (and its freshly allocated outputs): what `norm_linear` hands to the library and `form` asks about."""
     lib = get_lib()
     require_device(lib, x, weight, bias, norm_weight, residual, z, lora_a, lora_b, conv_state, conv_weight, conv_bias, conv_state_indices,
                    weight_scale)
@@ -121,5 +147,5 @@ def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=No
                      group_size=0 if group_size is None else int(group_size), conv_offset=int(conv_offset), eps=float(eps),
                      lora_scale=float(lora_scale), norm_before_gate=int(bool(norm_before_gate)), conv_silu=int(bool(conv_silu)),
                      conv_state_indices=K.T(idx), weight_scale=K.T(weight_scale))
-    K.run(lib, "omk_norm_linear", p, x)
-    return out if ro is None else (out, ro)
+    p._keep = (x, z, idx)   # (the descriptor holds raw pointers: the copies made here live as long as it does)
+    return lib, p, x, out, ro

@@ -16,6 +16,31 @@ from omnimamba_amd.stack import OmniMambaLM, StackConfig  # noqa: E402
 from omnimamba_amd.train import Stage2Step, TrainConfig, init_distributed, synthetic_batch, wrap_ddp  # noqa: E402
 
 
+class _ProjectionForms:
+    """Which kernel each fused decode-step projection took (norm_linear.form), by projection and number of sequences: active around a
+    warm-up run, asks once per (projection, sequences) and launches nothing itself.  -> {"in_proj": {"8": "matrix"}, ...}"""
+
+    def __enter__(self):
+        from omnimamba_amd import norm_linear as NL
+        self.NL, self.real, self.forms = NL, NL.norm_linear, {}
+
+        def logging(x, *a, **k):
+            role, nseq = ("out_proj" if k.get("z") is not None else "in_proj"), str(x.shape[0])
+            if nseq not in self.forms.setdefault(role, {}):
+                f = NL.form(x, *a, **k)
+                self.forms[role][nseq] = NL.FORM_NAMES.get(f, f"status {f}")
+            return self.real(x, *a, **k)
+
+        NL.norm_linear = logging
+        return self
+
+    def __exit__(self, *exc):
+        self.NL.norm_linear = self.real
+
+    def sorted(self):
+        return {r: dict(sorted(d.items(), key=lambda kv: int(kv[0]))) for r, d in sorted(self.forms.items())}
+
+
 def bench_decode(args, dev):
     """configs[2]: T2I autoregressive decode, 72-token prompt + 256 image tokens, greedy, hipGraph replay, fp32 weights
     (the reference inference scripts never cast the model: scripts/inference_t2i.py:21-26)."""
@@ -33,8 +58,10 @@ def bench_decode(args, dev):
     ids = torch.zeros(B, P, dtype=torch.long, device=dev)
     emb = torch.randn(B, P, cfg.d_model, device=dev, dtype=wdt) * 0.02 + model.backbone.pos_embed[:, :P].to(wdt)
     out = {}
+    forms = _ProjectionForms()
     for cg in (True, False) if args.eager_too else (True,):
-        decode(ids, emb, model, P + new, top_k=1, task="t2i", cg=cg)          # warm-up (captures the graph)
+        with forms:
+            decode(ids, emb, model, P + new, top_k=1, task="t2i", cg=cg)      # warm-up (captures the graph)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         seq = decode(ids, emb, model, P + new, top_k=1, task="t2i", cg=cg)
@@ -55,7 +82,7 @@ def bench_decode(args, dev):
                       "ms_per_token": round(ms_tok, 3), "tokens_per_s": round(B * new / out["graph"], 1),
                       "weights_GBs": round(n_bytes / (ms_tok * 1e-3) / 1e9, 1), "params": n_param,
                       "dtype": "bf16" if wdt == torch.bfloat16 else "f32", "decode_projections": "fp8_e4m3" if quant == "fp8" else None,
-                      "eager_ms_per_token": round(out["eager"] / new * 1e3, 3) if "eager" in out else None}), flush=True)
+                      "projection_forms": forms.sorted(), "eager_ms_per_token": round(out["eager"] / new * 1e3, 3) if "eager" in out else None}), flush=True)
 
 
 def bench_decode_mmu(args, dev):
@@ -190,7 +217,8 @@ def bench_decode_mmu_batch(args, dev):
         # warm-ups: the sequential step graph at the largest max_length (later calls reuse it), every bucket of the ragged step
         if not args.no_sequential:
             model.mmu_generate(feats[0], qs[0], max_length=max(lens), cg=True)
-        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
+        with _ProjectionForms() as forms:
+            model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
         torch.cuda.synchronize()
         seq, t_seq = None, None
         if not args.no_sequential:
@@ -212,7 +240,7 @@ def bench_decode_mmu_batch(args, dev):
         assert got == [4 + q.shape[1] + n for q, n in zip(qs, new)], got
         same = None if seq is None else sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
         print(json.dumps({"workload": "OmniMamba-1.3B MMU continuous batching", "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
-                          "decode_projections": "fp8_e4m3" if quant == "fp8" else None,
+                          "decode_projections": "fp8_e4m3" if quant == "fp8" else None, "projection_forms": forms.sorted(),
                           "requests": len(qs), "generated_tokens": n_tok, "max_batch": args.max_batch, **opts,
                           "sequential_s": None if t_seq is None else round(t_seq, 3), "ragged_s": round(t_rag, 3),
                           "ragged_s_all": [round(t, 3) for t in t_rags],
