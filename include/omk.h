@@ -24,11 +24,11 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 12
+#define OMK_ABI_VERSION 13
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
-typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices; ABI 10: per-row lengths */,
+typedef enum { OMK_F32 = 0, OMK_BF16 = 1, OMK_F16 = 2, OMK_U8 = 3 /* masks only */, OMK_I32 = 4 /* ABI 8: slot indices; ABI 10 / 13: per-row lengths */,
                OMK_F8E4M3 = 5 /* ABI 11: OCP e4m3fn (bias 7, max 448, 0x7F / 0xFF NaN, no infinities; NOT the fnuz form) -- the weight of
                                  omk_norm_linear only, together with OmkNormLinear.weight_scale */ } omk_dtype;
 typedef void* omk_stream; /* hipStream_t */
@@ -164,6 +164,11 @@ typedef struct {
    * and the row's out is zeros.  Two rows with the same non-negative index: undefined result.  Indices are read on the
    * device only (graph-capturable).  Absent: conv_state is (B, C, S) and row b is state row b. */
   OmkTensor conv_state_indices;
+  /* ABI 13, optional int32 (B): row b applies only its first n_b = clamp(seq_lens[b], 0, T) tokens (the rows of a right-padded batch of
+   * follow-up turns).  Afterwards its state holds the last S values of (old state ++ x[b, :, :n_b]), out[b, :, t] for t < n_b is what a
+   * call on that row alone with T = n_b gives, bit for bit, and out[b, :, t] = 0 for t >= n_b.  n_b == 0: the row's state is neither
+   * read nor written.  Read on the device only (graph-capturable).  Absent: every row applies T tokens, as in ABI 12. */
+  OmkTensor seq_lens;
 } OmkConv1dUpdate;
 int omk_causal_conv1d_update(const OmkConv1dUpdate* p, omk_stream stream);
 
@@ -212,6 +217,11 @@ typedef struct {
    * exceed B; a negative index (or one >= the pool's rows) marks a padding row: no state is read or written and its T outputs
    * are zeros.  Absent: state is (B, H, P, N) and row b is state row b. */
   OmkTensor state_batch_indices;
+  /* ABI 13, optional int32 (B): row b applies only its first n_b = clamp(seq_lens[b], 0, T) tokens (the rows of a right-padded batch of
+   * follow-up turns).  Its state is stored once, after token n_b - 1; out[b, t] for t < n_b and the state are what a call on that row
+   * alone with T = n_b gives, bit for bit; out[b, t] = 0 for n_b <= t < T.  n_b == 0: the row's state is neither read nor written
+   * (what a padding slot does).  Read on the device only (graph-capturable).  Absent: every row applies T tokens, as in ABI 12. */
+  OmkTensor seq_lens;
 } OmkStateExtend;
 int omk_selective_state_extend(const OmkStateExtend* p, omk_stream stream);
 

@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 12
+OMK_ABI_VERSION = 13
 OMK_MAX_DIMS = 5
 OMK_EUNSUPPORTED = -4   # omk_status: the kernel does not take this call (the caller may have another way)
 NL_FORM_GENERIC, NL_FORM_FAST, NL_FORM_BATCHED, NL_FORM_MATRIX = 0, 1, 2, 3   # omk_norm_linear_form (ABI 12)
@@ -62,11 +62,12 @@ Conv1dFwd = _S("OmkConv1dFwd", [(n, _t) for n in ("x", "weight", "bias", "initia
                + [("silu", _i), ("seq_lens", _t)])   # ABI 10: per-row lengths of a right-padded batch
 Conv1dBwd = _S("OmkConv1dBwd", [(n, _t) for n in ("x", "weight", "bias", "initial_states", "dout", "dx", "dweight",
                                                   "dbias", "dinitial_states")] + [("silu", _i), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)])
-Conv1dUpdate = _S("OmkConv1dUpdate", [(n, _t) for n in ("x", "conv_state", "weight", "bias", "out")] + [("silu", _i), ("conv_state_indices", _t)])
+Conv1dUpdate = _S("OmkConv1dUpdate", [(n, _t) for n in ("x", "conv_state", "weight", "bias", "out")] + [("silu", _i), ("conv_state_indices", _t),
+                                                                                                        ("seq_lens", _t)])   # ABI 13: per-row token counts
 StateUpdate = _S("OmkStateUpdate", [(n, _t) for n in ("state", "x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "out")]
                  + [("dt_softplus", _i), ("state_batch_indices", _t)])
 StateExtend = _S("OmkStateExtend", [(n, _t) for n in ("state", "x", "dt", "A", "Bm", "Cm", "D", "z", "dt_bias", "out")]
-                 + [("dt_softplus", _i), ("state_batch_indices", _t)])   # ABI 9: OmkStateUpdate with a token dimension
+                 + [("dt_softplus", _i), ("state_batch_indices", _t), ("seq_lens", _t)])   # ABI 9: OmkStateUpdate with a token dimension; ABI 13: per-row token counts
 SelScanFwd = _S("OmkSelScanFwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm", "D", "z", "delta_bias", "out",
                                                     "last_state", "pass_states")] + [("delta_softplus", _i)])
 SelScanBwd = _S("OmkSelScanBwd", [(n, _t) for n in ("u", "delta", "A", "Bm", "Cm", "D", "z", "delta_bias", "dout", "du",

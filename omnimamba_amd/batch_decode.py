@@ -16,6 +16,10 @@ Ragged prefill (both off by default).  ``prefill_batch`` > 1: the plain requests
 same moment are admitted by ONE right-padded prefill (``InferenceParams.seq_lens``: the kernels leave every row's states as after its
 own length) into the first rows of a staging cache, which are then copied into their slots.  ``prefill_bucket`` > 0 with ``cg``: a
 prompt longer than the exact-length capture limit replays a captured batch-1 prefill of its length rounded up to the bucket.
+
+Ragged extend (off by default).  ``extend_batch`` > 1: the continued requests at the head of the queue that find a free slot at the same
+moment are admitted by ONE right-padded extend straight on their pool slots (``InferenceParams.state_indices`` + ``extend_lens``:
+every row's states end up as after its own pending id and turn).
 """
 from __future__ import annotations
 
@@ -185,6 +189,33 @@ def _extend(model, c, slot, state, emb, task):
     return out.mmu_logits.squeeze(1)
 
 
+def _extend_group(model, c, slots, states, embs, task):
+    """ONE right-padded extend of several conversations -> logits (len(embs), vocab), row j read at the last position of turn j.  The
+    states are copied into the pool rows `slots`, which the pass then extends in place through InferenceParams.state_indices; row j is
+    [states[j].pending_id] + embs[j] with the position rows from states[j].seqlen on added here (as _extend), zeros behind it, and
+    InferenceParams.extend_lens makes every row's states those after its own length."""
+    for st in states:
+        if st.task != task or st.dtype != c["dtype"]:
+            raise ValueError(f"decode_ragged: a {st.task} / {st.dtype} state cannot continue in a {task} / {c['dtype']} cache")
+    g, dev = len(embs), embs[0].device
+    dst = [t[s:s + 1] for s in slots for k in sorted(c["pool"]) for t in c["pool"][k]]
+    torch._foreach_copy_(dst, [t for st in states for pair in st.layers for t in pair])
+    lens_h = [1 + e.shape[1] for e in embs]
+    pend = model.get_input_embeddings()(torch.tensor([[st.pending_id] for st in states], dtype=torch.long, device=dev))   # (g, 1, d)
+    buf = torch.zeros(g, max(lens_h), embs[0].shape[-1], dtype=embs[0].dtype, device=dev)
+    pos = torch.zeros(g, max(lens_h), dtype=torch.long)
+    for j, (st, e) in enumerate(zip(states, embs)):
+        h = torch.cat([pend[j:j + 1].to(e.dtype), e], dim=1)
+        buf[j, :lens_h[j]].copy_((h + model.backbone.mmu_pos_embed[:, st.seqlen: st.seqlen + lens_h[j]].to(h.dtype))[0])
+        pos[j, :lens_h[j]] = torch.arange(st.seqlen, st.seqlen + lens_h[j])
+    # seqlen_offset > 0 selects the extend branch; its value is not read.  position_ids tells the stack that the position rows are in
+    ip = InferenceParams(max_seqlen=c["max_seqlen"], max_batch_size=g, seqlen_offset=1, key_value_memory_dict=c["pool"],
+                         state_indices=torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True),
+                         extend_lens=torch.tensor(lens_h, dtype=torch.int32).to(dev, non_blocking=True))
+    out = model(None, buf, position_ids=pos.to(dev, non_blocking=True), task=task, inference_params=ip, num_last_tokens=1)
+    return out.mmu_logits.squeeze(1)
+
+
 def _save(c, slot, seqlen, pending_id, task):
     return DecodeState(layers=[tuple(t[slot:slot + 1].clone() for t in c["pool"][k]) for k in sorted(c["pool"])], seqlen=seqlen,
                        pending_id=pending_id, task=task, dtype=c["dtype"])
@@ -192,7 +223,7 @@ def _save(c, slot, seqlen, pending_id, task):
 
 @torch.inference_mode()
 def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
-                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0):
+                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1):
     """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
     generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
     model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
@@ -207,7 +238,12 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     prefill_batch > 1: up to that many plain requests (not continued ones) that are queued while as many slots are free are admitted
     by one right-padded prefill (_prefill_group); admission stays FIFO, a continued request ends the group before it, and nothing
     waits for a larger group.  prefill_bucket > 0 (with cg): prompts longer than generation.PREFILL_GRAPH_MAX_LEN replay a captured
-    prefill of their length rounded up to a multiple of it (_prefill).  With both at their defaults nothing changes."""
+    prefill of their length rounded up to a multiple of it (_prefill).  With both at their defaults nothing changes.
+
+    extend_batch > 1: up to that many continued requests at the head of the queue that find a free slot at the same moment are admitted
+    by one right-padded extend on their slots (_extend_group); admission stays FIFO, a plain request ends the group before it, nothing
+    waits for a larger group, and the position-table IndexError of every request of the group is raised before anything is launched.  A
+    group of one, or one whose turns are all empty (padded length 1: a decode step), is admitted request by request.  1: off."""
     n = len(requests)
     if n == 0:
         return ([], []) if return_states else []
@@ -218,6 +254,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
         raise ValueError("decode_ragged: max_batch must be >= 1")
     if prefill_batch < 1 or prefill_bucket < 0:
         raise ValueError("decode_ragged: prefill_batch must be >= 1 and prefill_bucket >= 0")
+    if extend_batch < 1:
+        raise ValueError("decode_ragged: extend_batch must be >= 1")
     for r in requests:
         if len(r) not in (2, 3):
             raise ValueError("decode_ragged: every request is (input_ids, input_embeddings) or (input_ids, input_embeddings, state)")
@@ -261,6 +299,10 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             grp = []                                           # the plain requests at the head of the queue that find a slot now
             while prefill_batch > 1 and len(grp) < min(prefill_batch, len(free), len(queue)) and len(requests[queue[len(grp)]]) == 2:
                 grp.append(queue[len(grp)])
+            xgrp = []                                          # ... and the continued ones (a request is one or the other)
+            while (extend_batch > 1 and len(xgrp) < min(extend_batch, len(free), len(queue))
+                   and len(requests[queue[len(xgrp)]]) == 3):
+                xgrp.append(queue[len(xgrp)])
             if len(grp) > 1:
                 for _ in grp:
                     queue.popleft()
@@ -268,6 +310,18 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
                 toks = draw(_prefill_group(model, c, slots, [requests[i][1] for i in grp], task))   # (len(grp),)
                 toks_h = toks.tolist() if check_eos else [None] * len(grp)
                 admitted = [(i, s, requests[i][1].shape[1], toks[j:j + 1], toks_h[j]) for j, (i, s) in enumerate(zip(grp, slots))]
+            elif len(xgrp) > 1 and any(requests[i][1].shape[1] > 0 for i in xgrp):   # (all turns empty: a decode step, not an extend)
+                offs = [requests[i][2].seqlen + 1 + requests[i][1].shape[1] for i in xgrp]
+                for i, off in zip(xgrp, offs):
+                    if n_pos is not None and off > n_pos:
+                        raise IndexError(f"decode_ragged: request {i} continues to position {off - 1}, outside the {task} position table of "
+                                         f"{n_pos} rows (StackConfig.{{t2i,mmu}}_positions)")
+                for _ in xgrp:
+                    queue.popleft()
+                slots = [free.pop(0) for _ in xgrp]
+                toks = draw(_extend_group(model, c, slots, [requests[i][2] for i in xgrp], [requests[i][1] for i in xgrp], task))
+                toks_h = toks.tolist() if check_eos else [None] * len(xgrp)
+                admitted = [(i, s, off, toks[j:j + 1], toks_h[j]) for j, (i, s, off) in enumerate(zip(xgrp, slots, offs))]
             else:
                 i = queue.popleft()
                 s = free.pop(0)

@@ -90,21 +90,25 @@ def causal_conv1d_fn(x, weight, bias=None, seq_idx=None, initial_states=None, re
 
 
 def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None, cache_seqlens=None,
-                         conv_state_indices=None):
+                         conv_state_indices=None, seq_lens=None):
     """x: (batch, dim) or (batch, dim, seqlen); conv_state: (batch, dim, state_len >= width-1), updated in place.
     conv_state_indices: optional (batch,) int32 (int64 is cast: one extra launch): row b rolls conv_state row
     conv_state_indices[b] of a pool with any number of rows; a negative index marks a padding row -- its state is neither read
-    nor written and its output is zeros.  The values are never read on the host (graph-capturable)."""
+    nor written and its output is zeros.  The values are never read on the host (graph-capturable).
+    seq_lens (extension): optional (batch,) int32 (int64 is cast) for x (batch, dim, seqlen), the rows of a right-padded batch of turns:
+    row b applies its first n_b = clamp(seq_lens[b], 0, seqlen) tokens only -- its state ends as the last state_len values of
+    (old state ++ x[b, :, :n_b]), out[b, :, n_b:] is zeros, a row of length 0 leaves its state untouched.  Never read on the host."""
     if cache_seqlens is not None:
         raise NotImplementedError("cache_seqlens is not on the OmniMamba path")
     lib = get_lib()
-    require_device(lib, x, conv_state, weight, bias, conv_state_indices)
+    require_device(lib, x, conv_state, weight, bias, conv_state_indices, seq_lens)
     idx = slot_indices(conv_state_indices, x.shape[0], x.device, "conv_state_indices")
+    lens = slot_indices(seq_lens, x.shape[0], x.device, "seq_lens")
     squeeze = x.dim() == 2
     x3 = x.unsqueeze(-1) if squeeze else x
     out = torch.empty_like(x3)
     if x3.numel() > 0:
         p = K.Conv1dUpdate(x=K.T(x3), conv_state=K.T(conv_state), weight=K.T(weight), bias=K.T(bias), out=K.T(out),
-                           silu=_act_flag(activation), conv_state_indices=K.T(idx))
+                           silu=_act_flag(activation), conv_state_indices=K.T(idx), seq_lens=K.T(lens))
         K.run(lib, "omk_causal_conv1d_update", p, x3)
     return out.squeeze(-1) if squeeze else out

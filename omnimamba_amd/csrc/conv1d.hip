@@ -794,20 +794,26 @@ __global__ void conv1d_dinit_kernel(ConvArgs a) {
 struct ConvUpdArgs {
   const void* x; void* state; const void* w; const void* bias; void* out;
   const int* csi;                        // ABI 8: slot of row b in the state pool (null: row b)
+  const int* lens;                       // ABI 13: tokens row b applies (null: T), clamped to 0 .. T on the device
   int64_t xsb, xsc, xsl, ssb, ssc, ssl, osb, osc, osl, wsc, wsk;
   int B, C, T, S, W, silu, xdt, sdt, wdt, bdt, pool;
 };
+// RAGGED (ABI 13, seq_lens present): the row shifts and appends by its own length nT, outputs behind it are zeros.  An instantiation of
+// its own: as a run-time branch the length cost every caller five VGPRs.
+template <bool RAGGED>
 __global__ void conv1d_update_kernel(ConvUpdArgs a) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (int64_t)a.B * a.C) return;
   const int c = (int)(g % a.C), b = (int)(g / a.C);
-  int sb = b;
-  if (a.csi) {                           // slot of this row; negative or outside the pool: a padding row, no state traffic, zeros out
-    sb = a.csi[b];
-    if (sb < 0 || sb >= a.pool) {
-      for (int t = 0; t < a.T; t++) store_rt(a.out, (int64_t)b * a.osb + (int64_t)c * a.osc + (int64_t)t * a.osl, a.xdt, 0.f);
-      return;
-    }
+  int sb = b, nT = a.T;
+  if (a.csi) sb = a.csi[b];              // slot of this row; negative or outside the pool: a padding row
+  if constexpr (RAGGED) {
+    const int n = a.lens[b];
+    nT = n < 0 ? 0 : (n < a.T ? n : a.T);
+  }
+  if (sb < 0 || sb >= a.pool || (RAGGED && nT == 0)) {   // padding row or a row of length 0: no state traffic, zeros out
+    for (int t = 0; t < a.T; t++) store_rt(a.out, (int64_t)b * a.osb + (int64_t)c * a.osc + (int64_t)t * a.osl, a.xdt, 0.f);
+    return;
   }
   float w[CONV_MAXW], win[CONV_MAXW];
   for (int k = 0; k < CONV_MAXW; k++) w[k] = k < a.W ? load_rt(a.w, (int64_t)c * a.wsc + k * a.wsk, a.wdt) : 0.f;
@@ -816,11 +822,11 @@ __global__ void conv1d_update_kernel(ConvUpdArgs a) {
   // window = last W-1 state entries
   for (int k = 0; k < CONV_MAXW; k++) win[k] = 0.f;
   for (int k = 0; k + 1 < a.W; k++) win[k] = load_rt(a.state, sbase + (int64_t)(a.S - (a.W - 1) + k) * a.ssl, a.sdt);
-  // shift the stored state left by T (S is tiny: W-1 or W)
-  if (a.T < a.S) {
-    for (int s = 0; s + a.T < a.S; s++) store_rt(a.state, sbase + (int64_t)s * a.ssl, a.sdt, load_rt(a.state, sbase + (int64_t)(s + a.T) * a.ssl, a.sdt));
+  // shift the stored state left by the row's nT tokens (S is tiny: W-1 or W)
+  if (nT < a.S) {
+    for (int s = 0; s + nT < a.S; s++) store_rt(a.state, sbase + (int64_t)s * a.ssl, a.sdt, load_rt(a.state, sbase + (int64_t)(s + nT) * a.ssl, a.sdt));
   }
-  for (int t = 0; t < a.T; t++) {
+  for (int t = 0; t < nT; t++) {
     float xv = load_rt(a.x, (int64_t)b * a.xsb + (int64_t)c * a.xsc + (int64_t)t * a.xsl, a.xdt);
     win[a.W - 1] = xv;
     float acc = bias;
@@ -828,8 +834,11 @@ __global__ void conv1d_update_kernel(ConvUpdArgs a) {
     if (a.silu) acc = silu_f(acc);
     store_rt(a.out, (int64_t)b * a.osb + (int64_t)c * a.osc + (int64_t)t * a.osl, a.xdt, acc);
     for (int k = 0; k + 1 < a.W; k++) win[k] = win[k + 1];
-    int spos = a.S - a.T + t;
+    int spos = a.S - nT + t;
     if (spos >= 0) store_rt(a.state, sbase + (int64_t)spos * a.ssl, a.sdt, xv);
+  }
+  if constexpr (RAGGED) {                // behind the row's length: zeros
+    for (int t = nT; t < a.T; t++) store_rt(a.out, (int64_t)b * a.osb + (int64_t)c * a.osc + (int64_t)t * a.osl, a.xdt, 0.f);
   }
 }
 
@@ -1019,6 +1028,8 @@ extern "C" int omk_causal_conv1d_update(const OmkConv1dUpdate* p, omk_stream str
   OMK_REQUIRE((indexed || p->conv_state.shape[0] == a.B) && p->conv_state.shape[1] == a.C && p->weight.shape[0] == a.C, "causal_conv1d_update: shape mismatch");
   OMK_REQUIRE(indices_ok(p->conv_state_indices, a.B), "causal_conv1d_update: conv_state_indices must be contiguous int32 (B)");
   a.csi = (const int*)p->conv_state_indices.data; a.pool = (int)p->conv_state.shape[0];
+  OMK_REQUIRE(indices_ok(p->seq_lens, a.B), "causal_conv1d_update: seq_lens must be contiguous int32 (B)");
+  a.lens = (const int*)p->seq_lens.data;
   OMK_REQUIRE(p->out.dtype == p->x.dtype, "causal_conv1d_update: out dtype");
   a.x = p->x.data; a.state = p->conv_state.data; a.w = p->weight.data; a.bias = p->bias.data; a.out = p->out.data;
   a.xsb = p->x.stride[0]; a.xsc = p->x.stride[1]; a.xsl = p->x.stride[2];
@@ -1029,6 +1040,7 @@ extern "C" int omk_causal_conv1d_update(const OmkConv1dUpdate* p, omk_stream str
   if ((int64_t)a.B * a.C * a.T == 0) return OMK_OK;
   int64_t n = (int64_t)a.B * a.C;
   dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  OMK_LAUNCH(conv1d_update_kernel, grid, block, 0, stream, a);
+  if (a.lens) OMK_LAUNCH(conv1d_update_kernel<true>, grid, block, 0, stream, a);
+  else OMK_LAUNCH(conv1d_update_kernel<false>, grid, block, 0, stream, a);
   return finish_launch("causal_conv1d_update");
 }

@@ -194,6 +194,7 @@ struct SeArgs {
   void* state; const void* x; const void* dt; const void* A; const void* Bm; const void* Cm; const void* D; const void* z;
   const void* dtb; void* out;
   const int* sbi;
+  const int* lens;                                    // ABI 13: tokens row b applies (null: T), clamped to 0 .. T on the device
   int64_t ssb, ssh, ssp, xsb, xst, xsh, xsp, dsb, dst, dsh, dsp, ash, asp, asn, bsb, bst, bsg, csb, cst, csg;
   int64_t Dsh, Dsp, zsb, zst, zsh, zsp, tsh, tsp, osb, ost, osh, osp;
   int B, T, H, P, N, G, softplus, xdt, dtdt, adt, ddt, tbdt, pool;
@@ -212,7 +213,16 @@ __device__ __forceinline__ float se_recur(float s, float dA, float xdt, float b)
 #endif
 }
 
-template <class TS, class TX, int LPR>
+// the number of tokens batch row b applies: seq_lens[b] clamped to 0 .. T.  Workgroup-uniform like su_slot: one scalar load.
+__device__ __forceinline__ int se_len(const SeArgs& a, int b) {
+  const int n = a.lens[b];
+  return n < 0 ? 0 : (n < a.T ? n : a.T);
+}
+
+// RAGGED (ABI 13, seq_lens present): the token loop, the prefetch ring and the tail re-reads run on the row's own length nT, outputs behind
+// it are zeros.  An instantiation of its own: as a run-time branch the length cost every caller two VGPRs and the f16-activation LPR 32
+// kernels a wave per SIMD; without seq_lens the kernel is the ABI 12 one to the register.
+template <class TS, class TX, int LPR, bool RAGGED>
 __global__ __launch_bounds__(256) void state_extend_kernel(SeArgs a) {
   constexpr int VEC = 4, RPW = 64 / LPR, RPB = RPW * 4;       // host: N == LPR * VEC
   using VT = vec_t<TX, VEC>;
@@ -226,7 +236,8 @@ __global__ __launch_bounds__(256) void state_extend_kernel(SeArgs a) {
   const int g = h / (a.H / a.G), n0 = lr * VEC;
   TX* out = (TX*)a.out + (int64_t)b * a.osb + (int64_t)h * a.osh + (int64_t)pp * a.osp;
   const int sb = su_slot(a, b);
-  if (sb < 0) {                                      // padding row: no state traffic, zeros out
+  const int nT = RAGGED ? se_len(a, b) : a.T;
+  if (sb < 0 || (RAGGED && nT == 0)) {               // padding row or a row of length 0: no state traffic, zeros out
     if (live && lr == 0)
       for (int t = 0; t < a.T; t++) out[(int64_t)t * a.ost] = from_f32<TX>(0.f);
     return;
@@ -249,7 +260,7 @@ __global__ __launch_bounds__(256) void state_extend_kernel(SeArgs a) {
     dq[j] = raw_rt_flat(a.dt, dto + (int64_t)t * a.dst, a.dtdt);
   };
 #pragma unroll
-  for (int j = 0; j < SE_PF; j++) issue(j, j < a.T ? j : a.T - 1);
+  for (int j = 0; j < SE_PF; j++) issue(j, j < nT ? j : nT - 1);
   // the per-row constants and the state row, right behind the first tokens' requests
   TS* s = (TS*)a.state + (int64_t)sb * a.ssb + (int64_t)h * a.ssh + (int64_t)pp * a.ssp + n0;
   float sv[VEC], Av[VEC];
@@ -261,7 +272,7 @@ __global__ __launch_bounds__(256) void state_extend_kernel(SeArgs a) {
   const RawElem q_dtb = raw_rt_flat(a.dtb ? a.dtb : a.dt, a.dtb ? (int64_t)h * a.tsh + (int64_t)pp * a.tsp : 0, a.dtb ? a.tbdt : a.dtdt);
   const RawElem q_D = raw_rt_flat(a.D ? a.D : a.A, a.D ? (int64_t)h * a.Dsh + (int64_t)pp * a.Dsp : 0, a.D ? a.ddt : a.adt);
   const float dtbv = cvt_rt_flat(q_dtb, a.dtb ? a.tbdt : a.dtdt), Dv = cvt_rt_flat(q_D, a.D ? a.ddt : a.adt);
-  for (int t0 = 0; t0 < a.T; t0 += SE_PF) {
+  for (int t0 = 0; t0 < nT; t0 += SE_PF) {
 #pragma unroll
     for (int j = 0; j < SE_PF; j++) {
       const int t = t0 + j;
@@ -270,9 +281,9 @@ __global__ __launch_bounds__(256) void state_extend_kernel(SeArgs a) {
       for (int i = 0; i < VEC; i++) { bv[i] = to_f32(bq[j].e[i]); cv[i] = to_f32(cq[j].e[i]); }
       const float xv = to_f32(xq[j]), zv = to_f32(zq[j]);
       float dt = cvt_rt_flat(dq[j], a.dtdt);
-      const int tn = t + SE_PF < a.T ? t + SE_PF : a.T - 1;   // clamped: the tail re-reads the last token, never past the tensors
+      const int tn = t + SE_PF < nT ? t + SE_PF : nT - 1;     // clamped: the tail re-reads the row's last token, never past it
       issue(j, tn);
-      if (t < a.T) {                                            // workgroup-uniform
+      if (t < nT) {                                             // workgroup-uniform
         if (a.dtb) dt += dtbv;
         if (a.softplus) dt = softplus_f(dt);
         const float xdt = xv * dt;
@@ -295,7 +306,11 @@ __global__ __launch_bounds__(256) void state_extend_kernel(SeArgs a) {
       }
     }
   }
-  if (live) store_vec<TS, VEC>(s, sv);              // the one rounding to the storage dtype
+  if (live) store_vec<TS, VEC>(s, sv);              // the one rounding to the storage dtype, after token nT - 1
+  if constexpr (RAGGED) {                             // behind the row's length: zeros, from the lanes that store y
+    if (live && lr == 0)
+      for (int t = nT; t < a.T; t++) out[(int64_t)t * a.ost] = from_f32<TX>(0.f);
+  }
 }
 
 }  // namespace omk
@@ -384,6 +399,8 @@ extern "C" int omk_selective_state_extend(const OmkStateExtend* p, omk_stream st
   a.H = (int)p->state.shape[1]; a.P = (int)p->state.shape[2]; a.N = (int)p->state.shape[3]; a.G = (int)p->Bm.shape[2];
   OMK_REQUIRE(indices_ok(p->state_batch_indices, a.B), "selective_state_extend: state_batch_indices must be contiguous int32 (B)");
   a.sbi = (const int*)p->state_batch_indices.data;
+  OMK_REQUIRE(indices_ok(p->seq_lens, a.B), "selective_state_extend: seq_lens must be contiguous int32 (B)");
+  a.lens = (const int*)p->seq_lens.data;
   OMK_REQUIRE(a.G > 0 && a.H % a.G == 0, "selective_state_extend: H must be a multiple of ngroups");
   auto bthp = [&](const OmkTensor& t) {
     return t.shape[0] == a.B && t.shape[1] == a.T && t.shape[2] == a.H && t.shape[3] == a.P;
@@ -423,12 +440,13 @@ extern "C" int omk_selective_state_extend(const OmkStateExtend* p, omk_stream st
                 "(got N=%d); step such states one token at a time with omk_selective_state_update", a.N);
   const int rpb = (64 / lpr) * 4;
   dim3 grid((unsigned)((int64_t)a.B * a.H * ((a.P + rpb - 1) / rpb))), block(256);
-#define SE_LAUNCH(TS, TX) do { \
-    if (lpr == 32) OMK_LAUNCH((state_extend_kernel<TS, TX, 32>), grid, block, 0, stream, a); \
-    else if (lpr == 16) OMK_LAUNCH((state_extend_kernel<TS, TX, 16>), grid, block, 0, stream, a); \
-    else if (lpr == 8) OMK_LAUNCH((state_extend_kernel<TS, TX, 8>), grid, block, 0, stream, a); \
-    else OMK_LAUNCH((state_extend_kernel<TS, TX, 4>), grid, block, 0, stream, a); } while (0)
-  OMK_DISPATCH_DTYPE(p->state.dtype, TS, OMK_DISPATCH_DTYPE(p->x.dtype, TX, SE_LAUNCH(TS, TX)));
+#define SE_LAUNCH(TS, TX, RAGGED) do { \
+    if (lpr == 32) OMK_LAUNCH((state_extend_kernel<TS, TX, 32, RAGGED>), grid, block, 0, stream, a); \
+    else if (lpr == 16) OMK_LAUNCH((state_extend_kernel<TS, TX, 16, RAGGED>), grid, block, 0, stream, a); \
+    else if (lpr == 8) OMK_LAUNCH((state_extend_kernel<TS, TX, 8, RAGGED>), grid, block, 0, stream, a); \
+    else OMK_LAUNCH((state_extend_kernel<TS, TX, 4, RAGGED>), grid, block, 0, stream, a); } while (0)
+  if (a.lens) OMK_DISPATCH_DTYPE(p->state.dtype, TS, OMK_DISPATCH_DTYPE(p->x.dtype, TX, SE_LAUNCH(TS, TX, true)));
+  else OMK_DISPATCH_DTYPE(p->state.dtype, TS, OMK_DISPATCH_DTYPE(p->x.dtype, TX, SE_LAUNCH(TS, TX, false)));
 #undef SE_LAUNCH
   return finish_launch("selective_state_extend");
 }

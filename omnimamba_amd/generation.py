@@ -30,6 +30,11 @@ class InferenceParams:
     # caches hold the states after seq_lens[b] positions of row b and the head reads row seq_lens[b] - 1; read on the device only,
     # so one captured prefill serves every length up to its buffer's.  None: every row is as long as the batch.
     seq_lens: Optional[torch.Tensor] = None
+    # ragged extend: int32 (batch,) number of valid positions of every right-padded row of an extend (seqlen_offset > 0, more than one
+    # position): row b's cached sequence continues by its first extend_lens[b] tokens, a row of length 0 keeps its states, and the head
+    # reads row extend_lens[b] - 1.  May be set together with state_indices (pool rows, non-negative and distinct).  Read on the device
+    # only.  None: every row is as long as the batch.  A batch of padded length 1 is a decode step and carries none.
+    extend_lens: Optional[torch.Tensor] = None
 
     def reset(self, max_seqlen, max_batch_size):
         self.max_seqlen = max_seqlen

@@ -5,7 +5,8 @@ models/stage2/config_mamba.py:16; called at models/stage2/block.py:117,149-150).
 
   forward(u)            training / no cache : in_proj (hipBLASLt) -> fused conv1d+SSD+gated-norm+out_proj node
   forward(u, ip, off=0) prefill with cache  : conv_state / ssm_state are fully overwritten
-  forward(u, ip, off>0) L > 1: extend       : the cached sequence continues by L tokens (a follow-up turn), states in place
+  forward(u, ip, off>0) L > 1: extend       : the cached sequence continues by L tokens (a follow-up turn), states in place;
+                                              with ip.extend_lens row b continues by its first extend_lens[b] tokens (ragged extend)
   step(u, conv, ssm)    decode              : causal_conv1d_update + selective_state_update, in place
 ``in_proj`` stays an nn.Linear attribute invoked through __call__ because the reference swaps it for its task-switched
 LoRA Linear (models/stage2/lora.py:90-106) and sets ``.task_types`` on it (mixer_seq_simple.py:368-371).
@@ -19,6 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._lib import slot_indices
 from .causal_conv1d import causal_conv1d_fn, causal_conv1d_update
 from .layernorm_gated import RMSNorm as RMSNormGated
 from . import norm_linear as NL
@@ -128,7 +130,14 @@ class Mamba2(nn.Module):
             if seq_lens is not None and inference_params.seqlen_offset > 0:
                 raise NotImplementedError("InferenceParams.seq_lens belongs to the prefill (seqlen_offset == 0): extending and stepping "
                                           "rows of different lengths is not implemented")
+            # ragged extend: int32 (batch,) lengths of right-padded follow-up turns (test caches are namespaces without the field)
+            extend_lens = getattr(inference_params, "extend_lens", None)
+            if extend_lens is not None and not (inference_params.seqlen_offset > 0 and seqlen > 1):
+                raise NotImplementedError("InferenceParams.extend_lens belongs to an extend (seqlen_offset > 0, more than one position): "
+                                          "a prefill takes seq_lens, a decode step takes neither")
             if inference_params.seqlen_offset > 0 and seqlen > 1:
+                if extend_lens is not None:
+                    return self._extend_ragged(u, batch, seqlen, seqlen_og, conv_state, ssm_state, inference_params, extend_lens)
                 return self._extend(u, batch, seqlen, seqlen_og, conv_state, ssm_state, inference_params)
             if inference_params.seqlen_offset > 0:
                 out, _, _ = self.step(u, conv_state, ssm_state, state_indices=getattr(inference_params, "state_indices", None))
@@ -240,6 +249,74 @@ class Mamba2(nn.Module):
                                                       initial_states=ssm_state, dt_softplus=True, return_final_states=True,
                                                       **dt_limit_kwargs)
             ssm_state.copy_(last_state)
+        y = y.flatten(-2)
+        if self.rmsnorm:
+            y = self.norm(y, z)
+        if d_mlp > 0:
+            y = torch.cat([F.silu(z0) * x0, y], dim=-1)
+        if seqlen_og is not None:
+            y = y.reshape(batch * seqlen, -1)
+        return self.out_proj(y)
+
+    def _extend_ragged(self, u, batch, seqlen, seqlen_og, conv_state, ssm_state, inference_params, extend_lens):
+        """_extend for right-padded rows of different lengths: row b continues its cached sequence by its first extend_lens[b] of the
+        `seqlen` tokens, and both of its caches end up as after exactly those.  Outputs at positions >= extend_lens[b] are finite and
+        unspecified.  With inference_params.state_indices the caches are the slot pool and row b is pool row state_indices[b]: the
+        indices must be non-negative and distinct (they are never read on the host, so neither is checked); a row that should do
+        nothing gets length 0, not a negative index.  The path is chosen by the PADDED length, as _extend chooses by its length:
+        short turns run causal_conv1d_update + the extend kernel straight on the (pool) states, one launch each; long ones gather the
+        rows' states, run conv and chunked scan from them with seq_lens, and copy the final states back -- a row of length 0 writes
+        back what it read."""
+        if getattr(inference_params, "seq_lens", None) is not None:
+            raise NotImplementedError("Mamba2 extend takes extend_lens: InferenceParams.seq_lens belongs to the prefill")
+        if torch.is_grad_enabled():
+            raise NotImplementedError("Mamba2 extend is an inference path (no autograd through the cached states)")
+        lens = slot_indices(extend_lens, batch, u.device, "extend_lens")
+        slots = slot_indices(getattr(inference_params, "state_indices", None), batch, u.device, "state_indices")
+        zxbcdt = linear(u, self.in_proj.weight, self.in_proj.bias) if type(self.in_proj) is nn.Linear else self.in_proj(u)
+        if seqlen_og is not None:
+            zxbcdt = zxbcdt.view(batch, seqlen, -1)
+        A = self._A_inference()
+        d_mlp = (zxbcdt.shape[-1] - 2 * self.d_ssm - 2 * self.ngroups * self.d_state - self.nheads) // 2
+        z0, x0, z, xBC, dt = torch.split(
+            zxbcdt, [d_mlp, d_mlp, self.d_ssm, self.d_ssm + 2 * self.ngroups * self.d_state, self.nheads], dim=-1)
+        xBC_t = xBC.contiguous().transpose(1, 2)      # channel-last: the conv output keeps it, B / C rows stay unit-stride
+        cw = self.conv1d.weight.squeeze(1)
+        short = seqlen <= EXTEND_SCAN_MAX_T and self.dt_limit == (0.0, float("inf")) and self.d_state in (16, 32, 64, 128)
+        if short:
+            # the cached inputs are shifted by each row's own length and its new ones appended, in place on the (pool) rows
+            xBC = causal_conv1d_update(xBC_t, conv_state, cw, self.conv1d.bias, self.activation, conv_state_indices=slots,
+                                       seq_lens=lens).transpose(1, 2)
+        else:
+            rows = None if slots is None else slots.long()
+            conv_old = conv_state if rows is None else conv_state.index_select(0, rows)
+            ssm_old = ssm_state if rows is None else ssm_state.index_select(0, rows)
+            moved = lens > 0                           # a row of length 0 keeps its states to the bit
+            conv_new = torch.empty(batch, self.d_conv, xBC_t.shape[1], dtype=xBC_t.dtype, device=u.device).transpose(1, 2)
+            xBC = causal_conv1d_fn(xBC_t, cw, self.conv1d.bias, initial_states=conv_old[..., 1:], return_final_states=True,
+                                   final_states_out=conv_new, activation=self.activation, seq_lens=lens)[0].transpose(1, 2)
+            conv_new = torch.where(moved[:, None, None], conv_new.to(conv_state.dtype), conv_old)
+            if rows is None:
+                conv_state.copy_(conv_new)
+            else:
+                conv_state.index_copy_(0, rows, conv_new)
+        x, B, C = torch.split(xBC, [self.d_ssm, self.ngroups * self.d_state, self.ngroups * self.d_state], dim=-1)
+        x = x.unflatten(-1, (self.nheads, self.headdim))
+        B, C = B.unflatten(-1, (self.ngroups, self.d_state)), C.unflatten(-1, (self.ngroups, self.d_state))
+        zh = z.unflatten(-1, (self.nheads, self.headdim)) if not self.rmsnorm else None
+        if short:
+            y = selective_state_extend(ssm_state, x, dt, A, B, C, D=self._D(), z=zh, dt_bias=self.dt_bias, dt_softplus=True,
+                                       state_batch_indices=slots, seq_lens=lens)
+        else:
+            dt_limit_kwargs = {} if self.dt_limit == (0.0, float("inf")) else dict(dt_limit=self.dt_limit)
+            y, last_state = mamba_chunk_scan_combined(x, dt, A, B, C, chunk_size=self.chunk_size, D=self._D(), z=zh, dt_bias=self.dt_bias,
+                                                      initial_states=ssm_old, dt_softplus=True, return_final_states=True,
+                                                      seq_lens=lens, **dt_limit_kwargs)
+            ssm_new = torch.where(moved[:, None, None, None], last_state.to(ssm_state.dtype), ssm_old)
+            if rows is None:
+                ssm_state.copy_(ssm_new)
+            else:
+                ssm_state.index_copy_(0, rows, ssm_new)
         y = y.flatten(-2)
         if self.rmsnorm:
             y = self.norm(y, z)

@@ -222,21 +222,22 @@ class OmniMambaPath(nn.Module):
 
     @torch.no_grad()
     def mmu_continue(self, states, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1, top_p=0.0, max_batch=8,
-                     cg=True, prefill_batch=1, prefill_bucket=0):
+                     cg=True, prefill_batch=1, prefill_bucket=0, extend_batch=1):
         """The follow-up turn of each conversation: states[i] is the DecodeState its previous turn returned (mmu_generate_batch or
         mmu_continue with states), input_ids_list[i] (1, T_i) the new turn's ids, already templated by the caller.  The conversation is
         not re-prefilled: the state takes the previous turn's last sampled id and the new ids (text only, embedded with
         embed_input_ids), then decodes.  max_length: an int or one per conversation, counted over the whole conversation's positions
         as in mmu_generate on the full prompt.  Returns (ids, states): ids[i] the new ids followed by the generated ids, states[i] the
         DecodeState for the turn after.  prefill_batch / prefill_bucket are accepted and passed on; a continued request is extended, never
-        prefilled, so they change nothing here yet."""
+        prefilled, so they change nothing here.  extend_batch > 1: up to that many conversations that find a free slot at the same moment
+        are extended by one right-padded pass (decode_ragged; off by default, DESIGN.md 4.6 says what was measured)."""
         from .batch_decode import decode_ragged
         if len(states) != len(input_ids_list):
             raise ValueError("mmu_continue: one state per conversation")
         reqs = [(q, self.llm_backbone.embed_input_ids(q), st) for st, q in zip(states, input_ids_list)]
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
                              top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=True,
-                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket)
+                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, extend_batch=extend_batch)
 
     # ---- T2I generation (omnimamba.py:311-337 minus the VQ decoder network)
     @torch.no_grad()

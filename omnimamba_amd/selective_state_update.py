@@ -47,18 +47,23 @@ def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     return out if has_heads else out.squeeze(1)
 
 
-def selective_state_extend(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, state_batch_indices=None):
+def selective_state_extend(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False, state_batch_indices=None,
+                           seq_lens=None):
     """T tokens of one turn applied to a cached state in one launch (omk_selective_state_extend): what T successive
     ``selective_state_update`` calls do, with the state read once, kept in fp32 and stored once.
     state: (batch, nheads, dim, dstate), updated IN PLACE; x, z: (batch, T, nheads, dim); dt: (batch, T, nheads[, dim]);
     A: (nheads[, dim, dstate]); B, C: (batch, T, ngroups, dstate); D, dt_bias: (nheads[, dim]).  Returns out like x.
     state_batch_indices: as in ``selective_state_update`` -- row b extends pool row state_batch_indices[b], a negative index is a
-    padding row (no state traffic, zero outputs)."""
+    padding row (no state traffic, zero outputs).
+    seq_lens: optional (batch,) int32 (int64 is cast), the rows of a right-padded batch of turns: row b applies its first
+    clamp(seq_lens[b], 0, T) tokens only -- state and out[b, :n_b] bit-identical to a call on that row alone with T = n_b, out[b, n_b:]
+    zeros, a row of length 0 leaves its state untouched.  The values are never read on the host (graph-capturable)."""
     lib = get_lib()
-    require_device(lib, state, x, dt, A, B, C, D, z, dt_bias, state_batch_indices)
+    require_device(lib, state, x, dt, A, B, C, D, z, dt_bias, state_batch_indices, seq_lens)
     if state.dim() != 4 or x.dim() != 4:
         raise ValueError("selective_state_extend: state (batch, nheads, dim, dstate) and x (batch, T, nheads, dim)")
     idx = slot_indices(state_batch_indices, x.shape[0], x.device, "state_batch_indices")
+    lens = slot_indices(seq_lens, x.shape[0], x.device, "seq_lens")
     H, P, N = state.shape[1:]
     # per-head parameters as stride-0 expansions (the kernel's tied form)
     dt_v = dt[..., None].expand(*dt.shape, P) if dt.dim() == 3 else dt
@@ -71,6 +76,7 @@ def selective_state_extend(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, 
     out = torch.empty_like(x)
     if x.numel() > 0:
         p = K.StateExtend(state=K.T(state), x=K.T(x), dt=K.T(dt_v), A=K.T(A_v), Bm=K.T(B_v), Cm=K.T(C_v), D=K.T(D_v), z=K.T(z_v),
-                          dt_bias=K.T(tb_v), out=K.T(out), dt_softplus=int(dt_softplus), state_batch_indices=K.T(idx))
+                          dt_bias=K.T(tb_v), out=K.T(out), dt_softplus=int(dt_softplus), state_batch_indices=K.T(idx),
+                          seq_lens=K.T(lens))
         K.run(lib, "omk_selective_state_extend", p, x)
     return out

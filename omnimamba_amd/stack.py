@@ -211,6 +211,8 @@ class ResidualBlock(nn.Module):
         if inference_params is not None and inference_params.seqlen_offset > 0 and hidden_states.shape[1] == 1:
             if getattr(inference_params, "seq_lens", None) is not None:
                 raise NotImplementedError("InferenceParams.seq_lens belongs to the prefill (seqlen_offset == 0), not to a decode step")
+            if getattr(inference_params, "extend_lens", None) is not None:
+                raise NotImplementedError("InferenceParams.extend_lens belongs to an extend of more than one position, not to a decode step")
             fused = self._decode_step_fused(hidden_states, residual, inference_params)
             if fused is not None:
                 return fused
@@ -438,9 +440,11 @@ class OmniMambaLM(nn.Module, GenerationMixin):
                 num_last_tokens=0):
         h = self.backbone(input_ids, input_embeddings, position_ids, task, inference_params=inference_params)
         seq_lens = getattr(inference_params, "seq_lens", None)
+        if seq_lens is None:
+            seq_lens = getattr(inference_params, "extend_lens", None)
         if num_last_tokens == 1 and seq_lens is not None:
-            # ragged prefill: the last VALID row of every right-padded sequence (a device gather; a row of length 0 is a padding row of
-            # a bucket and hands the head row 0: its logits mean nothing)
+            # ragged prefill / ragged extend: the last VALID row of every right-padded sequence (a device gather; a row of length 0 is a
+            # padding row of a bucket and hands the head row 0: its logits mean nothing)
             idx = (seq_lens.long() - 1).clamp_(0, h.shape[1] - 1)
             h = h.gather(1, idx[:, None, None].expand(-1, 1, h.shape[-1]))
         elif num_last_tokens > 0:

@@ -330,8 +330,10 @@ def _time_ms(fn, reps):
 def bench_mmu_followup(args, dev):
     """Multi-turn MMU.  (1) Per layer (1.3B shapes: H 64, P 64, N 128, batch 1): omk_selective_state_extend against the chunked scan
     with initial states for T in {1, 8, 32, 64, 128, 256} -- the sweep behind mamba2.EXTEND_SCAN_MAX_T.  (2) Time to the first token of
-    turn 2 for --batch conversations (729 image positions, Q1 of 24 ids, A1 of 32 ids, Q2 of 24 ids): mmu_continue from the turn-1
-    states against re-prefilling the whole conversation with mmu_generate_batch.  fp32 and bf16 weights, eager both ways."""
+    turn 2 for --batch conversations (729 image positions, Q1 of 24 ids, A1 of 32 ids, Q2 of --turn2-ids ids, 24 unless given): mmu_continue from the turn-1
+    states against re-prefilling the whole conversation with mmu_generate_batch.  fp32 and bf16 weights, eager both ways.
+    --extend-batch N > 1: mmu_continue is timed twice, at extend_batch 1 (every conversation extended on its own) and at N (those that
+    find a slot together extended by one right-padded pass), and the JSON line names both."""
     from omnimamba_amd.selective_state_update import selective_state_extend
     from omnimamba_amd.ssd_combined import mamba_chunk_scan_combined
     H, P, N = 64, 64, 128
@@ -363,23 +365,29 @@ def bench_mmu_followup(args, dev):
         g = torch.Generator().manual_seed(3)
         feats = [torch.randn(1, 729, cfg.fused_vision_dim, generator=g).to(dev).to(wdt) for _ in range(n)]
         q1 = [torch.randint(0, 50000, (1, 24), generator=g).to(dev) for _ in range(n)]
-        q2 = [torch.randint(0, 50000, (1, 24), generator=g).to(dev) for _ in range(n)]
+        q2 = [torch.randint(0, 50000, (1, args.turn2_ids), generator=g).to(dev) for _ in range(n)]
         ids1, st1 = model.mmu_generate_batch(feats, q1, max_length=4 + 729 + 24 + 32, max_batch=args.max_batch, cg=False, return_states=True)
         full = [torch.cat([a, i[:, 4 + a.shape[1]:], b], dim=1) for a, i, b in zip(q1, ids1, q2)]
         L2 = [s.seqlen + 1 + b.shape[1] + 1 for s, b in zip(st1, q2)]          # one sampled id: the first token of turn 2
 
-        def cont():
-            return model.mmu_continue(st1, q2, max_length=L2, max_batch=args.max_batch, cg=False)
+        def cont(extend_batch=1):
+            return model.mmu_continue(st1, q2, max_length=L2, max_batch=args.max_batch, cg=False, extend_batch=extend_batch)
 
         def again():
             return model.mmu_generate_batch(feats, full, max_length=L2, max_batch=args.max_batch, cg=False)
         t_cont = _time_ms(cont, args.steps)
         t_full = _time_ms(again, args.steps)
         same = sum(int(a[0, -1]) == int(b[0, -1]) for a, b in zip(cont()[0], again()))
+        grouped = {}
+        if args.extend_batch > 1:
+            t_grp = _time_ms(lambda: cont(args.extend_batch), args.steps)
+            grouped = {"extend_batch": args.extend_batch, "continue_extend_batch_1_ms": round(t_cont, 2),
+                       f"continue_extend_batch_{args.extend_batch}_ms": round(t_grp, 2), "extend_batch_speedup": round(t_cont / t_grp, 2),
+                       "first_ids_equal_grouped": sum(int(a[0, -1]) == int(b[0, -1]) for a, b in zip(cont(args.extend_batch)[0], cont()[0]))}
         print(json.dumps({"workload": "OmniMamba-1.3B MMU turn 2, time to first token", "dtype": "bf16" if wdt == torch.bfloat16 else "f32",
-                          "conversations": n, "max_batch": args.max_batch, "turn2_positions": L2[0] - 1,
+                          "conversations": n, "max_batch": args.max_batch, "turn2_positions": L2[0] - 1, "turn2_ids": args.turn2_ids,
                           "continue_ms": round(t_cont, 2), "reprefill_ms": round(t_full, 2), "speedup": round(t_full / t_cont, 2),
-                          "first_ids_equal": same}), flush=True)
+                          "first_ids_equal": same, **grouped}), flush=True)
         del model
         torch.cuda.empty_cache()
 
@@ -445,6 +453,9 @@ def main():
     ap.add_argument("--max-batch", type=int, default=8, help="decode_mmu_batch: slots of the ragged decoder")
     ap.add_argument("--prefill-batch", type=int, default=1, help="decode_mmu_batch: requests admitted by one right-padded prefill (1 = off)")
     ap.add_argument("--prefill-bucket", type=int, default=0, help="decode_mmu_batch: length bucket of the captured prefill graphs (0 = off; 128 for MMU)")
+    ap.add_argument("--turn2-ids", type=int, default=24, help="mmu_followup: ids of the second question (with the pending id: up to mamba2.EXTEND_SCAN_MAX_T "
+                                                                  "positions take the extend kernel, more the chunked scan)")
+    ap.add_argument("--extend-batch", type=int, default=1, help="mmu_followup: also time mmu_continue with this many turns per grouped extend (1 = off)")
     ap.add_argument("--reps", type=int, default=1, help="decode_mmu_batch: timed repetitions of the ragged run")
     ap.add_argument("--dtypes", default="f32,bf16", help="decode_mmu_batch: weight dtypes to run")
     ap.add_argument("--no-sequential", action="store_true", help="decode_mmu_batch: skip the sequential mmu_generate baseline")
