@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 13
+#define OMK_ABI_VERSION 14
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
@@ -492,6 +492,38 @@ typedef struct {
   float min_p;             /* ABI 7 (occupies the former tail padding): 0 = off; > 0 only with top_k == 0 */
 } OmkSample;
 int omk_sample(const OmkSample* p, omk_stream stream);
+
+/* ---- ABI 14: the sampler with one set of settings PER ROW (continuous batching: every row of a decode step is another request) ----
+ * One launch, one workgroup per row, the branches of omk_sample chosen row by row; every setting is a device array of `batch` entries,
+ * so the launch reads nothing from the host and a captured step replays it while the arrays are rewritten in between.
+ * Random stream: row b draws the uniform that omk_sample draws for row 0 of a one-row batch with seed = seeds[b], offset = steps[b] and no
+ * step_counter -- Philox4x32-10, counter (0, steps[b] lo, steps[b] hi, 0), key seeds[b].  The row index is NOT in the counter: the id of a
+ * row depends on its logits and its own settings only, not on where in the batch it sits or on what its neighbours are.
+ * Repetition penalty (reference generation.py:73-85, optional): the logit of every id in history[b][0 .. history_lens[b]) is multiplied by
+ * penalty[b] when negative and divided by it (IEEE division) otherwise, ONCE however often the id occurs, and rounded to the dtype of the
+ * logits, before any branch looks at the row; penalty[b] == 1 (or no penalty / history array) leaves the row alone.  `logits` is never
+ * written.  Nothing in the arrays can be checked on the host, so the kernel defines it: top_k is clamped to [0, 64], a history id outside
+ * [0, vocab) is skipped, history_lens[b] is clamped to [0, history_cap].  A non-positive or NaN temperature counts as 1, a non-positive
+ * penalty as 1, min_p applies with top_k == 0 only.  active[b] == 0 (optional; the padding rows of a bucket): the row writes nothing and
+ * none of its settings has any effect (they may hold anything; its history and penalty are not read).  Its entries are still loaded: every
+ * required array holds `batch` valid entries, inactive rows included.  OMK_EUNSUPPORTED: a history with a vocabulary too large for the kernel's id map (penalise a copy instead). */
+typedef struct {
+  OmkTensor logits;          /* (batch, vocab) f32 / bf16 / f16, unit last stride; read only */
+  OmkTensor out_ids;         /* out (batch) int64, dense (dtype field ignored) */
+  const void* top_k;         /* device int32 (batch) */
+  const void* top_p;         /* device f32 (batch) */
+  const void* temperature;   /* device f32 (batch) */
+  const void* min_p;         /* device f32 (batch) */
+  const void* seeds;         /* device uint64 (batch) */
+  const void* steps;         /* device int64 (batch) */
+  const void* penalty;       /* optional device f32 (batch); NULL = 1 everywhere */
+  const void* history;       /* optional device int64 (batch, history_cap), row b at history + b * history_stride */
+  const void* history_lens;  /* device int32 (batch); required with history */
+  const void* active;        /* optional device int32 (batch); NULL = every row */
+  int64_t history_stride;    /* elements between the rows of history */
+  int64_t history_cap;       /* width of history */
+} OmkSampleRows;
+int omk_sample_rows(const OmkSampleRows* p, omk_stream stream);
 
 #ifdef __cplusplus
 }

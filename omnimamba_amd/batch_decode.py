@@ -24,13 +24,14 @@ every row's states end up as after its own pending id and turn).
 from __future__ import annotations
 
 from collections import deque
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import List, Tuple
 
 import torch
 
 from . import generation as G
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
+from .sampling import SamplingParams, pack_rows, sample_rows
 
 
 @dataclass
@@ -68,6 +69,7 @@ class _Bucket:
                                   state_indices=self.slots)
         self.task = task
         self.model = model
+        self.samp = None        # per-request sampling (decode_ragged(sampling=...)): the rows' setting tensors, made on first use
         self.graph = None
         if cg:
             s = torch.cuda.Stream()
@@ -91,6 +93,94 @@ class _Bucket:
             return self._fwd()
         self.graph.replay()
         return self.logits
+
+    def row_settings(self):
+        """Static per-row setting tensors of sample_rows next to `slots`: rewritten when the rows change, steps / history_lens advanced
+        on the device in between; `active` is 0 for the padding rows."""
+        if self.samp is None:
+            dev = self.input_ids.device
+            self.samp = pack_rows([SamplingParams()] * self.nb, dev)
+            self.samp = {k: v.clone() for k, v in self.samp.items()}      # (pack_rows hands out rows of shared tensors)
+            self.samp["active"] = torch.zeros(self.nb, dtype=torch.int32, device=dev)
+            self.samp["history_lens"] = torch.zeros(self.nb, dtype=torch.int32, device=dev)
+            self.samp["out"] = torch.zeros(self.nb, dtype=torch.long, device=dev)
+        return self.samp
+
+
+class _RowSampler:
+    """decode_ragged(sampling=...): every draw of the call through ONE row-wise launch (sampling.sample_rows), request i with
+    params[i].  The n-th id request i samples is drawn at stream position params[i].step0 + n of its seed, whichever rows share the
+    launch.  With a repetition penalty somewhere the pool owns a history buffer (max_batch, cap) int64: a slot's history is its request's
+    input_ids followed by its sampled ids.  Its length is ids_len[i] + count[i] on the host; the device copy the kernel reads is the
+    bucket's static history_lens, advanced on the device between row changes."""
+
+    def __init__(self, c, params, requests, lens, dev):
+        self.c, self.params, self.dev = c, params, dev
+        self.count = [0] * len(params)             # ids sampled so far, per request
+        self.ids_len = [r[0].shape[1] for r in requests]
+        self.requests = requests
+        self.pen = any(p.repetition_penalty != 1.0 for p in params)
+        self.prev = None                           # (bucket size, requests of the rows) of the last step
+        if self.pen:
+            cap = max(c["max_seqlen"], max(l + m for l, m in zip(self.ids_len, lens)))
+            h = c.get("history")
+            if h is None or h.shape[1] < cap or h.device != dev:
+                c["history"] = torch.zeros(c["max_batch"], cap, dtype=torch.long, device=dev)
+            self.hist = c["history"]
+
+    def _settings(self, reqs):
+        return pack_rows([replace(self.params[i], step0=self.params[i].step0 + self.count[i]) for i in reqs], self.dev)
+
+    def _rows_history(self, rows, reqs):
+        """The histories of the pool slots `rows` (device) in row order, as wide as the longest of the requests `reqs` is now: the
+        lengths are known on the host (a request's input_ids + the ids it has sampled), so the gather leaves the unused tail alone."""
+        w = max(1, max(self.ids_len[i] + self.count[i] for i in reqs))
+        return self.hist[:, :w].index_select(0, rows)
+
+    def admit(self, reqs, slots, logits):
+        """The first id of the requests `reqs` (just admitted into `slots`) from their prefill / extend logits (len(reqs), vocab)."""
+        pk = self._settings(reqs)
+        if self.pen:
+            rows = torch.tensor(slots, dtype=torch.long).to(self.dev, non_blocking=True)
+            for i, s in zip(reqs, slots):
+                self.hist[s, :self.ids_len[i]].copy_(self.requests[i][0][0], non_blocking=True)
+            hl = torch.tensor([self.ids_len[i] for i in reqs], dtype=torch.long).to(self.dev, non_blocking=True)
+            toks = sample_rows(logits, **pk, history=self._rows_history(rows, reqs), history_lens=hl.int())
+            self.hist.index_put_((rows, hl), toks)
+        else:
+            pk.pop("penalty")
+            toks = sample_rows(logits, **pk)
+        for i in reqs:
+            self.count[i] += 1
+        self.prev = None
+        return toks
+
+    def step(self, bk, live, rows, logits):
+        """One id for every live row of bucket `bk` from the step's logits (bk.nb, vocab); rows: the slots of the bucket's rows (device)."""
+        st, nl = bk.row_settings(), len(live)
+        key = (bk.nb, tuple(i for i, _, _ in live))
+        if key != self.prev:
+            reqs = [i for i, _, _ in live]
+            pk = self._settings(reqs)
+            for k, v in pk.items():
+                st[k][:nl].copy_(v)
+            st["active"].copy_(torch.tensor([1] * nl + [0] * (bk.nb - nl), dtype=torch.int32), non_blocking=True)
+            if self.pen:
+                st["history_lens"].copy_(torch.tensor([self.ids_len[i] + self.count[i] for i in reqs] + [0] * (bk.nb - nl), dtype=torch.int32),
+                                         non_blocking=True)
+            self.prev = key
+        kw = {k: st[k] for k in ("top_k", "top_p", "temperature", "min_p", "seeds", "steps", "active", "out")}
+        if self.pen:
+            toks = sample_rows(logits, **kw, penalty=st["penalty"], history=self._rows_history(rows, [i for i, _, _ in live]),
+                               history_lens=st["history_lens"])[:nl]
+            self.hist.index_put_((rows[:nl], st["history_lens"][:nl].long()), toks)
+            st["history_lens"].add_(1)
+        else:
+            toks = sample_rows(logits, **kw)[:nl]
+        st["steps"].add_(1)
+        for i, _, _ in live:
+            self.count[i] += 1
+        return toks.clone()      # (`out` is the bucket's static buffer: the next step overwrites it)
 
 
 def _pool_cache(model, max_batch, max_seqlen, task, cg):
@@ -223,7 +313,7 @@ def _save(c, slot, seqlen, pending_id, task):
 
 @torch.inference_mode()
 def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
-                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1):
+                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None):
     """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
     generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
     model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
@@ -243,7 +333,14 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     extend_batch > 1: up to that many continued requests at the head of the queue that find a free slot at the same moment are admitted
     by one right-padded extend on their slots (_extend_group); admission stays FIFO, a plain request ends the group before it, nothing
     waits for a larger group, and the position-table IndexError of every request of the group is raised before anything is launched.  A
-    group of one, or one whose turns are all empty (padded length 1: a decode step), is admitted request by request.  1: off."""
+    group of one, or one whose turns are all empty (padded length 1: a decode step), is admitted request by request.  1: off.
+
+    sampling: None -- top_k / top_p / min_p / temperature hold for the whole call and the draws go through generation.sample, as ever.  One
+    sampling.SamplingParams for all requests, or a list with one per request: request i is sampled with its own settings (a repetition
+    penalty over its input_ids and sampled ids among them) and its own random stream -- its n-th sampled id of this call is drawn at
+    position step0 + n of its seed, so its ids do not depend on which requests share its steps, on max_batch or on the admission
+    order.  Every draw (prefill, extend, grouped or not, and the step) is one row-wise launch (sampling.sample_rows); top_k, top_p,
+    min_p and temperature are not read.  A follow-up turn continues its stream when it is given step0 = the ids drawn so far."""
     n = len(requests)
     if n == 0:
         return ([], []) if return_states else []
@@ -264,6 +361,10 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             raise ValueError("decode_ragged: every request is (input_ids (1, L), input_embeddings (1, P, d))")
         if len(r) == 3 and (task != "mmu" or not isinstance(r[2], DecodeState)):
             raise ValueError("decode_ragged: a continued request carries a DecodeState and is an mmu request")
+    if sampling is not None:
+        sampling = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
+        if len(sampling) != n or not all(isinstance(p, SamplingParams) for p in sampling):
+            raise ValueError(f"decode_ragged: sampling is one SamplingParams or a list of {n}, one per request")
     dev = requests[0][1].device
     if hasattr(model, "prepare_decode"):
         model.prepare_decode(task)
@@ -277,7 +378,10 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             c["buckets"][nb] = _Bucket(model, c["pool"], nb, c["max_seqlen"], task, cg, c["mempool"])
         return c["buckets"][nb]
 
-    draw = lambda lg: sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+    rs = None if sampling is None else _RowSampler(c, sampling, requests, lens, dev)
+    # the first id(s) of the requests `reqs` admitted into `slots`, from their prefill / extend logits
+    draw = lambda lg, reqs, slots: (sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature) if rs is None
+                                    else rs.admit(reqs, slots, lg))
     last = torch.zeros(c["max_batch"], dtype=torch.long, device=dev)   # last sampled id of every slot: the next step's input
     drawn, n_drawn = [], 0               # every sampled id tensor in order, and how many ids they hold
     pieces = [[] for _ in range(n)]      # per request: the positions of its ids in cat(drawn), in sampling order
@@ -307,7 +411,7 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
                 for _ in grp:
                     queue.popleft()
                 slots = [free.pop(0) for _ in grp]
-                toks = draw(_prefill_group(model, c, slots, [requests[i][1] for i in grp], task))   # (len(grp),)
+                toks = draw(_prefill_group(model, c, slots, [requests[i][1] for i in grp], task), grp, slots)   # (len(grp),)
                 toks_h = toks.tolist() if check_eos else [None] * len(grp)
                 admitted = [(i, s, requests[i][1].shape[1], toks[j:j + 1], toks_h[j]) for j, (i, s) in enumerate(zip(grp, slots))]
             elif len(xgrp) > 1 and any(requests[i][1].shape[1] > 0 for i in xgrp):   # (all turns empty: a decode step, not an extend)
@@ -319,7 +423,7 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
                 for _ in xgrp:
                     queue.popleft()
                 slots = [free.pop(0) for _ in xgrp]
-                toks = draw(_extend_group(model, c, slots, [requests[i][2] for i in xgrp], [requests[i][1] for i in xgrp], task))
+                toks = draw(_extend_group(model, c, slots, [requests[i][2] for i in xgrp], [requests[i][1] for i in xgrp], task), xgrp, slots)
                 toks_h = toks.tolist() if check_eos else [None] * len(xgrp)
                 admitted = [(i, s, off, toks[j:j + 1], toks_h[j]) for j, (i, s, off) in enumerate(zip(xgrp, slots, offs))]
             else:
@@ -332,9 +436,9 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
                     if n_pos is not None and off > n_pos:
                         raise IndexError(f"decode_ragged: request {i} continues to position {off - 1}, outside the {task} position table of "
                                          f"{n_pos} rows (StackConfig.{{t2i,mmu}}_positions)")
-                    tok = draw(_extend(model, c, s, st, emb, task))
+                    tok = draw(_extend(model, c, s, st, emb, task), [i], [s])
                 else:
-                    tok = draw(_prefill(model, c, s, emb, task, cg, prefill_bucket, n_pos))   # (1,)
+                    tok = draw(_prefill(model, c, s, emb, task, cg, prefill_bucket, n_pos), [i], [s])   # (1,)
                     off = emb.shape[1]
                 admitted = [(i, s, off, tok, int(tok[0]) if check_eos else None)]
             for i, s, off, tok, tok_h in admitted:
@@ -361,7 +465,10 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
         bk.input_ids[:, 0] = last.index_select(0, rows)
         bk.position_ids.copy_(torch.tensor([[off] for _, _, off in live] + [[0]] * pad, dtype=torch.long), non_blocking=True)
         bk.slots.copy_(torch.tensor(slots_h + [-1] * pad, dtype=torch.int32), non_blocking=True)
-        toks = draw(bk.run()[: len(live)])
+        if rs is None:
+            toks = sample(bk.run()[: len(live)], top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+        else:
+            toks = rs.step(bk, live, rows, bk.run())
         last.index_copy_(0, rows[: len(live)], toks)
         toks_h = toks.tolist() if check_eos else None
         still = []

@@ -21,6 +21,7 @@
 //                   inverse-CDF draw with one Philox4x32-10 uniform keyed by (seed, row, step counter).
 // The reference draws with torch.multinomial; the streams differ, the distribution is the same (tests: chi-square at fixed
 // seeds, bit-exact ids for top_k == 1).
+#include <atomic>
 #include "omk_common.h"
 
 namespace omk {
@@ -120,6 +121,328 @@ template <class T, class F> __device__ __forceinline__ void wave_find_digit(F cn
   }
 }
 
+// The settings of ONE row of omk_sample_rows, uniform over its workgroup: the row's entries of the device arrays.  c0 is the first Philox
+// counter word (0: the row index is not in the counter, see include/omk.h).
+struct RowCfg {
+  int top_k; float top_p, inv_temp, min_p;
+  unsigned long long seed, step; uint32_t c0;
+  float pen;   // PEN only: what the logits marked in the id map are multiplied with (negative ones) / divided by
+};
+
+// One row of logits -> one id, by the whole workgroup.  PEN: `pmap` (LDS, one byte per token) marks the ids of the row's history; the
+// loader penalises a marked logit and rounds it to T as the in-place torch version does, so every pass sees the same penalised row.
+template <class T, bool PEN>
+__device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* outp, const RowCfg a, const unsigned char* pmap) {
+  // The branches are exclusive, so their large buffers share two raw blocks (they were 69 KB as separate arrays):
+  //   rawA  hist (top-k select)  |  hm8 + hc8 (whole-vocabulary top-p)
+  //   rawB  sc64, sc32 (one after the other: a block scan ends with a barrier)  |  scf (plain whole-vocabulary draw)
+  // hist / hm8 / hc8: eight copies of every counter, picked by the lane: the keys of a row share their top byte(s), and 64 lanes adding to ONE
+  // LDS address are 64 serial atomics (copy c of digit d lives at 8 d + c: the copies of a digit sit in different banks)
+  __shared__ __attribute__((aligned(16))) unsigned long long rawA[256 * 8 + 256 * 4];
+  __shared__ __attribute__((aligned(16))) unsigned long long rawB[2 * SNT];
+  uint32_t* const hist = (uint32_t*)rawA;
+  unsigned long long* const hm8 = rawA;
+  uint32_t* const hc8 = (uint32_t*)(rawA + 256 * 8);
+  unsigned long long* const sc64 = rawB;
+  uint32_t* const sc32 = (uint32_t*)rawB;
+  float* const scf = (float*)rawB;
+  __shared__ uint32_t sel_prefix, sel_need, n_gt, n_eq;
+  __shared__ float cval[SAMPLE_KMAX];
+  __shared__ int cidx[SAMPLE_KMAX];
+  __shared__ float wmax[SNW];
+  __shared__ int wimax[SNW];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  auto ld = [&](int i) -> float {
+    float v = to_f32(rowp[i]);
+    if constexpr (PEN) { if (pmap[i]) v = to_f32(from_f32<T>(v < 0.f ? v * a.pen : v / a.pen)); }
+    return v;
+  };
+  // one pass over the row, thread-strided (coalesced), four requests in flight per lane
+  auto strided = [&](auto&& fn) {
+    for (int i0 = tid; i0 < V; i0 += 4 * SNT) {
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) { const int i = i0 + u * SNT; v[u] = ld(i < V ? i : V - 1); }
+#pragma unroll
+      for (int u = 0; u < 4; u++) { const int i = i0 + u * SNT; if (i < V) fn(v[u], i); }
+    }
+  };
+  // block maximum + its lowest index, in every thread
+  auto block_argmax = [&](float& m, int& mi) {
+    m = -INFINITY; mi = 0x7fffffff;
+    strided([&](float v, int i) { if (v > m || (v == m && i < mi)) { m = v; mi = i; } });
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float om = shfl_xor(m, off); const int oi = shfl_xor(mi, off);
+      if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    if (lane == 0) { wmax[wv] = m; wimax[wv] = mi; }
+    block_sync();
+    for (int k = 0; k < SNW; k++) if (wmax[k] > m || (wmax[k] == m && wimax[k] < mi)) { m = wmax[k]; mi = wimax[k]; }
+  };
+  auto philox_u24 = [&]() -> uint32_t {
+    uint32_t cc[4] = {a.c0, (uint32_t)a.step, (uint32_t)(a.step >> 32), 0u};
+    philox4x32(cc, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
+    return cc[0] >> 8;
+  };
+
+  if (a.top_k == 1) {
+    float m; int mi;
+    block_argmax(m, mi);
+    if (tid == 0) outp[0] = mi == 0x7fffffff ? 0 : mi;
+    return;
+  }
+  if (a.top_k == 0 && (a.min_p > 0.f || (a.top_p > 0.f && a.top_p < 1.f))) {
+    // ---- the whole vocabulary behind one of the reference's two filters (see the header)
+    __shared__ unsigned long long hm[256];
+    __shared__ uint32_t hc[256];
+    __shared__ unsigned long long s_acc, s_ztot;
+    __shared__ uint32_t s_prefix, s_r;
+    __shared__ float wsumf[SNW];
+    __shared__ int pick_f;
+    const int c = (V + SNT - 1) / SNT, lo = tid * c < V ? tid * c : V, hi = lo + c < V ? lo + c : V;
+    float m; int mi;
+    if (tid == 0) pick_f = -1;
+    block_argmax(m, mi);
+    const float sct = a.inv_temp * LOG2E;
+    // mass of a token in the tempered distribution, 2^-40 units of the largest one (an integer: sums are exact and order-free)
+    auto mass = [&](float l) -> unsigned long long { return (unsigned long long)(exp2_fast((l - m) * sct) * 1099511627776.0f); };
+    const bool use_min_p = a.min_p > 0.f;
+    float thr = -INFINITY;           // min_p: raw logits below it are cut
+    uint32_t vstar = 0u, rcut = 0u;  // top-p: keys below vstar are cut, and the first rcut tokens (index order) whose key equals it
+    if (use_min_p) {
+      float z = 0.f;
+      strided([&](float v, int) { z += exp2_fast((v - m) * LOG2E); });          // softmax of the UNtempered logits (:109)
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) z += shfl_xor(z, off);
+      if (lane == 0) wsumf[wv] = z;
+      block_sync();
+      z = 0.f;
+      for (int k = 0; k < SNW; k++) z += wsumf[k];
+      thr = a.min_p / z;                                                        // max probability = 1 / z
+    } else {
+      unsigned long long zt = 0ull;
+      strided([&](float v, int) { zt += mass(v); });
+      const unsigned long long incl = block_incl_scan<unsigned long long>(zt, sc64, tid);
+      if (tid == SNT - 1) s_ztot = incl;
+      if (tid == 0) { s_prefix = 0u; s_acc = 0ull; }
+      block_sync();
+      const unsigned long long ztot = s_ztot;
+      unsigned long long Q = (unsigned long long)((double)(1.f - a.top_p) * (double)ztot);   // masses <= Q (cumulative, ascending) are cut
+      if (Q >= ztot) Q = ztot ? ztot - 1 : 0ull;
+      for (int pass = 0; pass < 4; pass++) {
+        const int shift = 24 - 8 * pass;
+        for (int i = tid; i < 256 * 8; i += SNT) { hm8[i] = 0ull; hc8[i] = 0u; }
+        block_sync();
+        const uint32_t pre = s_prefix, pmask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+        strided([&](float l, int) {
+          const uint32_t k = fkey(l);
+          if ((k & pmask) == pre) { const uint32_t d = 8u * ((k >> shift) & 255u) + (uint32_t)(lane & 7); lds_add_u64(&hm8[d], mass(l)); lds_fetch_add_u32(&hc8[d], 1u); }
+        });
+        block_sync();
+        if (tid < 256) {
+          unsigned long long tm = 0ull; uint32_t tc = 0u;
+#pragma unroll
+          for (int c8 = 0; c8 < 8; c8++) { tm += hm8[8 * tid + c8]; tc += hc8[8 * tid + c8]; }
+          hm[tid] = tm; hc[tid] = tc;
+        }
+        block_sync();
+        if (wv == 0) {   // ascending: digits whose whole mass still fits under Q are cut; the first one that does not holds the boundary
+          const unsigned long long acc0 = s_acc;
+          uint32_t d; unsigned long long before;
+          wave_find_digit<unsigned long long>([&](int rr) -> unsigned long long { return hm[rr]; }, Q - acc0, lane, d, before);
+          if (lane == 0) {
+            const unsigned long long acc = acc0 + before;
+            s_acc = acc; s_prefix = pre | (d << shift);
+            if (pass == 3) { const unsigned long long one = hc[d] ? hm[d] / hc[d] : 0ull; s_r = one ? (uint32_t)((Q - acc) / one) : 0u; if (s_r >= hc[d] && hc[d]) s_r = hc[d] - 1u; }
+          }
+        }
+        block_sync();
+      }
+      vstar = s_prefix; rcut = s_r;
+    }
+    // ---- kept mass of the thread's tokens.  Ties at the boundary value that are cut (rare) need index-order ranks: contiguous slices then;
+    // otherwise thread t owns t, t + SNT, ... (coalesced reads; the inverse CDF may lay the tokens out in any fixed order)
+    const bool contig = !use_min_p && rcut > 0u;
+    uint32_t tie_before = 0u;
+    if (contig) {
+      uint32_t tc = 0u;
+      for (int i = lo; i < hi; i++) tc += fkey(ld(i)) == vstar ? 1u : 0u;
+      tie_before = block_incl_scan<uint32_t>(tc, sc32, tid) - tc;
+    }
+    auto owned = [&](auto&& fn) {
+      if (contig) { for (int i = lo; i < hi; i++) fn(ld(i), i); }
+      else strided(fn);
+    };
+    unsigned long long km = 0ull;
+    {
+      uint32_t rank = tie_before;
+      owned([&](float l, int) {
+        bool keep;
+        if (use_min_p) keep = l >= thr;
+        else { const uint32_t k = fkey(l); keep = k > vstar || (k == vstar && rank++ >= rcut); }
+        if (keep) km += mass(l);
+      });
+    }
+    const unsigned long long incl = block_incl_scan<unsigned long long>(km, sc64, tid);
+    if (tid == SNT - 1) s_ztot = incl;
+    block_sync();
+    const unsigned long long ktot = s_ztot, start = incl - km;
+    const unsigned long long u24 = philox_u24();
+    const unsigned long long target = (ktot >> 24) * u24 + (((ktot & 0xffffffull) * u24) >> 24);   // floor(u ktot), u in [0, 1): < ktot
+    if (ktot > 0ull && target >= start && target < incl) {   // exactly one thread
+      unsigned long long run = start; uint32_t rank = tie_before; int got = -1; bool done = false;
+      owned([&](float l, int i) {
+        bool keep;
+        if (use_min_p) keep = l >= thr;
+        else { const uint32_t k = fkey(l); keep = k > vstar || (k == vstar && rank++ >= rcut); }
+        const unsigned long long e = keep ? mass(l) : 0ull;
+        if (!done && e > 0ull) got = i;
+        run += e;
+        if (run > target) done = true;
+      });
+      pick_f = got;
+    }
+    block_sync();
+    // (nothing kept -- min_p with every logit under the threshold, where the reference's multinomial raises on a row of NaN: the arg max)
+    if (tid == 0) outp[0] = pick_f >= 0 ? pick_f : (mi == 0x7fffffff ? 0 : mi);
+    return;
+  }
+  if (a.top_k == 0) {
+    // full-vocabulary multinomial (the reference's top_k == 0 branch with top_p outside (0, 1): softmax(logits / T), one draw).
+    // Block maximum, the mass of every thread's tokens, an inclusive scan of the SNT masses (the scan values tile [0, total) exactly:
+    // end_t = start_{t + 1}), one Philox number scaled to the total, and the thread whose interval holds it walks its tokens.
+    __shared__ float tot_s;
+    __shared__ int pick_s;
+    // (thread t owns the tokens t, t + SNT, ...: the inverse CDF may lay the tokens out in ANY fixed order, and this one reads coalesced --
+    // contiguous slices per thread were 64 scattered lines per request: 17 -> see profiles/r06_sampler.txt)
+    float m; int mi;
+    if (tid == 0) pick_s = 0;
+    block_argmax(m, mi);
+    const float sc = a.inv_temp * LOG2E;
+    float mine = 0.f;
+    strided([&](float v, int) { mine += exp2_fast((v - m) * sc); });
+    const float end = block_incl_scan<float>(mine, scf, tid);
+    scf[tid] = end;                                                 // (the scan values tile [0, total): a thread starts where its neighbour ends)
+    if (tid == SNT - 1) tot_s = end;
+    block_sync();
+    const float tot = tot_s, start = tid ? scf[tid - 1] : 0.f;
+    float u = (float)philox_u24() * (1.0f / 16777216.0f) * tot;   // uniform in [0, tot)
+    if (u >= tot) u = tot * 0.99999994f;                            // (the product may round up to the total)
+    if (u >= start && u < end) {   // exactly one thread when 0 < tot < inf
+      float run = start; int got = tid < V ? tid : 0; bool done = false;
+      strided([&](float v, int i) {
+        const float e = exp2_fast((v - m) * sc);
+        if (!done && e > 0.f) got = i;                              // rounding inside the walk: the last token with mass
+        run += e;
+        if (run > u) done = true;
+      });
+      pick_s = got;
+    }
+    block_sync();
+    if (tid == 0) outp[0] = pick_s;
+    return;
+  }
+  const int K = a.top_k < V ? a.top_k : V;
+  // ---- radix select: the key of the K-th largest logit, 8 bits per pass from the top
+  if (tid == 0) { sel_prefix = 0u; sel_need = (uint32_t)K; }
+  for (int pass = 0; pass < 4; pass++) {
+    const int shift = 24 - 8 * pass;
+    for (int i = tid; i < 256 * 8; i += SNT) hist[i] = 0u;
+    block_sync();
+    const uint32_t pre = sel_prefix, pmask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+    strided([&](float v, int) {   // (aggregating the lanes of a wave per distinct digit with ballots instead: slower, 55.7 -> 66.3 us)
+      const uint32_t k = fkey(v);
+      if ((k & pmask) == pre) lds_fetch_add_u32(&hist[8u * ((k >> shift) & 255u) + (uint32_t)(lane & 7)], 1u);
+    });
+    block_sync();
+    if (tid < 256) {
+      uint32_t t = 0u;
+#pragma unroll
+      for (int c = 0; c < 8; c++) t += hist[8 * tid + c];
+      hist[8 * tid] = t;
+    }
+    block_sync();
+    if (wv == 0) {   // walk the digits from the top until `need` keys are covered
+      const uint32_t need = sel_need;
+      uint32_t r, before;
+      wave_find_digit<uint32_t>([&](int rr) -> uint32_t { return hist[8u * (255u - (uint32_t)rr)]; }, need - 1u, lane, r, before);
+      if (lane == 0) { sel_prefix = pre | ((255u - r) << shift); sel_need = need - before; }
+    }
+    block_sync();
+  }
+  const uint32_t kth = sel_prefix;           // keys > kth: all taken; keys == kth: sel_need of them (lowest indices first)
+  const uint32_t take_eq = sel_need;
+  if (tid == 0) { n_gt = 0u; n_eq = 0u; }
+  block_sync();
+  const uint32_t base_eq = (uint32_t)K - take_eq;   // slots [0, base_eq) for keys > kth, [base_eq, K) for the ties at the threshold
+  strided([&](float v, int i) {
+    const uint32_t k = fkey(v);
+    if (k > kth) { const uint32_t s = lds_fetch_add_u32(&n_gt, 1u); if (s < base_eq) { cval[s] = v; cidx[s] = i; } }
+    else if (k == kth) { const uint32_t s = lds_fetch_add_u32(&n_eq, 1u); if (s < take_eq) { cval[base_eq + s] = v; cidx[base_eq + s] = i; } }
+  });
+  block_sync();
+  if (wv != 0) return;
+  if (n_eq > take_eq) {
+    // more logits equal the threshold than there are slots left (16-bit logits tie often): which of them are candidates must not
+    // depend on the order the tickets were handed out -- one wave walks the row in index order and keeps the first take_eq
+    uint32_t got = 0u;
+    for (int i0 = 0; i0 < V && got < take_eq; i0 += 64) {
+      const int i = i0 + lane;
+      float v = 0.f;
+      bool eq = false;
+      if (i < V) { v = ld(i); eq = fkey(v) == kth; }
+#ifdef OMK_EMU
+      const unsigned long long m = emu::ballot(eq ? 1 : 0);
+#else
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(eq);
+#endif
+      const uint32_t rank = got + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+      if (eq && rank < take_eq) { cval[base_eq + rank] = v; cidx[base_eq + rank] = i; }
+      got += (uint32_t)__builtin_popcountll(m);
+    }
+  }
+  // ---- one wave: sort the K candidates (value descending, index ascending), softmax, top-p, draw
+  float v = lane < K ? cval[lane] : -INFINITY;
+  int ix = lane < K ? cidx[lane] : 0x7fffffff;
+#pragma unroll
+  for (int size = 2; size <= 64; size <<= 1)
+#pragma unroll
+    for (int stride = size >> 1; stride >= 1; stride >>= 1) {
+      const float ov = shfl_xor(v, stride); const int oi = shfl_xor(ix, stride);
+      const bool first = (lane & stride) == 0;                  // lower lane of the pair
+      const bool desc = (lane & size) == 0;                     // direction of this bitonic block
+      const bool mine_before = v > ov || (v == ov && ix < oi);  // "mine sorts before the other" in descending order
+      const bool keep = (first == desc) ? mine_before : !mine_before;
+      if (!keep) { v = ov; ix = oi; }
+    }
+  const float vmax = wave_read_lane(v, 0);
+  float p = lane < K ? exp2_fast((v - vmax) * a.inv_temp * LOG2E) : 0.f;
+  const float tot = wave_sum(p);
+  p /= tot;
+  float incl = wave_incl_scan_add(p);
+  const float excl = incl - p;
+  const bool keep = lane < K && (a.top_p <= 0.f || a.top_p >= 1.f || excl < a.top_p);
+  const float pk = keep ? p : 0.f;
+  const float ktot = wave_sum(pk);
+  const float cum = wave_incl_scan_add(pk);
+  const float u = (float)philox_u24() * (1.0f / 16777216.0f) * ktot;   // uniform in [0, ktot)
+  // first kept candidate whose cumulative mass exceeds u
+  const bool hit = keep && cum > u;
+  unsigned long long mask;
+#ifdef OMK_EMU
+  mask = emu::ballot(hit ? 1 : 0);
+#else
+  mask = __builtin_amdgcn_ballot_w64(hit);
+#endif
+  int pick = mask ? __builtin_ctzll(mask) : 0;   // rounding at the top end: fall back to the largest candidate
+  const int chosen = shfl(ix, pick);
+  if (lane == 0) outp[0] = chosen;
+}
+
+// omk_sample's kernel: the whole-batch settings are kernel arguments.  It is kept as it was before sample_row existed, separate arrays
+// and all (69 KB of LDS): sharing sample_row's body cost it 0.2 - 0.9 us per launch on the MI355X (profiles/sample_rows.txt), more than the
+// spread of its own repetitions, and its callers sit inside captured steps.  A change to one of the two bodies belongs in the other too.
 template <class T>
 __global__ __launch_bounds__(SNT) void sample_kernel(SampleArgs a) {
   // eight copies of every counter, picked by the lane: the keys of a row share their top byte(s), and 64 lanes adding to ONE LDS address are 64
@@ -420,6 +743,55 @@ __global__ __launch_bounds__(SNT) void sample_kernel(SampleArgs a) {
   if (lane == 0) a.out[row] = chosen;
 }
 
+struct SampleRowsArgs {
+  const void* logits; int64_t ls;
+  int64_t* out; int V;
+  const int* top_k; const float *top_p, *temperature, *min_p;
+  const unsigned long long* seeds; const int64_t* steps;
+  const float* penalty; const int64_t* history; const int* history_lens; const int* active;
+  int64_t hs; int hcap;
+};
+
+// omk_sample_rows: row b's settings come from the device arrays.  Nothing in them is trusted: see the clamps (include/omk.h).
+// PEN: dynamic LDS holds the id map of the row's history, (V rounded up to 4) bytes.
+template <class T, bool PEN>
+__global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  // The row's entries are all requested in ONE round of scalar loads, the active flag among them: nothing of the passes over the row
+  // can start before the branch is known, so a flag tested first puts its own rounds (its pointer, then its value) in front of the
+  // round of the settings.  The compiler sinks the loads behind the test when it may: the OMK_OPAQUE_S lines pin them in front of it.
+  // An inactive row's entries are inside the (batch) arrays like every row's; what they hold is not looked at.
+  int act = *(a.active ? a.active + row : a.top_k + row);   // (no flag array: any valid word, so the load needs no branch of its own)
+  int k = a.top_k[row];
+  float tp = a.top_p[row], t = a.temperature[row], mp = a.min_p[row];
+  unsigned long long sd = a.seeds[row], st = (unsigned long long)a.steps[row];
+  OMK_OPAQUE_S(k); OMK_OPAQUE_S(tp); OMK_OPAQUE_S(t); OMK_OPAQUE_S(mp); OMK_OPAQUE_S(sd); OMK_OPAQUE_S(st); OMK_OPAQUE_S(act);
+  if (a.active && act == 0) return;   // (uniform over the workgroup, in front of every barrier)
+  RowCfg c;
+  c.top_k = uniform_i(k < 0 ? 0 : (k > SAMPLE_KMAX ? SAMPLE_KMAX : k));   // (the clamp is a VALU v_med3: back into a scalar register, as omk_sample's argument is)
+  c.top_p = tp;
+  c.inv_temp = t > 0.f ? 1.f / t : 1.f;
+  c.min_p = c.top_k == 0 ? mp : 0.f;
+  c.seed = sd; c.step = st; c.c0 = 0u; c.pen = 1.f;
+  const unsigned char* pmap = nullptr;
+  if constexpr (PEN) {
+    OMK_DYN_SMEM(dyn);
+    unsigned char* const map = (unsigned char*)dyn;
+    const float pen = a.penalty[row];
+    int hl = a.history_lens[row];
+    hl = hl < 0 ? 0 : (hl > a.hcap ? a.hcap : hl);
+    if (!(pen > 0.f) || pen == 1.f) hl = 0;     // off: an empty map
+    else c.pen = pen;
+    for (int i = tid; i < (a.V + 3) / 4; i += SNT) ((uint32_t*)map)[i] = 0u;
+    block_sync();
+    const int64_t* hrow = a.history + (int64_t)row * a.hs;
+    for (int j = tid; j < hl; j += SNT) { const int64_t id = hrow[j]; if (id >= 0 && id < (int64_t)a.V) map[id] = 1; }   // plain stores of 1: duplicates mark once
+    block_sync();
+    pmap = map;
+  }
+  sample_row<T, PEN>((const T*)a.logits + (int64_t)row * a.ls, a.V, a.out + row, c, pmap);
+}
+
 }  // namespace omk
 
 using namespace omk;
@@ -444,4 +816,59 @@ extern "C" int omk_sample(const OmkSample* p, omk_stream stream) {
   dim3 grid((unsigned)a.B), block(SNT);
   OMK_DISPATCH_DTYPE(a.dt, T, OMK_LAUNCH((sample_kernel<T>), grid, block, 0, stream, a));
   return finish_launch("sample");
+}
+
+// the id map of the penalty launch: one byte per token in dynamic LDS, next to the 44 KB the branches share
+constexpr int64_t SAMPLE_PEN_MAX_V = 65536;
+
+// Raise the dynamic-LDS limit of the penalty instantiation when a launch needs more than the device was already granted, not on every
+// step (the attribute belongs to a function on a device).  0 = granted.
+template <class T> static int grant_map_lds(size_t smem) {
+#ifdef OMK_EMU
+  return 0;
+#else
+  constexpr int MAXDEV = 64;
+  static std::atomic<size_t> granted[MAXDEV];
+  int d = -1;
+  const bool known = hipGetDevice(&d) == hipSuccess && d >= 0 && d < MAXDEV;
+  if (known && granted[d].load(std::memory_order_relaxed) >= smem) return 0;
+  if (OMK_SET_MAX_DYN_SMEM((sample_rows_kernel<T, true>), smem)) return 1;
+  if (known) granted[d].store(smem, std::memory_order_relaxed);
+  return 0;
+#endif
+}
+
+extern "C" int omk_sample_rows(const OmkSampleRows* p, omk_stream stream) {
+  OMK_REQUIRE(p && present(p->logits) && present(p->out_ids), "sample_rows: logits and out_ids required");
+  OMK_REQUIRE(p->logits.ndim == 2 && p->logits.stride[1] == 1, "sample_rows: logits must be (batch, vocab) with unit last stride");
+  OMK_REQUIRE(p->out_ids.ndim == 1 && p->out_ids.shape[0] == p->logits.shape[0] && p->out_ids.stride[0] == 1, "sample_rows: out_ids must be dense int64 (batch)");
+  OMK_REQUIRE(p->logits.dtype == OMK_F32 || p->logits.dtype == OMK_BF16 || p->logits.dtype == OMK_F16, "sample_rows: logits dtype");
+  OMK_REQUIRE(p->top_k && p->top_p && p->temperature && p->min_p && p->seeds && p->steps,
+              "sample_rows: top_k, top_p, temperature, min_p, seeds and steps are required device arrays of (batch) entries");
+  OMK_REQUIRE(!p->history || p->history_lens, "sample_rows: history needs history_lens");
+  OMK_REQUIRE(!p->history || (p->history_cap >= 0 && p->history_cap < (1ll << 31)), "sample_rows: history_cap");
+  if (p->logits.shape[0] == 0) return OMK_OK;
+  OMK_REQUIRE(p->logits.shape[1] > 0 && p->logits.shape[1] < (1ll << 31), "sample_rows: vocabulary size");
+  SampleRowsArgs a = {};
+  a.logits = p->logits.data; a.ls = p->logits.stride[0];
+  a.out = (int64_t*)p->out_ids.data; a.V = (int)p->logits.shape[1];
+  a.top_k = (const int*)p->top_k; a.top_p = (const float*)p->top_p; a.temperature = (const float*)p->temperature; a.min_p = (const float*)p->min_p;
+  a.seeds = (const unsigned long long*)p->seeds; a.steps = (const int64_t*)p->steps; a.active = (const int*)p->active;
+  const bool pen = p->penalty && p->history && p->history_cap > 0;   // (no penalty array, or no history: nothing to penalise)
+  dim3 grid((unsigned)p->logits.shape[0]), block(SNT);
+  const int dt = p->logits.dtype;
+  if (!pen) {
+    OMK_DISPATCH_DTYPE(dt, T, OMK_LAUNCH((sample_rows_kernel<T, false>), grid, block, 0, stream, a));
+    return finish_launch("sample_rows");
+  }
+  if (a.V > SAMPLE_PEN_MAX_V)
+    return fail(OMK_EUNSUPPORTED, "sample_rows: the id map of the repetition penalty holds %lld tokens, the vocabulary has %d", (long long)SAMPLE_PEN_MAX_V, a.V);
+  a.penalty = (const float*)p->penalty; a.history = (const int64_t*)p->history; a.history_lens = (const int*)p->history_lens;
+  a.hs = p->history_stride; a.hcap = (int)p->history_cap;
+  const size_t smem = (size_t)((a.V + 3) / 4) * 4;
+  OMK_DISPATCH_DTYPE(dt, T, {
+    if (grant_map_lds<T>(smem)) return fail(OMK_ELAUNCH, "sample_rows: cannot reserve %zu bytes of LDS for the id map", smem);
+    OMK_LAUNCH((sample_rows_kernel<T, true>), grid, block, smem, stream, a);
+  });
+  return finish_launch("sample_rows");
 }

@@ -2,7 +2,8 @@
 (/root/reference/models/stage2/generation.py:87-121).  One launch, no host scalar after it: usable inside a captured decode step."""
 from __future__ import annotations
 
-from typing import Optional
+from dataclasses import dataclass
+from typing import Optional, Sequence
 
 import torch
 
@@ -40,4 +41,105 @@ def sample_device(logits: torch.Tensor, top_k: int = 1, top_p: float = 0.0, temp
     p.out_ids.shape[0] = out.shape[0]
     p.out_ids.stride[0] = out.stride(0)
     K.run(lib, "omk_sample", p, logits)
+    return out
+
+
+# ---- per-request sampling: one set of settings per row of a batch (omk_sample_rows, ABI 14) --------------------------------------------
+
+@dataclass(frozen=True)
+class SamplingParams:
+    """How ONE request is sampled.  seed and step0 name its random stream: the n-th id the request samples is drawn at stream position
+    step0 + n of seed, whatever batch it shares a step with (a follow-up turn continues its stream by passing the number of ids drawn so
+    far as step0).  The rules are omk_sample's own; repetition_penalty 1.0 means off."""
+    top_k: int = 1
+    top_p: float = 0.0
+    min_p: float = 0.0
+    temperature: float = 1.0
+    repetition_penalty: float = 1.0
+    seed: int = 0
+    step0: int = 0
+
+    def __post_init__(self):
+        if not 0 <= int(self.top_k) <= MAX_TOP_K:
+            raise ValueError(f"SamplingParams: top_k must be in [0, {MAX_TOP_K}], got {self.top_k}")
+        if not self.temperature > 0.0:
+            raise ValueError(f"SamplingParams: temperature must be positive, got {self.temperature}")
+        if not self.top_p <= 1.0:
+            raise ValueError(f"SamplingParams: top-p should be in (0, 1], got {self.top_p}")
+        if not 0.0 <= self.min_p < 1.0:
+            raise ValueError(f"SamplingParams: min_p must be in [0, 1), got {self.min_p}")
+        if self.min_p > 0.0 and self.top_k != 0:
+            raise ValueError("SamplingParams: min_p belongs to the whole-vocabulary branch (top_k == 0)")
+        if not self.repetition_penalty > 0.0:
+            raise ValueError(f"SamplingParams: repetition_penalty must be positive, got {self.repetition_penalty}")
+        if self.step0 < 0:
+            raise ValueError(f"SamplingParams: step0 must be >= 0, got {self.step0}")
+
+
+def _signed64(v: int) -> int:
+    v = int(v) & (2 ** 64 - 1)
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def pack_rows(params_list: Sequence[SamplingParams], device) -> dict:
+    """The setting tensors of sample_rows for a list of SamplingParams, row b from params_list[b]: a dict with top_k (int32), top_p,
+    temperature, min_p, penalty (float32), seeds (the uint64 seed's bits in an int64) and steps (int64, step0)."""
+    n = len(params_list)
+    f = torch.tensor([[p.top_p, p.temperature, p.min_p, p.repetition_penalty] for p in params_list], dtype=torch.float32).reshape(n, 4).t().contiguous()
+    i = torch.tensor([[_signed64(p.seed), p.step0] for p in params_list], dtype=torch.int64).reshape(n, 2).t().contiguous()
+    k = torch.tensor([p.top_k for p in params_list], dtype=torch.int32)
+    f, i, k = f.to(device), i.to(device), k.to(device)
+    return {"top_k": k, "top_p": f[0], "temperature": f[1], "min_p": f[2], "penalty": f[3], "seeds": i[0], "steps": i[1]}
+
+
+def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev):
+    if t is None:
+        return None
+    if t.dtype != dtype or t.device != dev or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        raise ValueError(f"sample_rows: {name} must be a dense {dtype} tensor of ({n},) on {dev}")
+    return t.data_ptr()
+
+
+def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: Optional[torch.Tensor], temperature: Optional[torch.Tensor],
+                min_p: Optional[torch.Tensor], seeds: Optional[torch.Tensor], steps: Optional[torch.Tensor], penalty: Optional[torch.Tensor] = None,
+                history: Optional[torch.Tensor] = None, history_lens: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(batch, vocab) -> (batch,) int64 ids in ONE launch, row b sampled with its own settings: top_k (int32), top_p, temperature, min_p
+    (float32), seeds and steps (int64; the seed's 64 bits) -- device tensors of (batch,).  Row b draws what
+    sample_device(logits[b:b+1], ..., seed=seeds[b], offset=steps[b]) draws: its id does not depend on its place in the batch.
+    penalty (float32) with history (int64 (batch, cap), unit last stride) and history_lens (int32): the repetition penalty of
+    generation.modify_logit_for_repetition_penalty over history[b, :history_lens[b]], fused (logits is not written).  active (int32):
+    rows with 0 write nothing.  No host read: capturable, the tensors may be rewritten between replays."""
+    lib = get_lib()
+    n, dev = logits.shape[0], logits.device
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+    if out.dtype != torch.int64 or out.device != dev or out.dim() != 1 or out.shape[0] != n:
+        raise ValueError("sample_rows: out must be int64 (batch,) on the device of logits")
+    p = K.SampleRows(logits=K.T(logits), top_k=_ptr(top_k, torch.int32, n, "top_k", dev), top_p=_ptr(top_p, torch.float32, n, "top_p", dev),
+                     temperature=_ptr(temperature, torch.float32, n, "temperature", dev), min_p=_ptr(min_p, torch.float32, n, "min_p", dev),
+                     seeds=_ptr(seeds, torch.int64, n, "seeds", dev), steps=_ptr(steps, torch.int64, n, "steps", dev),
+                     penalty=_ptr(penalty, torch.float32, n, "penalty", dev), history_lens=_ptr(history_lens, torch.int32, n, "history_lens", dev),
+                     active=_ptr(active, torch.int32, n, "active", dev))
+    if history is not None:
+        if history.dtype != torch.int64 or history.device != dev or history.dim() != 2 or history.shape[0] != n or (history.shape[1] > 1 and history.stride(1) != 1):
+            raise ValueError("sample_rows: history must be int64 (batch, cap) with unit last stride on the device of logits")
+        p.history, p.history_stride, p.history_cap = history.data_ptr(), history.stride(0), history.shape[1]
+    p.out_ids.data = out.data_ptr()
+    p.out_ids.ndim = 1
+    p.out_ids.shape[0] = n
+    p.out_ids.stride[0] = out.stride(0)
+    if K.try_run(lib, "omk_sample_rows", p, logits):
+        return out
+    # the vocabulary does not fit the kernel's id map: penalise a copy with torch (a mask of the history ids -- every write is True, so
+    # duplicates and the order of the writes do not matter; dead entries go to a spare column) and draw without history
+    V, cap = logits.shape[1], history.shape[1]
+    live = (torch.arange(cap, device=dev)[None] < history_lens[:, None]) & (history >= 0) & (history < V)
+    mask = torch.zeros(n, V + 1, dtype=torch.bool, device=dev).scatter_(1, torch.where(live, history, torch.full_like(history, V)), True)[:, :V]
+    pen = torch.where(penalty > 0, penalty, torch.ones_like(penalty))[:, None]
+    lf = logits.float()
+    work = torch.where(mask, torch.where(lf < 0, lf * pen, lf / pen).to(logits.dtype), logits)
+    p.logits = K.T(work)
+    p.penalty = p.history = p.history_lens = None
+    K.run(lib, "omk_sample_rows", p, logits)
     return out

@@ -236,6 +236,7 @@ def bench_decode_mmu_batch(args, dev):
         with _AdmissionClock() as clk:
             model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
         burst = clk.first_token_s[:min(args.max_batch, len(qs))]
+        samp = _sampling_variants(args, model, feats, qs, lens, n_tok, opts) if args.sampling == "mixed" else {}
         got = [r.shape[1] for r in rag]
         assert got == [4 + q.shape[1] + n for q, n in zip(qs, new)], got
         same = None if seq is None else sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
@@ -248,9 +249,38 @@ def bench_decode_mmu_batch(args, dev):
                           "ragged_tokens_per_s": round(n_tok / t_rag, 1), "ragged_tokens_per_s_all": [round(n_tok / t, 1) for t in t_rags],
                           "speedup": None if t_seq is None else round(t_seq / t_rag, 2), "requests_with_identical_ids": same,
                           "admission_s": round(clk.seconds, 3), "first_token_first_request_ms": round(burst[0] * 1e3, 1),
-                          "first_token_last_of_burst_ms": round(burst[-1] * 1e3, 1)}), flush=True)
+                          "first_token_last_of_burst_ms": round(burst[-1] * 1e3, 1), **samp}), flush=True)
         del model
         torch.cuda.empty_cache()
+
+
+def _sampling_variants(args, model, feats, qs, lens, n_tok, opts):
+    """--sampling mixed: the ragged run (same requests, no EOS: the same number of tokens) with (1) top_k = 20 for the whole call through
+    the old path (generation.sample: one omk_sample launch per step), (2) top_k = 20 for every request through the row-wise launch
+    (sampling=SamplingParams: the cost of the new path alone) and (3) mixed per-request settings -- greedy, top-k 20 with top-p, the
+    whole vocabulary behind top-p, top-k 20 with a repetition penalty, the whole vocabulary behind min_p, in turn.  The variants
+    alternate, --reps times each (every time is printed); ragged_tokens_per_s of the same line is the greedy run."""
+    from omnimamba_amd.sampling import SamplingParams as SP
+    kinds = [SP(), SP(top_k=20, top_p=0.9), SP(top_k=0, top_p=0.9), SP(top_k=20, repetition_penalty=1.3), SP(top_k=0, min_p=0.05)]
+    from dataclasses import replace
+    mixed = [replace(kinds[i % len(kinds)], seed=1000 + i) for i in range(len(qs))]
+    uni = [SP(top_k=20, seed=1000 + i) for i in range(len(qs))]
+    runs = {"uniform_top_k20_old_path": dict(top_k=20), "uniform_top_k20_row_wise": dict(sampling=uni), "mixed_row_wise": dict(sampling=mixed)}
+    times = {k: [] for k in runs}
+    for k, kw in runs.items():       # warm-up: the setting tensors of every bucket, the history buffer
+        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts, **kw)
+    torch.cuda.synchronize()
+    for _ in range(max(args.reps, 1)):
+        for k, kw in runs.items():
+            t0 = time.perf_counter()
+            model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts, **kw)
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    out = {}
+    for k, ts in times.items():
+        out[k + "_tokens_per_s"] = round(n_tok / sorted(ts)[len(ts) // 2], 1)
+        out[k + "_tokens_per_s_all"] = [round(n_tok / t, 1) for t in ts]
+    return {"sampling": out}
 
 
 def bench_step_index_cost(args, dev):
@@ -456,6 +486,8 @@ def main():
     ap.add_argument("--turn2-ids", type=int, default=24, help="mmu_followup: ids of the second question (with the pending id: up to mamba2.EXTEND_SCAN_MAX_T "
                                                                   "positions take the extend kernel, more the chunked scan)")
     ap.add_argument("--extend-batch", type=int, default=1, help="mmu_followup: also time mmu_continue with this many turns per grouped extend (1 = off)")
+    ap.add_argument("--sampling", choices=["greedy", "mixed"], default="greedy",
+                    help="decode_mmu_batch: mixed = also time uniform top_k 20 (old path) and per-request settings (row-wise launch)")
     ap.add_argument("--reps", type=int, default=1, help="decode_mmu_batch: timed repetitions of the ragged run")
     ap.add_argument("--dtypes", default="f32,bf16", help="decode_mmu_batch: weight dtypes to run")
     ap.add_argument("--no-sequential", action="store_true", help="decode_mmu_batch: skip the sequential mmu_generate baseline")
