@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 14
+#define OMK_ABI_VERSION 15
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
@@ -524,6 +524,31 @@ typedef struct {
   int64_t history_cap;       /* width of history */
 } OmkSampleRows;
 int omk_sample_rows(const OmkSampleRows* p, omk_stream stream);
+
+/* ---- ABI 15: log-probabilities of the tokens a decode step sampled, the top_n most likely tokens of every row and the sampled token's rank ----
+ * One launch, one workgroup per row, a launch of its own behind the sampler (the sampler kernels are not touched); nothing is read from
+ * the host, so a captured step replays it while logits, ids and active are rewritten in between.  All values are those of the RAW row:
+ * no temperature, filter or repetition penalty (what serving APIs report by default).
+ *   lse        = m + log(sum_v exp(x_v - m)), x in fp32, m the row maximum; the sum runs in a fixed order that depends on neither the row's
+ *                index nor the batch size: the outputs of a row are the same bits wherever it sits
+ *   logprob[b] = x[ids[b]] - lse
+ *   The tokens of a row are ordered by (value descending, index ascending): top_ids / top_logprobs hold the first top_n of that order, entries
+ *   past vocab (top_n > vocab) id -1 and logprob -inf; rank[b] is the 1-based position of ids[b] in it.
+ * Nothing in ids is trusted: an id outside [0, vocab) gives logprob NaN and rank 0 and reads nothing.  A -inf logit scores -inf.  A row whose
+ * maximum is -inf, or that holds a NaN, gives unspecified values in bounded time; the mutual order of -0 and +0 is unspecified.
+ * active[b] == 0 (optional; the padding rows of a bucket): the row writes nothing and none of its inputs has an effect.
+ * ids == NULL: top_n only (logprob and rank are not written); with ids, logprob is required and rank optional.                          */
+typedef struct {
+  OmkTensor logits;          /* (rows, vocab) f32 / bf16 / f16, unit last stride, any row stride; read only */
+  OmkTensor logprob;         /* out (rows) f32, any stride; required with ids */
+  OmkTensor rank;            /* out (rows) int32, any stride; optional */
+  OmkTensor top_ids;         /* out (rows, top_n) int64, any strides (dtype field ignored); required with top_n > 0 */
+  OmkTensor top_logprobs;    /* out (rows, top_n) f32, any strides; required with top_n > 0 */
+  const void* ids;           /* optional device int64 (rows): the token to score in each row */
+  const void* active;        /* optional device int32 (rows); NULL = every row */
+  int32_t top_n;             /* 0 .. 64 */
+} OmkTokenLogprobs;
+int omk_token_logprobs(const OmkTokenLogprobs* p, omk_stream stream);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,8 @@ import torch
 
 from . import generation as G
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
-from .sampling import SamplingParams, pack_rows, sample_rows
+from . import sampling as _sampling
+from .sampling import SamplingParams, TokenLogprobs, pack_rows, sample_rows
 
 
 @dataclass
@@ -183,6 +184,58 @@ class _RowSampler:
         return toks.clone()      # (`out` is the bucket's static buffer: the next step overwrites it)
 
 
+class _LogprobLog:
+    """decode_ragged(logprobs=...): every draw of the call is followed by ONE sampling.token_logprobs launch over the logits the draw saw
+    and the ids it produced, at the largest N among the requests of its rows that asked for a record (none asked: no launch).  What a
+    launch returns stays on the device, one part per draw in the order of `drawn`, and is cut into the requests' records through
+    `pieces` at the end, as the ids are: nothing here reads the device."""
+
+    def __init__(self, want, dev):
+        self.want, self.dev = want, dev               # per request: None, or its N
+        self.nmax = max([w for w in want if w is not None], default=0)
+        self.parts = []                               # per draw: (rows, N, TokenLogprobs or None)
+
+    def note(self, logits, ids, reqs, active=None):
+        """logits (rows, vocab) and ids (rows,) of one draw whose first len(reqs) rows belong to the requests `reqs`; active: the int32
+        flags of the rows when logits and ids are those of a whole bucket (its padding rows are 0)."""
+        ns = [self.want[i] for i in reqs if self.want[i] is not None]
+        if not ns:
+            self.parts.append((len(reqs), 0, None))
+            return
+        self.parts.append((len(reqs), max(ns), _sampling.token_logprobs(logits, ids, top_n=max(ns), active=active)))
+
+    def records(self, pieces):
+        """One TokenLogprobs per request (None where none was asked for), row j of it for the request's j-th sampled id."""
+        dev, nmax = self.dev, self.nmax
+        lp, rk, ti, tl = [], [], [], []
+        for rows, n, r in self.parts:
+            if r is None:
+                lp.append(torch.zeros(rows, device=dev))
+                rk.append(torch.zeros(rows, dtype=torch.int32, device=dev))
+            else:
+                lp.append(r.logprob[:rows])
+                rk.append(r.rank[:rows])
+            if nmax:
+                a = torch.full((rows, nmax), -1, dtype=torch.long, device=dev) if n < nmax else r.top_ids[:rows]
+                b = torch.full((rows, nmax), float("-inf"), device=dev) if n < nmax else r.top_logprobs[:rows]
+                if 0 < n < nmax:
+                    a[:, :n] = r.top_ids[:rows]
+                    b[:, :n] = r.top_logprobs[:rows]
+                ti.append(a)
+                tl.append(b)
+        lp, rk = torch.cat(lp), torch.cat(rk)
+        ti = torch.cat(ti) if nmax else torch.zeros(lp.shape[0], 0, dtype=torch.long, device=dev)
+        tl = torch.cat(tl) if nmax else torch.zeros(lp.shape[0], 0, device=dev)
+        out = []
+        for w, pc in zip(self.want, pieces):
+            if w is None:
+                out.append(None)
+                continue
+            idx = torch.tensor(pc, dtype=torch.long).to(dev)
+            out.append(TokenLogprobs(logprob=lp[idx], rank=rk[idx], top_ids=ti[idx, :w], top_logprobs=tl[idx, :w]))
+        return out
+
+
 def _pool_cache(model, max_batch, max_seqlen, task, cg):
     """The slot pool and the per-bucket steps, kept on the model under the rule of generation.decode's `_decoding_cache`: a new device,
     dtype or task, or a larger max_batch / max_length, drops them."""
@@ -313,7 +366,7 @@ def _save(c, slot, seqlen, pending_id, task):
 
 @torch.inference_mode()
 def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
-                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None):
+                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None, logprobs=None):
     """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
     generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
     model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
@@ -340,10 +393,27 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     penalty over its input_ids and sampled ids among them) and its own random stream -- its n-th sampled id of this call is drawn at
     position step0 + n of its seed, so its ids do not depend on which requests share its steps, on max_batch or on the admission
     order.  Every draw (prefill, extend, grouped or not, and the step) is one row-wise launch (sampling.sample_rows); top_k, top_p,
-    min_p and temperature are not read.  A follow-up turn continues its stream when it is given step0 = the ids drawn so far."""
+    min_p and temperature are not read.  A follow-up turn continues its stream when it is given step0 = the ids drawn so far.
+
+    logprobs: None -- off.  An int N in [0, 64] for every request, or a list with one entry per request (an int, or None for a request
+    that wants no record): the call returns ONE MORE element behind what it returns otherwise (ids_list, logprobs_list) or (ids_list,
+    states_list, logprobs_list) -- per request a sampling.TokenLogprobs (None where none was asked for) whose rows are aligned with the
+    request's n_i sampled ids, EOS included: logprob (n_i,) and rank (n_i,) of the sampled id, top_ids and top_logprobs (n_i, N_i), the N_i
+    most likely tokens (N = 0: shape (n_i, 0)).  All of the RAW logits the draw saw: no temperature, filter or repetition penalty (a greedy
+    request has rank 1 everywhere).  Every draw is followed by one sampling.token_logprobs launch at the largest N among its rows; the
+    results stay on the device (the model's) until the call returns, no host synchronisation is added, and with cg the launch reads the
+    bucket's static logits before the next replay.  The sampled ids and the states are those of the call without logprobs."""
     n = len(requests)
+    if logprobs is not None:
+        want = [logprobs] * n if isinstance(logprobs, int) else list(logprobs)
+        if len(want) != n:
+            raise ValueError(f"decode_ragged: logprobs is None, an int or a list of {n}, one entry per request")
+        for w in want:
+            if w is not None and not (isinstance(w, int) and 0 <= w <= _sampling.MAX_TOP_N):
+                raise ValueError(f"decode_ragged: a logprobs entry is None or an int in [0, {_sampling.MAX_TOP_N}], got {w!r}")
     if n == 0:
-        return ([], []) if return_states else []
+        empty = ([], []) if return_states else []
+        return empty if logprobs is None else ((*empty, []) if return_states else ([], []))
     lens = [int(max_length)] * n if isinstance(max_length, int) else [int(m) for m in max_length]
     if len(lens) != n:
         raise ValueError(f"decode_ragged: {len(lens)} max_length values for {n} requests")
@@ -382,6 +452,14 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     # the first id(s) of the requests `reqs` admitted into `slots`, from their prefill / extend logits
     draw = lambda lg, reqs, slots: (sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature) if rs is None
                                     else rs.admit(reqs, slots, lg))
+    lp = None if logprobs is None else _LogprobLog(want, dev)
+    if lp is not None:
+        draw_ids = draw
+
+        def draw(lg, reqs, slots):
+            toks = draw_ids(lg, reqs, slots)
+            lp.note(lg, toks, reqs)
+            return toks
     last = torch.zeros(c["max_batch"], dtype=torch.long, device=dev)   # last sampled id of every slot: the next step's input
     drawn, n_drawn = [], 0               # every sampled id tensor in order, and how many ids they hold
     pieces = [[] for _ in range(n)]      # per request: the positions of its ids in cat(drawn), in sampling order
@@ -466,9 +544,15 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
         bk.position_ids.copy_(torch.tensor([[off] for _, _, off in live] + [[0]] * pad, dtype=torch.long), non_blocking=True)
         bk.slots.copy_(torch.tensor(slots_h + [-1] * pad, dtype=torch.int32), non_blocking=True)
         if rs is None:
-            toks = sample(bk.run()[: len(live)], top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+            lg = bk.run()[: len(live)]
+            toks = sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature)
+            if lp is not None:
+                lp.note(lg, toks, [i for i, _, _ in live])
         else:
-            toks = rs.step(bk, live, rows, bk.run())
+            lg = bk.run()
+            toks = rs.step(bk, live, rows, lg)
+            if lp is not None:     # (the bucket's rows: the ids are still in the sampler's static buffer, the padding rows are inactive)
+                lp.note(lg, bk.samp["out"], [i for i, _, _ in live], active=bk.samp["active"])
         last.index_copy_(0, rows[: len(live)], toks)
         toks_h = toks.tolist() if check_eos else None
         still = []
@@ -486,4 +570,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     flat = torch.cat(drawn)
     out = [torch.cat([r[0], flat[torch.tensor(pieces[i], device=dev)].view(1, -1).to(r[0].device)], dim=1)
            for i, r in enumerate(requests)]
-    return (out, states) if return_states else out
+    res = (out, states) if return_states else out
+    if lp is None:
+        return res
+    recs = lp.records(pieces)
+    return (out, states, recs) if return_states else (out, recs)

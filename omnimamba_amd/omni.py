@@ -205,7 +205,8 @@ class OmniMambaPath(nn.Module):
 
     @torch.no_grad()
     def mmu_generate_batch(self, images_feat_list, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1,
-                           top_p=0.0, max_batch=8, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, sampling=None):
+                           top_p=0.0, max_batch=8, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, sampling=None,
+                           logprobs=None):
         """Many MMU requests at once (continuous batching, omnimamba_amd/batch_decode.py): request i is images_feat_list[i] (1, n_img,
         fused_vision_dim) with the question input_ids_list[i] (1, T_i), its prompt built as in mmu_generate.  max_length: an int or one
         per request.  Returns one id tensor per request, each equal to what mmu_generate returns for that request alone.
@@ -214,18 +215,21 @@ class OmniMambaPath(nn.Module):
         are the suggested values for MMU prompts; DESIGN.md 4.5 says what was measured).
         sampling: one sampling.SamplingParams for every request or a list with one per request -- each request sampled with its own
         settings, repetition penalty and random stream in the shared steps (decode_ragged); temperature, top_k and
-        top_p are not read then."""
+        top_p are not read then.
+        logprobs: an int N in [0, 64] for every request, or a list with one entry (N or None) per request: the call returns one more
+        element, per request a sampling.TokenLogprobs aligned with its sampled ids -- the log-probability and rank of each sampled id and
+        the N most likely tokens of each step, of the raw logits (decode_ragged).  None: off."""
         from .batch_decode import decode_ragged
         if len(images_feat_list) != len(input_ids_list):
             raise ValueError("mmu_generate_batch: one images_feat per question")
         reqs = [self._mmu_prompt(f, q) for f, q in zip(images_feat_list, input_ids_list)]
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
                              top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=return_states,
-                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, sampling=sampling)
+                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, sampling=sampling, logprobs=logprobs)
 
     @torch.no_grad()
     def mmu_continue(self, states, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1, top_p=0.0, max_batch=8,
-                     cg=True, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None):
+                     cg=True, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None, logprobs=None):
         """The follow-up turn of each conversation: states[i] is the DecodeState its previous turn returned (mmu_generate_batch or
         mmu_continue with states), input_ids_list[i] (1, T_i) the new turn's ids, already templated by the caller.  The conversation is
         not re-prefilled: the state takes the previous turn's last sampled id and the new ids (text only, embedded with
@@ -234,14 +238,16 @@ class OmniMambaPath(nn.Module):
         DecodeState for the turn after.  prefill_batch / prefill_bucket are accepted and passed on; a continued request is extended, never
         prefilled, so they change nothing here.  extend_batch > 1: up to that many conversations that find a free slot at the same moment
         are extended by one right-padded pass (decode_ragged; off by default, DESIGN.md 4.6 says what was measured).
-        sampling: as in mmu_generate_batch; a conversation continues its random stream with step0 = the ids its earlier turns sampled."""
+        sampling: as in mmu_generate_batch; a conversation continues its random stream with step0 = the ids its earlier turns sampled.
+        logprobs: as in mmu_generate_batch; the call then returns (ids, states, logprobs), the records covering this turn's sampled ids."""
         from .batch_decode import decode_ragged
         if len(states) != len(input_ids_list):
             raise ValueError("mmu_continue: one state per conversation")
         reqs = [(q, self.llm_backbone.embed_input_ids(q), st) for st, q in zip(states, input_ids_list)]
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
                              top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=True,
-                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, extend_batch=extend_batch, sampling=sampling)
+                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, extend_batch=extend_batch, sampling=sampling,
+                             logprobs=logprobs)
 
     # ---- T2I generation (omnimamba.py:311-337 minus the VQ decoder network)
     @torch.no_grad()

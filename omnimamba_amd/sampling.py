@@ -92,11 +92,11 @@ def pack_rows(params_list: Sequence[SamplingParams], device) -> dict:
     return {"top_k": k, "top_p": f[0], "temperature": f[1], "min_p": f[2], "penalty": f[3], "seeds": i[0], "steps": i[1]}
 
 
-def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev):
+def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev, what: str = "sample_rows"):
     if t is None:
         return None
     if t.dtype != dtype or t.device != dev or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
-        raise ValueError(f"sample_rows: {name} must be a dense {dtype} tensor of ({n},) on {dev}")
+        raise ValueError(f"{what}: {name} must be a dense {dtype} tensor of ({n},) on {dev}")
     return t.data_ptr()
 
 
@@ -143,3 +143,71 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
     p.penalty = p.history = p.history_lens = None
     K.run(lib, "omk_sample_rows", p, logits)
     return out
+
+
+# ---- log-probabilities behind the sampler (omk_token_logprobs, ABI 15) ------------------------------------------------------------------
+
+MAX_TOP_N = 64
+
+
+@dataclass
+class TokenLogprobs:
+    """What token_logprobs returns; a field that was not asked for is None.  logprob (rows,) float32 and rank (rows,) int32: of the given
+    ids; top_ids (rows, top_n) int64 and top_logprobs (rows, top_n) float32: the top_n most likely tokens of every row."""
+    logprob: Optional[torch.Tensor] = None
+    rank: Optional[torch.Tensor] = None
+    top_ids: Optional[torch.Tensor] = None
+    top_logprobs: Optional[torch.Tensor] = None
+
+
+def _desc(t: torch.Tensor) -> K.OmkTensor:
+    """Descriptor of an int64 tensor (the C side knows what it points to: its dtype field is not read)."""
+    o = K.OmkTensor()
+    n = t.dim()
+    o.data, o.ndim = t.data_ptr(), n
+    o.shape[:n] = t.shape
+    o.stride[:n] = t.stride()
+    return o
+
+
+def token_logprobs(logits: torch.Tensor, ids: Optional[torch.Tensor] = None, *, top_n: int = 0, active: Optional[torch.Tensor] = None,
+                   out: Optional[TokenLogprobs] = None) -> TokenLogprobs:
+    """(rows, vocab) logits -> the log-probabilities of the RAW rows (no temperature, filter or penalty) in ONE launch:
+    ids (int64 (rows,)) given: logprob[b] = log_softmax(logits[b])[ids[b]] and rank[b], the 1-based position of ids[b] among the row's
+    tokens ordered by (value descending, index ascending); an id outside [0, vocab) gives NaN and rank 0.  top_n in [1, 64]: top_ids and
+    top_logprobs, the first top_n tokens of that order (entries past vocab: id -1, -inf).  active (int32 (rows,)): rows with 0 write
+    nothing.  out: a TokenLogprobs of buffers to write into (any strides; fields left None are allocated) -- the static buffers of a
+    captured launch.  A row's outputs do not depend on its place in the batch.  No host read: capturable, and logits, ids and active may be
+    rewritten between replays."""
+    lib = get_lib()
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("token_logprobs: logits must be (rows, vocab) with unit last stride")
+    n, dev = logits.shape[0], logits.device
+    top_n = int(top_n)
+    if not 0 <= top_n <= MAX_TOP_N:
+        raise ValueError(f"token_logprobs: top_n must be in [0, {MAX_TOP_N}], got {top_n}")
+    if ids is None and top_n == 0:
+        raise ValueError("token_logprobs: nothing to do: give ids, top_n > 0 or both")
+    o = out if out is not None else TokenLogprobs()
+    res = TokenLogprobs()
+
+    def buf(t, shape, dtype, name):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev)
+        if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape:
+            raise ValueError(f"token_logprobs: out.{name} must be a {dtype} tensor of {shape} on {dev}")
+        return t
+
+    p = K.TokenLogprobs(logits=K.T(logits), top_n=top_n, ids=_ptr(ids, torch.int64, n, "ids", dev, "token_logprobs"),
+                        active=_ptr(active, torch.int32, n, "active", dev, "token_logprobs"))
+    if ids is not None:
+        res.logprob = buf(o.logprob, (n,), torch.float32, "logprob")
+        res.rank = buf(o.rank, (n,), torch.int32, "rank")
+        p.logprob, p.rank = K.T(res.logprob), K.T(res.rank)
+    if top_n > 0:
+        res.top_ids = buf(o.top_ids, (n, top_n), torch.int64, "top_ids")
+        res.top_logprobs = buf(o.top_logprobs, (n, top_n), torch.float32, "top_logprobs")
+        p.top_ids, p.top_logprobs = _desc(res.top_ids), K.T(res.top_logprobs)
+    if n > 0:               # (an empty tensor has no data pointer to describe)
+        K.run(lib, "omk_token_logprobs", p, logits)
+    return res

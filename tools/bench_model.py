@@ -237,6 +237,8 @@ def bench_decode_mmu_batch(args, dev):
             model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
         burst = clk.first_token_s[:min(args.max_batch, len(qs))]
         samp = _sampling_variants(args, model, feats, qs, lens, n_tok, opts) if args.sampling == "mixed" else {}
+        if args.logprobs is not None:
+            samp.update(_logprobs_variant(args, model, feats, qs, lens, n_tok, opts, rag))
         got = [r.shape[1] for r in rag]
         assert got == [4 + q.shape[1] + n for q, n in zip(qs, new)], got
         same = None if seq is None else sum(int(torch.equal(r, s_)) for r, s_ in zip(rag, seq))
@@ -281,6 +283,29 @@ def _sampling_variants(args, model, feats, qs, lens, n_tok, opts):
         out[k + "_tokens_per_s"] = round(n_tok / sorted(ts)[len(ts) // 2], 1)
         out[k + "_tokens_per_s_all"] = [round(n_tok / t, 1) for t in ts]
     return {"sampling": out}
+
+
+def _logprobs_variant(args, model, feats, qs, lens, n_tok, opts, rag):
+    """--logprobs N: the greedy ragged run with logprobs=N for every request (one token_logprobs launch behind every draw, the records
+    assembled at the end) alternating with the same run without, --reps times each (every time is printed).  The ids must be those of
+    the run without."""
+    kw = dict(max_length=lens, max_batch=args.max_batch, cg=True, **opts)
+    ids, recs = model.mmu_generate_batch(feats, qs, logprobs=args.logprobs, **kw)       # warm-up
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(ids, rag)) and all(r.logprob.shape[0] == n for r, n in zip(recs, [o.shape[1] - 4 - q.shape[1] for o, q in zip(ids, qs)]))
+    times = {"without": [], "with": []}
+    for _ in range(max(args.reps, 1)):
+        for k, extra in (("without", {}), ("with", dict(logprobs=args.logprobs))):
+            t0 = time.perf_counter()
+            model.mmu_generate_batch(feats, qs, **kw, **extra)
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    med = {k: sorted(ts)[len(ts) // 2] for k, ts in times.items()}
+    return {"logprobs": {"top_n": args.logprobs, "tokens_per_s": round(n_tok / med["with"], 1),
+                         "tokens_per_s_all": [round(n_tok / t, 1) for t in times["with"]],
+                         "without_tokens_per_s": round(n_tok / med["without"], 1),
+                         "without_tokens_per_s_all": [round(n_tok / t, 1) for t in times["without"]],
+                         "ms_per_call": round((med["with"] - med["without"]) * 1e3, 1)}}
 
 
 def bench_step_index_cost(args, dev):
@@ -488,6 +513,7 @@ def main():
     ap.add_argument("--extend-batch", type=int, default=1, help="mmu_followup: also time mmu_continue with this many turns per grouped extend (1 = off)")
     ap.add_argument("--sampling", choices=["greedy", "mixed"], default="greedy",
                     help="decode_mmu_batch: mixed = also time uniform top_k 20 (old path) and per-request settings (row-wise launch)")
+    ap.add_argument("--logprobs", type=int, default=None, help="decode_mmu_batch: also time the greedy run with logprobs=N (token_logprobs behind every draw)")
     ap.add_argument("--reps", type=int, default=1, help="decode_mmu_batch: timed repetitions of the ragged run")
     ap.add_argument("--dtypes", default="f32,bf16", help="decode_mmu_batch: weight dtypes to run")
     ap.add_argument("--no-sequential", action="store_true", help="decode_mmu_batch: skip the sequential mmu_generate baseline")
