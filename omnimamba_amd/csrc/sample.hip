@@ -22,7 +22,7 @@
 // The reference draws with torch.multinomial; the streams differ, the distribution is the same (tests: chi-square at fixed
 // seeds, bit-exact ids for top_k == 1).
 #include <atomic>
-#include "omk_common.h"
+#include "sample_select.h"
 
 namespace omk {
 
@@ -45,20 +45,7 @@ __device__ __forceinline__ void philox4x32(uint32_t (&c)[4], uint32_t k0, uint32
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
 }
-// order-preserving key: larger float <-> larger unsigned (NaN sorts above +inf; -0 below +0)
-__device__ __forceinline__ uint32_t fkey(float f) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-#ifdef OMK_EMU
-__device__ __forceinline__ uint32_t lds_fetch_add_u32(uint32_t* p, uint32_t v) { const uint32_t o = *p; *p = o + v; return o; }
-__device__ __forceinline__ void lds_add_u64(unsigned long long* p, unsigned long long v) { *p += v; }
-#else
-__device__ __forceinline__ uint32_t lds_fetch_add_u32(uint32_t* p, uint32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void lds_add_u64(unsigned long long* p, unsigned long long v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-#endif
-constexpr int SAMPLE_KMAX = 64;
+constexpr int SAMPLE_KMAX = SELECT_NMAX;
 // threads / waves per row of logits (round 6: 256 -> 1024, typed loads, four requests in flight per lane in every pass: the kernel is a chain
 // of passes over one row from L2, bound by latency -- profiles/r06_sampler.txt).  The CPU emulator runs the same code with 256 (it executes the
 // lanes one after the other: sixteen waves per row would make the CPU suite four times slower for nothing).
@@ -88,64 +75,65 @@ __device__ __forceinline__ T block_incl_scan(T v, T* buf, int tid) {
   return r;
 }
 
-// inclusive scan over the lanes of a wave (any additive type the shuffles move)
-template <class T> __device__ __forceinline__ T wave_incl_scan_t(T v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const T o = shfl(v, lane >= off ? lane - off : lane); if (lane >= off) v += o; }
-  return v;
-}
-// The digit walk of a radix pass by ONE WAVE instead of one thread (a thread reading 60 - 190 counters one after the other was 2 - 8 us per pass):
-// cnt(r) for r = 0 .. 255 in WALK order, lane l holds r = 4 l .. 4 l + 3; returns in every lane the first r whose running total reaches `need`
-// by the rule `total before + cnt(r) > limit` (limit = need - 1 for "covers need keys"), and the total BEFORE it; r = 255 when none does.
-template <class T, class F> __device__ __forceinline__ void wave_find_digit(F cnt, T limit, int lane, uint32_t& r_out, T& before_out) {
-  T c[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) { c[j] = cnt(4 * lane + j); s += c[j]; }
-  const T incl = wave_incl_scan_t<T>(s, lane);
-  T run = incl - s;
-  int jj = -1; T bef = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) { if (jj < 0 && run + c[j] > limit) { jj = j; bef = run; } run += c[j]; }
-#ifdef OMK_EMU
-  const unsigned long long m = emu::ballot(jj >= 0 ? 1 : 0);
-#else
-  const unsigned long long m = __builtin_amdgcn_ballot_w64(jj >= 0);
-#endif
-  if (m) {
-    const int l0 = __builtin_ctzll(m);
-    r_out = (uint32_t)(4 * l0 + shfl(jj, l0));
-    before_out = shfl(bef, l0);
-  } else {   // (the walk ends on the last digit: everything in front of it is "before")
-    r_out = 255u;
-    before_out = shfl(incl, 63) - shfl(c[3], 63);
-  }
-}
-
-// The settings of ONE row of omk_sample_rows, uniform over its workgroup: the row's entries of the device arrays.  c0 is the first Philox
-// counter word (0: the row index is not in the counter, see include/omk.h).
+// The settings of one row, uniform over its workgroup, in the two forms sample_row takes them in.  Both fill the four Philox counter
+// words themselves: (first word, step low, step high, 0).
+// omk_sample_rows: the row's entries of the device arrays.  c0 is the first counter word (0: the row index is not in the counter, see
+// include/omk.h).
 struct RowCfg {
   int top_k; float top_p, inv_temp, min_p;
   unsigned long long seed, step; uint32_t c0;
   float pen;   // PEN only: what the logits marked in the id map are multiplied with (negative ones) / divided by
+  int64_t* out;   // where the row's id goes
+  __device__ __forceinline__ void philox_counter(uint32_t (&cc)[4]) const {
+    cc[0] = c0; cc[1] = (uint32_t)step; cc[2] = (uint32_t)(step >> 32); cc[3] = 0u;
+  }
+  __device__ __forceinline__ void put(int64_t id) const { out[0] = id; }
+};
+// omk_sample: the kernel arguments of the whole batch and the row index, which is the first counter word.  The device counter is read
+// HERE, at the draw, behind every pass over the row: the captured step advances it on the same stream in front of the launch.
+struct BatchCfg {
+  int top_k; float top_p, inv_temp, min_p;
+  unsigned long long seed; const int64_t* counter; unsigned long long offset; int64_t* out; int row;
+  static constexpr float pen = 1.f;
+  __device__ __forceinline__ void philox_counter(uint32_t (&cc)[4]) const {
+    const unsigned long long step = (counter ? (unsigned long long)counter[0] : 0ull) + offset;
+    cc[0] = (uint32_t)row; cc[1] = (uint32_t)step; cc[2] = (uint32_t)(step >> 32); cc[3] = 0u;
+  }
+  // (indexed at every exit of the body.  Through a pointer made beforehand the compiler folds the exits into one store at the end of the
+  // function, and that build measured +0.5 / +0.9 us a launch: profiles/sampler_one_body.txt section 3)
+  __device__ __forceinline__ void put(int64_t id) const { out[row] = id; }
 };
 
-// One row of logits -> one id, by the whole workgroup.  PEN: `pmap` (LDS, one byte per token) marks the ids of the row's history; the
-// loader penalises a marked logit and rounds it to T as the in-place torch version does, so every pass sees the same penalised row.
-template <class T, bool PEN>
-__device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* outp, const RowCfg a, const unsigned char* pmap) {
-  // The branches are exclusive, so their large buffers share two raw blocks (they were 69 KB as separate arrays):
-  //   rawA  hist (top-k select)  |  hm8 + hc8 (whole-vocabulary top-p)
-  //   rawB  sc64, sc32 (one after the other: a block scan ends with a barrier)  |  scf (plain whole-vocabulary draw)
-  // hist / hm8 / hc8: eight copies of every counter, picked by the lane: the keys of a row share their top byte(s), and 64 lanes adding to ONE
-  // LDS address are 64 serial atomics (copy c of digit d lives at 8 d + c: the copies of a digit sit in different banks)
-  __shared__ __attribute__((aligned(16))) unsigned long long rawA[256 * 8 + 256 * 4];
-  __shared__ __attribute__((aligned(16))) unsigned long long rawB[2 * SNT];
-  uint32_t* const hist = (uint32_t*)rawA;
-  unsigned long long* const hm8 = rawA;
-  uint32_t* const hc8 = (uint32_t*)(rawA + 256 * 8);
-  unsigned long long* const sc64 = rawB;
-  uint32_t* const sc32 = (uint32_t*)rawB;
-  float* const scf = (float*)rawB;
+// One row of logits -> one id, by the whole workgroup: the one implementation behind omk_sample and omk_sample_rows.  PEN: `pmap` (LDS, one
+// byte per token) marks the ids of the row's history; the loader penalises a marked logit and rounds it to T as the in-place torch version
+// does, so every pass sees the same penalised row.  ALIASED picks the layout of the large LDS buffers, Cfg is RowCfg or BatchCfg.
+template <class T, bool PEN, bool ALIASED, class Cfg>
+__device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg a, const unsigned char* pmap) {
+  // hist / hm8 / hc8: the counters of the radix passes, eight copies of every counter, picked by the lane: the keys of a row share their top
+  // byte(s), and 64 lanes adding to ONE LDS address are 64 serial atomics (copy c of digit d lives at 8 d + c: the copies of a digit sit in
+  // different banks).  sc64 / sc32 / scf: the buffers of the block scans.  Two layouts:
+  //   ALIASED (omk_sample_rows, 44 792 B)  the branches are exclusive, so their buffers share two raw blocks:
+  //              rawA  hist (top-k select)  |  hm8 + hc8 (whole-vocabulary top-p)
+  //              rawB  sc64, sc32 (one after the other: a block scan ends with a barrier)  |  scf (plain whole-vocabulary draw)
+  //            which leaves room for the id map of the penalty launch (50 288 B at the MMU vocabulary) next to them
+  //   separate (omk_sample, 69 368 B)      an array each, as omk_sample always had.  It sits inside captured decode steps and has no id map
+  //            to make room for, and this is the layout its per-launch time was measured with: not slower than the kernel it had to
+  //            itself (profiles/sampler_one_body.txt section 3).  The aliased layout has not been measured for it on its own.
+  // (a __shared__ array of the branch that is not taken is not allocated)
+  uint32_t *hist, *hc8, *sc32;
+  unsigned long long *hm8, *sc64;
+  float* scf;
+  if constexpr (ALIASED) {
+    __shared__ __attribute__((aligned(16))) unsigned long long rawA[256 * 8 + 256 * 4];
+    __shared__ __attribute__((aligned(16))) unsigned long long rawB[2 * SNT];
+    hist = (uint32_t*)rawA; hm8 = rawA; hc8 = (uint32_t*)(rawA + 256 * 8);
+    sc64 = rawB; sc32 = (uint32_t*)rawB; scf = (float*)rawB;
+  } else {
+    __shared__ uint32_t hist_s[256 * 8], hc8_s[256 * 8], sc32_s[2 * SNT];
+    __shared__ unsigned long long hm8_s[256 * 8], sc64_s[2 * SNT];
+    __shared__ float scf_s[2 * SNT];
+    hist = hist_s; hm8 = hm8_s; hc8 = hc8_s; sc64 = sc64_s; sc32 = sc32_s; scf = scf_s;
+  }
   __shared__ uint32_t sel_prefix, sel_need, n_gt, n_eq;
   __shared__ float cval[SAMPLE_KMAX];
   __shared__ int cidx[SAMPLE_KMAX];
@@ -181,7 +169,8 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* 
     for (int k = 0; k < SNW; k++) if (wmax[k] > m || (wmax[k] == m && wimax[k] < mi)) { m = wmax[k]; mi = wimax[k]; }
   };
   auto philox_u24 = [&]() -> uint32_t {
-    uint32_t cc[4] = {a.c0, (uint32_t)a.step, (uint32_t)(a.step >> 32), 0u};
+    uint32_t cc[4];
+    a.philox_counter(cc);
     philox4x32(cc, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
     return cc[0] >> 8;
   };
@@ -189,7 +178,7 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* 
   if (a.top_k == 1) {
     float m; int mi;
     block_argmax(m, mi);
-    if (tid == 0) outp[0] = mi == 0x7fffffff ? 0 : mi;
+    if (tid == 0) a.put(mi == 0x7fffffff ? 0 : mi);
     return;
   }
   if (a.top_k == 0 && (a.min_p > 0.f || (a.top_p > 0.f && a.top_p < 1.f))) {
@@ -305,7 +294,7 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* 
     }
     block_sync();
     // (nothing kept -- min_p with every logit under the threshold, where the reference's multinomial raises on a row of NaN: the arg max)
-    if (tid == 0) outp[0] = pick_f >= 0 ? pick_f : (mi == 0x7fffffff ? 0 : mi);
+    if (tid == 0) a.put(pick_f >= 0 ? pick_f : (mi == 0x7fffffff ? 0 : mi));
     return;
   }
   if (a.top_k == 0) {
@@ -340,11 +329,13 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* 
       pick_s = got;
     }
     block_sync();
-    if (tid == 0) outp[0] = pick_s;
+    if (tid == 0) a.put(pick_s);
     return;
   }
   const int K = a.top_k < V ? a.top_k : V;
   // ---- radix select: the key of the K-th largest logit, 8 bits per pass from the top
+  // (this loop, the walk over the ties and the sort below are repeated in token_logprobs.hip: as templates of sample_select.h each changed the
+  // instruction sequences of both files' kernels)
   if (tid == 0) { sel_prefix = 0u; sel_need = (uint32_t)K; }
   for (int pass = 0; pass < 4; pass++) {
     const int shift = 24 - 8 * pass;
@@ -392,11 +383,7 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* 
       float v = 0.f;
       bool eq = false;
       if (i < V) { v = ld(i); eq = fkey(v) == kth; }
-#ifdef OMK_EMU
-      const unsigned long long m = emu::ballot(eq ? 1 : 0);
-#else
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(eq);
-#endif
+      const unsigned long long m = ballot64(eq);
       const uint32_t rank = got + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
       if (eq && rank < take_eq) { cval[base_eq + rank] = v; cidx[base_eq + rank] = i; }
       got += (uint32_t)__builtin_popcountll(m);
@@ -429,318 +416,20 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, int64_t* 
   const float u = (float)philox_u24() * (1.0f / 16777216.0f) * ktot;   // uniform in [0, ktot)
   // first kept candidate whose cumulative mass exceeds u
   const bool hit = keep && cum > u;
-  unsigned long long mask;
-#ifdef OMK_EMU
-  mask = emu::ballot(hit ? 1 : 0);
-#else
-  mask = __builtin_amdgcn_ballot_w64(hit);
-#endif
+  const unsigned long long mask = ballot64(hit);
   int pick = mask ? __builtin_ctzll(mask) : 0;   // rounding at the top end: fall back to the largest candidate
   const int chosen = shfl(ix, pick);
-  if (lane == 0) outp[0] = chosen;
+  if (lane == 0) a.put(chosen);
 }
 
-// omk_sample's kernel: the whole-batch settings are kernel arguments.  It is kept as it was before sample_row existed, separate arrays
-// and all (69 KB of LDS): sharing sample_row's body cost it 0.2 - 0.9 us per launch on the MI355X (profiles/sample_rows.txt), more than the
-// spread of its own repetitions, and its callers sit inside captured steps.  A change to one of the two bodies belongs in the other too.
+// omk_sample: the whole-batch settings are kernel arguments (one round of scalar loads), and the row index goes into the Philox counter.
+// sample_row's body with the separate LDS arrays.  The kernel sits inside captured steps: its registers and LDS are those it had as a body
+// of its own (56 VGPRs, 66 SGPRs, 69 368 B, no scratch), its per-launch time is not above that body's (profiles/sampler_one_body.txt).
 template <class T>
 __global__ __launch_bounds__(SNT) void sample_kernel(SampleArgs a) {
-  // eight copies of every counter, picked by the lane: the keys of a row share their top byte(s), and 64 lanes adding to ONE LDS address are 64
-  // serial atomics (copy c of digit d lives at 8 d + c: the copies of a digit sit in different banks)
-  __shared__ uint32_t hist[256 * 8];
-  __shared__ uint32_t sel_prefix, sel_need, n_gt, n_eq;
-  __shared__ float cval[SAMPLE_KMAX];
-  __shared__ int cidx[SAMPLE_KMAX];
-  __shared__ float wmax[SNW];
-  __shared__ int wimax[SNW];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int V = a.V;
-  const T* rowp = (const T*)a.logits + (int64_t)row * a.ls;
-  auto ld = [&](int i) -> float { return to_f32(rowp[i]); };
-  // one pass over the row, thread-strided (coalesced), four requests in flight per lane
-  auto strided = [&](auto&& fn) {
-    for (int i0 = tid; i0 < V; i0 += 4 * SNT) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) { const int i = i0 + u * SNT; v[u] = ld(i < V ? i : V - 1); }
-#pragma unroll
-      for (int u = 0; u < 4; u++) { const int i = i0 + u * SNT; if (i < V) fn(v[u], i); }
-    }
-  };
-  // block maximum + its lowest index, in every thread
-  auto block_argmax = [&](float& m, int& mi) {
-    m = -INFINITY; mi = 0x7fffffff;
-    strided([&](float v, int i) { if (v > m || (v == m && i < mi)) { m = v; mi = i; } });
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float om = shfl_xor(m, off); const int oi = shfl_xor(mi, off);
-      if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-    }
-    if (lane == 0) { wmax[wv] = m; wimax[wv] = mi; }
-    block_sync();
-    for (int k = 0; k < SNW; k++) if (wmax[k] > m || (wmax[k] == m && wimax[k] < mi)) { m = wmax[k]; mi = wimax[k]; }
-  };
-  auto philox_u24 = [&]() -> uint32_t {
-    uint32_t cc[4] = {(uint32_t)row, 0u, 0u, 0u};
-    const unsigned long long step = (a.counter ? (unsigned long long)a.counter[0] : 0ull) + a.offset;
-    cc[1] = (uint32_t)step; cc[2] = (uint32_t)(step >> 32);
-    philox4x32(cc, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-    return cc[0] >> 8;
-  };
-
-  if (a.top_k == 1) {
-    float m; int mi;
-    block_argmax(m, mi);
-    if (tid == 0) a.out[row] = mi == 0x7fffffff ? 0 : mi;
-    return;
-  }
-  if (a.top_k == 0 && (a.min_p > 0.f || (a.top_p > 0.f && a.top_p < 1.f))) {
-    // ---- the whole vocabulary behind one of the reference's two filters (see the header)
-    __shared__ unsigned long long hm[256], hm8[256 * 8], sc64[2 * SNT];   // (hm8 / hc8: eight copies per digit, picked by the lane -- see hist)
-    __shared__ uint32_t hc[256], hc8[256 * 8], sc32[2 * SNT];
-    __shared__ unsigned long long s_acc, s_ztot;
-    __shared__ uint32_t s_prefix, s_r;
-    __shared__ float wsumf[SNW];
-    __shared__ int pick_f;
-    const int c = (V + SNT - 1) / SNT, lo = tid * c < V ? tid * c : V, hi = lo + c < V ? lo + c : V;
-    float m; int mi;
-    if (tid == 0) pick_f = -1;
-    block_argmax(m, mi);
-    const float sct = a.inv_temp * LOG2E;
-    // mass of a token in the tempered distribution, 2^-40 units of the largest one (an integer: sums are exact and order-free)
-    auto mass = [&](float l) -> unsigned long long { return (unsigned long long)(exp2_fast((l - m) * sct) * 1099511627776.0f); };
-    const bool use_min_p = a.min_p > 0.f;
-    float thr = -INFINITY;           // min_p: raw logits below it are cut
-    uint32_t vstar = 0u, rcut = 0u;  // top-p: keys below vstar are cut, and the first rcut tokens (index order) whose key equals it
-    if (use_min_p) {
-      float z = 0.f;
-      strided([&](float v, int) { z += exp2_fast((v - m) * LOG2E); });          // softmax of the UNtempered logits (:109)
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) z += shfl_xor(z, off);
-      if (lane == 0) wsumf[wv] = z;
-      block_sync();
-      z = 0.f;
-      for (int k = 0; k < SNW; k++) z += wsumf[k];
-      thr = a.min_p / z;                                                        // max probability = 1 / z
-    } else {
-      unsigned long long zt = 0ull;
-      strided([&](float v, int) { zt += mass(v); });
-      const unsigned long long incl = block_incl_scan<unsigned long long>(zt, sc64, tid);
-      if (tid == SNT - 1) s_ztot = incl;
-      if (tid == 0) { s_prefix = 0u; s_acc = 0ull; }
-      block_sync();
-      const unsigned long long ztot = s_ztot;
-      unsigned long long Q = (unsigned long long)((double)(1.f - a.top_p) * (double)ztot);   // masses <= Q (cumulative, ascending) are cut
-      if (Q >= ztot) Q = ztot ? ztot - 1 : 0ull;
-      for (int pass = 0; pass < 4; pass++) {
-        const int shift = 24 - 8 * pass;
-        for (int i = tid; i < 256 * 8; i += SNT) { hm8[i] = 0ull; hc8[i] = 0u; }
-        block_sync();
-        const uint32_t pre = s_prefix, pmask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-        strided([&](float l, int) {
-          const uint32_t k = fkey(l);
-          if ((k & pmask) == pre) { const uint32_t d = 8u * ((k >> shift) & 255u) + (uint32_t)(lane & 7); lds_add_u64(&hm8[d], mass(l)); lds_fetch_add_u32(&hc8[d], 1u); }
-        });
-        block_sync();
-        if (tid < 256) {
-          unsigned long long tm = 0ull; uint32_t tc = 0u;
-#pragma unroll
-          for (int c8 = 0; c8 < 8; c8++) { tm += hm8[8 * tid + c8]; tc += hc8[8 * tid + c8]; }
-          hm[tid] = tm; hc[tid] = tc;
-        }
-        block_sync();
-        if (wv == 0) {   // ascending: digits whose whole mass still fits under Q are cut; the first one that does not holds the boundary
-          const unsigned long long acc0 = s_acc;
-          uint32_t d; unsigned long long before;
-          wave_find_digit<unsigned long long>([&](int rr) -> unsigned long long { return hm[rr]; }, Q - acc0, lane, d, before);
-          if (lane == 0) {
-            const unsigned long long acc = acc0 + before;
-            s_acc = acc; s_prefix = pre | (d << shift);
-            if (pass == 3) { const unsigned long long one = hc[d] ? hm[d] / hc[d] : 0ull; s_r = one ? (uint32_t)((Q - acc) / one) : 0u; if (s_r >= hc[d] && hc[d]) s_r = hc[d] - 1u; }
-          }
-        }
-        block_sync();
-      }
-      vstar = s_prefix; rcut = s_r;
-    }
-    // ---- kept mass of the thread's tokens.  Ties at the boundary value that are cut (rare) need index-order ranks: contiguous slices then;
-    // otherwise thread t owns t, t + SNT, ... (coalesced reads; the inverse CDF may lay the tokens out in any fixed order)
-    const bool contig = !use_min_p && rcut > 0u;
-    uint32_t tie_before = 0u;
-    if (contig) {
-      uint32_t tc = 0u;
-      for (int i = lo; i < hi; i++) tc += fkey(ld(i)) == vstar ? 1u : 0u;
-      tie_before = block_incl_scan<uint32_t>(tc, sc32, tid) - tc;
-    }
-    auto owned = [&](auto&& fn) {
-      if (contig) { for (int i = lo; i < hi; i++) fn(ld(i), i); }
-      else strided(fn);
-    };
-    unsigned long long km = 0ull;
-    {
-      uint32_t rank = tie_before;
-      owned([&](float l, int) {
-        bool keep;
-        if (use_min_p) keep = l >= thr;
-        else { const uint32_t k = fkey(l); keep = k > vstar || (k == vstar && rank++ >= rcut); }
-        if (keep) km += mass(l);
-      });
-    }
-    const unsigned long long incl = block_incl_scan<unsigned long long>(km, sc64, tid);
-    if (tid == SNT - 1) s_ztot = incl;
-    block_sync();
-    const unsigned long long ktot = s_ztot, start = incl - km;
-    const unsigned long long u24 = philox_u24();
-    const unsigned long long target = (ktot >> 24) * u24 + (((ktot & 0xffffffull) * u24) >> 24);   // floor(u ktot), u in [0, 1): < ktot
-    if (ktot > 0ull && target >= start && target < incl) {   // exactly one thread
-      unsigned long long run = start; uint32_t rank = tie_before; int got = -1; bool done = false;
-      owned([&](float l, int i) {
-        bool keep;
-        if (use_min_p) keep = l >= thr;
-        else { const uint32_t k = fkey(l); keep = k > vstar || (k == vstar && rank++ >= rcut); }
-        const unsigned long long e = keep ? mass(l) : 0ull;
-        if (!done && e > 0ull) got = i;
-        run += e;
-        if (run > target) done = true;
-      });
-      pick_f = got;
-    }
-    block_sync();
-    // (nothing kept -- min_p with every logit under the threshold, where the reference's multinomial raises on a row of NaN: the arg max)
-    if (tid == 0) a.out[row] = pick_f >= 0 ? pick_f : (mi == 0x7fffffff ? 0 : mi);
-    return;
-  }
-  if (a.top_k == 0) {
-    // full-vocabulary multinomial (the reference's top_k == 0 branch with top_p outside (0, 1): softmax(logits / T), one draw).
-    // Block maximum, the mass of every thread's tokens, an inclusive scan of the SNT masses (the scan values tile [0, total) exactly:
-    // end_t = start_{t + 1}), one Philox number scaled to the total, and the thread whose interval holds it walks its tokens.
-    __shared__ float scf[2 * SNT];
-    __shared__ float tot_s;
-    __shared__ int pick_s;
-    // (thread t owns the tokens t, t + SNT, ...: the inverse CDF may lay the tokens out in ANY fixed order, and this one reads coalesced --
-    // contiguous slices per thread were 64 scattered lines per request: 17 -> see profiles/r06_sampler.txt)
-    float m; int mi;
-    if (tid == 0) pick_s = 0;
-    block_argmax(m, mi);
-    const float sc = a.inv_temp * LOG2E;
-    float mine = 0.f;
-    strided([&](float v, int) { mine += exp2_fast((v - m) * sc); });
-    const float end = block_incl_scan<float>(mine, scf, tid);
-    scf[tid] = end;                                                 // (the scan values tile [0, total): a thread starts where its neighbour ends)
-    if (tid == SNT - 1) tot_s = end;
-    block_sync();
-    const float tot = tot_s, start = tid ? scf[tid - 1] : 0.f;
-    float u = (float)philox_u24() * (1.0f / 16777216.0f) * tot;   // uniform in [0, tot)
-    if (u >= tot) u = tot * 0.99999994f;                            // (the product may round up to the total)
-    if (u >= start && u < end) {   // exactly one thread when 0 < tot < inf
-      float run = start; int got = tid < V ? tid : 0; bool done = false;
-      strided([&](float v, int i) {
-        const float e = exp2_fast((v - m) * sc);
-        if (!done && e > 0.f) got = i;                              // rounding inside the walk: the last token with mass
-        run += e;
-        if (run > u) done = true;
-      });
-      pick_s = got;
-    }
-    block_sync();
-    if (tid == 0) a.out[row] = pick_s;
-    return;
-  }
-  const int K = a.top_k < V ? a.top_k : V;
-  // ---- radix select: the key of the K-th largest logit, 8 bits per pass from the top
-  if (tid == 0) { sel_prefix = 0u; sel_need = (uint32_t)K; }
-  for (int pass = 0; pass < 4; pass++) {
-    const int shift = 24 - 8 * pass;
-    for (int i = tid; i < 256 * 8; i += SNT) hist[i] = 0u;
-    block_sync();
-    const uint32_t pre = sel_prefix, pmask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    strided([&](float v, int) {   // (aggregating the lanes of a wave per distinct digit with ballots instead: slower, 55.7 -> 66.3 us)
-      const uint32_t k = fkey(v);
-      if ((k & pmask) == pre) lds_fetch_add_u32(&hist[8u * ((k >> shift) & 255u) + (uint32_t)(lane & 7)], 1u);
-    });
-    block_sync();
-    if (tid < 256) {
-      uint32_t t = 0u;
-#pragma unroll
-      for (int c = 0; c < 8; c++) t += hist[8 * tid + c];
-      hist[8 * tid] = t;
-    }
-    block_sync();
-    if (wv == 0) {   // walk the digits from the top until `need` keys are covered
-      const uint32_t need = sel_need;
-      uint32_t r, before;
-      wave_find_digit<uint32_t>([&](int rr) -> uint32_t { return hist[8u * (255u - (uint32_t)rr)]; }, need - 1u, lane, r, before);
-      if (lane == 0) { sel_prefix = pre | ((255u - r) << shift); sel_need = need - before; }
-    }
-    block_sync();
-  }
-  const uint32_t kth = sel_prefix;           // keys > kth: all taken; keys == kth: sel_need of them (lowest indices first)
-  const uint32_t take_eq = sel_need;
-  if (tid == 0) { n_gt = 0u; n_eq = 0u; }
-  block_sync();
-  const uint32_t base_eq = (uint32_t)K - take_eq;   // slots [0, base_eq) for keys > kth, [base_eq, K) for the ties at the threshold
-  strided([&](float v, int i) {
-    const uint32_t k = fkey(v);
-    if (k > kth) { const uint32_t s = lds_fetch_add_u32(&n_gt, 1u); if (s < base_eq) { cval[s] = v; cidx[s] = i; } }
-    else if (k == kth) { const uint32_t s = lds_fetch_add_u32(&n_eq, 1u); if (s < take_eq) { cval[base_eq + s] = v; cidx[base_eq + s] = i; } }
-  });
-  block_sync();
-  if (wv != 0) return;
-  if (n_eq > take_eq) {
-    // more logits equal the threshold than there are slots left (16-bit logits tie often): which of them are candidates must not
-    // depend on the order the tickets were handed out -- one wave walks the row in index order and keeps the first take_eq
-    uint32_t got = 0u;
-    for (int i0 = 0; i0 < V && got < take_eq; i0 += 64) {
-      const int i = i0 + lane;
-      float v = 0.f;
-      bool eq = false;
-      if (i < V) { v = ld(i); eq = fkey(v) == kth; }
-#ifdef OMK_EMU
-      const unsigned long long m = emu::ballot(eq ? 1 : 0);
-#else
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(eq);
-#endif
-      const uint32_t rank = got + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-      if (eq && rank < take_eq) { cval[base_eq + rank] = v; cidx[base_eq + rank] = i; }
-      got += (uint32_t)__builtin_popcountll(m);
-    }
-  }
-  // ---- one wave: sort the K candidates (value descending, index ascending), softmax, top-p, draw
-  float v = lane < K ? cval[lane] : -INFINITY;
-  int ix = lane < K ? cidx[lane] : 0x7fffffff;
-#pragma unroll
-  for (int size = 2; size <= 64; size <<= 1)
-#pragma unroll
-    for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-      const float ov = shfl_xor(v, stride); const int oi = shfl_xor(ix, stride);
-      const bool first = (lane & stride) == 0;                  // lower lane of the pair
-      const bool desc = (lane & size) == 0;                     // direction of this bitonic block
-      const bool mine_before = v > ov || (v == ov && ix < oi);  // "mine sorts before the other" in descending order
-      const bool keep = (first == desc) ? mine_before : !mine_before;
-      if (!keep) { v = ov; ix = oi; }
-    }
-  const float vmax = wave_read_lane(v, 0);
-  float p = lane < K ? exp2_fast((v - vmax) * a.inv_temp * LOG2E) : 0.f;
-  const float tot = wave_sum(p);
-  p /= tot;
-  float incl = wave_incl_scan_add(p);
-  const float excl = incl - p;
-  const bool keep = lane < K && (a.top_p <= 0.f || a.top_p >= 1.f || excl < a.top_p);
-  const float pk = keep ? p : 0.f;
-  const float ktot = wave_sum(pk);
-  const float cum = wave_incl_scan_add(pk);
-  const float u = (float)philox_u24() * (1.0f / 16777216.0f) * ktot;   // uniform in [0, ktot)
-  // first kept candidate whose cumulative mass exceeds u
-  const bool hit = keep && cum > u;
-  unsigned long long mask;
-#ifdef OMK_EMU
-  mask = emu::ballot(hit ? 1 : 0);
-#else
-  mask = __builtin_amdgcn_ballot_w64(hit);
-#endif
-  int pick = mask ? __builtin_ctzll(mask) : 0;   // rounding at the top end: fall back to the largest candidate
-  const int chosen = shfl(ix, pick);
-  if (lane == 0) a.out[row] = chosen;
+  const int row = blockIdx.x;
+  const BatchCfg c = {a.top_k, a.top_p, a.inv_temp, a.min_p, a.seed, a.counter, a.offset, a.out, row};
+  sample_row<T, false, false>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, nullptr);
 }
 
 struct SampleRowsArgs {
@@ -772,7 +461,7 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
   c.top_p = tp;
   c.inv_temp = t > 0.f ? 1.f / t : 1.f;
   c.min_p = c.top_k == 0 ? mp : 0.f;
-  c.seed = sd; c.step = st; c.c0 = 0u; c.pen = 1.f;
+  c.seed = sd; c.step = st; c.c0 = 0u; c.pen = 1.f; c.out = a.out + row;
   const unsigned char* pmap = nullptr;
   if constexpr (PEN) {
     OMK_DYN_SMEM(dyn);
@@ -789,7 +478,7 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
     block_sync();
     pmap = map;
   }
-  sample_row<T, PEN>((const T*)a.logits + (int64_t)row * a.ls, a.V, a.out + row, c, pmap);
+  sample_row<T, PEN, true>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, pmap);
 }
 
 }  // namespace omk

@@ -12,14 +12,16 @@
 //      same in both forms of the kernel, for any row index and batch size.
 //   3. top_n > 0: the sampler's 4-pass 8-bit radix select over order-preserving integer keys (eight copies of every counter in LDS), the
 //      candidates gathered into LDS (ties at the threshold in index order), sorted by one wave (bitonic, ties by index).
-// The radix select, wave_find_digit and fkey are copies of sample.hip's: moving them into a header both files include is allowed only if
-// the sampler kernels compile to the same registers, and a copy cannot change them.  A change to one belongs in the other.
-#include "omk_common.h"
+// fkey / key_f32, the LDS add, the ballot and wave_find_digit are sample_select.h's, shared with sample.hip.  The radix select loop, the
+// walk over the ties and the bitonic sort below repeat sample.hip's on keys instead of floats: moved into that header each of them changed
+// this kernel's instruction sequence (the select its registers too: profiles/sampler_one_body.txt section 2).  A change to one belongs in
+// the other.
+#include "sample_select.h"
 
 namespace omk {
 namespace {
 
-constexpr int TL_NMAX = 64;   // = SAMPLE_KMAX of sample.hip
+constexpr int TL_NMAX = SELECT_NMAX;   // = SAMPLE_KMAX of sample.hip
 // threads per row: 1024, and 256 under the CPU emulator, as the sampler (the emulator executes the lanes one after the other)
 #ifdef OMK_EMU
 constexpr int TNT = 256;
@@ -39,49 +41,6 @@ struct TokLpArgs {
   float* top_lp; int64_t tls0, tls1;
   int top_n;
 };
-
-// order-preserving key: larger float <-> larger unsigned (NaN sorts above +inf; -0 below +0), and back
-__device__ __forceinline__ uint32_t fkey(float f) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_f32(uint32_t k) { return __builtin_bit_cast(float, (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-#ifdef OMK_EMU
-__device__ __forceinline__ uint32_t lds_fetch_add_u32(uint32_t* p, uint32_t v) { const uint32_t o = *p; *p = o + v; return o; }
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return emu::ballot(p ? 1 : 0); }
-#else
-__device__ __forceinline__ uint32_t lds_fetch_add_u32(uint32_t* p, uint32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-#endif
-
-// inclusive scan over the lanes of a wave
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = shfl(v, lane >= off ? lane - off : lane); if (lane >= off) v += o; }
-  return v;
-}
-// The digit walk of a radix pass by one wave: cnt(r) for r = 0 .. 255 in WALK order, lane l holds r = 4 l .. 4 l + 3; returns in every lane the
-// first r with `total before + cnt(r) > limit` and the total BEFORE it; r = 255 when none does.
-template <class F> __device__ __forceinline__ void wave_find_digit(F cnt, uint32_t limit, int lane, uint32_t& r_out, uint32_t& before_out) {
-  uint32_t c[4], s = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) { c[j] = cnt(4 * lane + j); s += c[j]; }
-  const uint32_t incl = wave_incl_scan_u32(s, lane);
-  uint32_t run = incl - s;
-  int jj = -1; uint32_t bef = 0;
-#pragma unroll
-  for (int j = 0; j < 4; j++) { if (jj < 0 && run + c[j] > limit) { jj = j; bef = run; } run += c[j]; }
-  const unsigned long long m = ballot64(jj >= 0);
-  if (m) {
-    const int l0 = __builtin_ctzll(m);
-    r_out = (uint32_t)(4 * l0 + shfl(jj, l0));
-    before_out = shfl(bef, l0);
-  } else {   // (the walk ends on the last digit: everything in front of it is "before")
-    r_out = 255u;
-    before_out = shfl(incl, 63) - shfl(c[3], 63);
-  }
-}
 
 // REG: V <= TL_RV x TNT, the row lives in registers after one read.
 template <class T, bool REG>
@@ -181,7 +140,7 @@ __global__ __launch_bounds__(TNT) void token_logprobs_kernel(TokLpArgs a) {
     if (wv == 0) {   // walk the digits from the top until `need` keys are covered
       const uint32_t need = sel_need;
       uint32_t r, before;
-      wave_find_digit([&](int rr) -> uint32_t { return hist[8u * (255u - (uint32_t)rr)]; }, need - 1u, lane, r, before);
+      wave_find_digit<uint32_t>([&](int rr) -> uint32_t { return hist[8u * (255u - (uint32_t)rr)]; }, need - 1u, lane, r, before);
       if (lane == 0) { sel_prefix = pre | ((255u - r) << shift); sel_need = need - before; }
     }
     block_sync();

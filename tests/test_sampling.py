@@ -227,6 +227,41 @@ def test_tiny_top_p_is_greedy_and_argument_checks(dev):
         sample_device(logits, top_k=4, temperature=0.0)
 
 
+@pytest.mark.parametrize("top_k,top_p,temp", [(20, 0.9, 0.7), (0, 0.9, 1.0), (0, 0.0, 1.0)])
+def test_a_batch_equals_each_row_alone_at_its_row_index(dev, top_k, top_p, temp):
+    """Row b of a batch draws from the stream (seed, b, step_counter + offset) and from nothing else: its id is the id of a launch in
+    which only row b holds the same logits (the rows in front of it hold other ones), with the counter absent and with a device counter
+    past 2^32; and the row index, the offset and the counter's high word do reach the draw.  V = 1500: more than one sweep of the workgroup, not a
+    multiple of four sweeps."""
+    from omnimamba_amd.sampling import sample_device
+    g = torch.Generator().manual_seed(11)
+    B, V = 3, 1500
+    logits = (torch.randn(B, V, generator=g) * 2.0).to(dev)
+    alone = []
+    for b in range(B):
+        other = torch.randn(B, V, generator=g) * 2.0
+        other[b] = logits[b].cpu()
+        alone.append(other.to(dev))
+    big = torch.tensor(2 ** 33 + 1, dtype=torch.int64, device=dev)
+    low = torch.tensor(1, dtype=torch.int64, device=dev)
+    moved_hi = moved_row = False
+    for counter, offset in ((None, 5), (big, 2)):
+        moved = False
+        for seed in range(8):
+            kw = dict(top_k=top_k, top_p=top_p, temperature=temp, seed=seed, step_counter=counter)
+            ids = sample_device(logits, offset=offset, **kw).cpu()
+            for b in range(B):
+                assert int(sample_device(alone[b], offset=offset, **kw)[b]) == int(ids[b]), (seed, b, offset)
+                moved_row |= b > 0 and int(sample_device(logits[b:b + 1], offset=offset, **kw)[0]) != int(ids[b])     # the same row as row 0
+            moved |= not torch.equal(sample_device(logits, offset=offset + 1, **kw).cpu(), ids)
+            if counter is not None:     # 2^33 + 1 and 1 share their low word
+                kw["step_counter"] = low
+                moved_hi |= not torch.equal(sample_device(logits, offset=offset, **kw).cpu(), ids)
+        assert moved, "the offset does not reach the Philox counter"
+    assert moved_hi, "the high word of the step counter does not reach the Philox counter"
+    assert moved_row, "the row index does not reach the Philox counter"
+
+
 def test_host_sample_calls_advance_the_stream_and_reseeding_reproduces_them(dev):
     """generation.sample() on the device sampler: two calls in a row are independent draws (the reference's torch.multinomial advances
     the global generator), and torch.manual_seed(s) followed by the same calls gives the same ids (advisor finding, round 3: a fixed
