@@ -416,10 +416,12 @@ typedef struct {
                                  * drifts by 2^60 (the arithmetic of the column-slice kernel, bit for bit; tests) */
 #define OMK_SSD_NO_SPLIT     8  /* never cut the sequence into segments (few (batch, head) sequences normally are: csrc/ssd_scan.h) */
 #define OMK_SSD_COLUMN_SLICE 16 /* class A scans on the column-slice kernel (ssd_a6.hip) instead of the specialised-wave kernel */
-/* Measurement aid (ABI 6): the scan kernels the LAST scan call of this thread launched -- omk_ssd_scan_fwd / _bwd or
- * omk_selective_scan_fwd / _bwd, whichever came last -- ';'-separated, template arguments included, e.g.
- * "ssd_dt_prep;ssd_a8<mode=0,dump=1,khilo=0,precise=0>" or "selscan_fwd_shared<lc=8,nu=2,state_only=0>".  bench.py puts it next to its
- * HIP-event time and refuses a PMC traffic file (profiles/ssd_*_traffic.json) recorded for another kernel. */
+/* Measurement aid (ABI 6): the kernels the LAST recording call of this thread launched, ';'-separated, template arguments included, e.g.
+ * "ssd_dt_prep;ssd_a8<mode=0,dump=1,khilo=0,precise=0>", "selscan_fwd_shared<lc=8,nu=2,state_only=0>" or
+ * "conv1d_bwd_cl4<t=bf16,w=4,wf=1>;conv1d_bwd_fold".  Recording calls: omk_ssd_scan_fwd / _bwd, omk_selective_scan_fwd / _bwd and the
+ * backward ops omk_causal_conv1d_bwd, omk_add_norm_bwd and omk_norm_gated_bwd.  Each resets the list on entry -- a refused or empty call
+ * leaves it empty -- so read it right behind the call you mean.  bench.py puts it next to its HIP-event time and refuses a PMC traffic file
+ * (profiles/ssd_*_traffic.json) recorded for another kernel. */
 const char* omk_ssd_last_kernels(void);
 size_t omk_ssd_scan_fwd_workspace_bytes(const OmkSsdFwd* p);
 /* bytes of window_states for these arguments (window_states itself is not looked at); 0 = this forward cannot save them (shape

@@ -6,6 +6,8 @@
 // W-1 previous inputs held in registers: every input byte is fetched once per tile (+ a W-1 token halo that
 // hits L2).  Any other layout (channel-first, odd sizes, fp32 rows not 16-byte aligned) takes the strided
 // scalar kernel, whose fastest thread index follows the unit-stride dimension.
+#include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 #include "omk_common.h"
 #include "ssd_tiles.h"
@@ -862,6 +864,65 @@ static int fill_common(ConvArgs& a, const OmkTensor& x, const OmkTensor& w, cons
   return OMK_OK;
 }
 
+// ---- who decides in the backward: conv_bwd_plan(), a pure function of the descriptor.  The launches read the plan only,
+// omk_causal_conv1d_bwd_workspace_bytes asks the same function (tests/test_stream_dispatch.py holds the table call by call).
+enum ConvFamily { CONV_GENERIC,   // strided scalar kernel: any layout
+                  CONV_CL,        // channel-last 16-bit rows, per-thread tiles (conv1d_bwd_cl_kernel, round 3)
+                  CONV_CL4 };     // channel-last 16-bit rows with scalar token positions (conv1d_bwd_cl4_kernel)
+constexpr int CONV_BWD_TL = 64, CONV_BWD_NS = 4;                // strips of 64 tokens, four strips (waves) per workgroup
+constexpr int CONV_BWD_TILE = CONV_BWD_NS * CONV_BWD_TL;        // = 256 tokens per workgroup and per partial dw / db row
+
+// conv1d_bwd_cl4_kernel adds a row offset of 32 bits to a buffer resource: every offset of L rows of 16-bit elements must fit 31 bits
+static bool conv_rows_near(int L, std::initializer_list<int64_t> row_strides) { return (int64_t)L * 2 * std::max(row_strides) < ((int64_t)1 << 31); }
+// The short prologue (WF) of conv1d_bwd_cl4_kernel: fp32 (C, W) weight rows, contiguous and 16-byte aligned, and an fp32 bias (or none) aligned
+// for the ONE request that fetches a lane's channels -- two channels per lane, one f32x2: 8 bytes.  (The forward's cl8 kernel has four channels
+// per lane, one f32x4, and asks 16 in omk_causal_conv1d_fwd: the two masks differ on purpose.)
+constexpr uintptr_t CONV_BWD_BIAS_ALIGN = 8;
+static bool conv_bwd_wf(const OmkTensor& w, const OmkTensor& bias) {
+  return w.dtype == OMK_F32 && w.stride[1] == 1 && w.stride[0] == w.shape[1] && ((uintptr_t)w.data & 15) == 0 &&
+         (!present(bias) || (bias.dtype == OMK_F32 && ((uintptr_t)bias.data & (CONV_BWD_BIAS_ALIGN - 1)) == 0));
+}
+static dim3 conv_blocks(int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+// f(integral constant W) for the run-time width 2 .. 4
+template <class F> static void conv_width(int W, F&& f) {
+  if (W == 4) f(std::integral_constant<int, 4>{}); else if (W == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 2>{});
+}
+
+struct ConvBwdPlan {
+  ConvFamily family; int dt, W;
+  bool wf;             // CONV_CL4: the short prologue
+  int tiles;           // 256-token tiles per batch element: workgroups along L, and the partial rows each batch element takes
+  size_t part_bytes;   // one partial dw / db row per (batch, tile), C (W + 1) floats each: what the workspace query answers (0: atomics only)
+  bool fold, dinit;    // conv1d_bwd_fold_kernel / conv1d_dinit_kernel follow
+  dim3 grid, fold_grid, dinit_grid;
+};
+// (asked by the workspace query on a descriptor nothing has checked yet: reads shapes, strides and pointers only)
+static ConvBwdPlan conv_bwd_plan(const OmkConv1dBwd* p) {
+  ConvBwdPlan pl = {};
+  const int B = (int)p->x.shape[0], C = (int)p->x.shape[1], L = (int)p->x.shape[2];
+  pl.dt = p->x.dtype; pl.W = (int)p->weight.shape[1];
+  pl.tiles = (L + CONV_BWD_TILE - 1) / CONV_BWD_TILE;
+  pl.dinit = present(p->dinitial_states);
+  pl.dinit_grid = conv_blocks((int64_t)B * C * (pl.W - 1));
+  // (the 16-bit channel-last kernels only; every other layout keeps its atomics and needs no workspace)
+  const bool fast = pl.dt != OMK_F32 && cl_fast_ok(p->x, C) && cl_fast_ok(p->dout, C) && cl_fast_ok(p->dx, C);
+  if (!fast) {
+    pl.family = CONV_GENERIC; pl.grid = conv_blocks((int64_t)B * C);
+    return pl;
+  }
+  pl.part_bytes = (size_t)B * pl.tiles * (size_t)C * (pl.W + 1) * 4;
+  // the scalar-position kernel (conv1d_bwd_cl4_kernel) when every row offset fits 31 bits; the round-3 kernel otherwise
+  const bool cl4 = conv_rows_near(L, {p->x.stride[2], p->dout.stride[2], p->dx.stride[2]}) && p->x.stride[1] == 1 && p->dout.stride[1] == 1 && p->dx.stride[1] == 1;
+  pl.family = cl4 ? CONV_CL4 : CONV_CL;
+  pl.grid = dim3((unsigned)((int64_t)B * pl.tiles * ((C / 2 + 63) / 64)));
+  if (cl4) {
+    pl.wf = conv_bwd_wf(p->weight, p->bias);
+    pl.fold = p->workspace && p->workspace_bytes >= pl.part_bytes;   // (none: fp32 atomics into dw / db)
+    pl.fold_grid = dim3((unsigned)(((int64_t)C * (pl.W + 1) + 63) / 64));
+  }
+  return pl;
+}
+
 }  // namespace omk
 
 using namespace omk;
@@ -940,18 +1001,13 @@ extern "C" int omk_causal_conv1d_fwd(const OmkConv1dFwd* p, omk_stream stream) {
   return finish_launch("causal_conv1d_fwd");
 }
 
-// partial dw / db rows of conv1d_bwd_cl4_kernel: one per (batch, tile of 4 x 64 tokens), C (W + 1) floats each
-static size_t conv_bwd_part_bytes(int B, int C, int L, int W) { return (size_t)B * ((L + 255) / 256) * (size_t)C * (W + 1) * 4; }
-
 extern "C" size_t omk_causal_conv1d_bwd_workspace_bytes(const OmkConv1dBwd* p) {
   if (!p || !present(p->x) || !present(p->weight) || !present(p->dout) || !present(p->dx) || p->x.ndim != 3 || p->weight.ndim != 2) return 0;
-  if (p->x.dtype == OMK_F32) return 0;   // (the 16-bit channel-last kernels only; every other layout keeps its atomics and needs nothing)
-  const int C = (int)p->x.shape[1];
-  if (!(cl_fast_ok(p->x, C) && cl_fast_ok(p->dout, C) && cl_fast_ok(p->dx, C))) return 0;
-  return conv_bwd_part_bytes((int)p->x.shape[0], C, (int)p->x.shape[2], (int)p->weight.shape[1]);
+  return conv_bwd_plan(p).part_bytes;
 }
 
 extern "C" int omk_causal_conv1d_bwd(const OmkConv1dBwd* p, omk_stream stream) {
+  kernels_reset();
   OMK_REQUIRE(p && present(p->x) && present(p->weight) && present(p->dout) && present(p->dx) && present(p->dweight), "causal_conv1d_bwd: x, weight, dout, dx, dweight required");
   ConvArgs a = {};
   int rc = fill_common(a, p->x, p->weight, p->bias, p->initial_states, "causal_conv1d_bwd");
@@ -968,52 +1024,27 @@ extern "C" int omk_causal_conv1d_bwd(const OmkConv1dBwd* p, omk_stream stream) {
     a.disb = p->dinitial_states.stride[0]; a.disc = p->dinitial_states.stride[1]; a.disl = p->dinitial_states.stride[2];
   }
   if ((int64_t)a.B * a.C * a.L == 0) return OMK_OK;
-  const bool fast = p->x.dtype != OMK_F32 && cl_fast_ok(p->x, a.C) && cl_fast_ok(p->dout, a.C) && cl_fast_ok(p->dx, a.C);
-  dim3 block(256);
-  if (fast) {
-    // strips of 64 tokens, 8 tokens in flight: 402 -> 373 us per call on the 1.3B slice against 32 / 4 (halo re-reads of W - 1 rows
-    // per strip and twice the loads in flight); 128-token strips gain nothing more
-    constexpr int TL = 64;
-#define CONV_BWD_V(T_, VEC_, TG_) do { const int CVB = (a.C / VEC_ + 63) / 64, NT4 = (a.L + 4 * TL - 1) / (4 * TL); \
-      dim3 grid((unsigned)((int64_t)a.B * NT4 * CVB)); \
-      if (a.W == 4) OMK_LAUNCH((conv1d_bwd_cl_kernel<T_, VEC_, TL, 4, TG_>), grid, block, 0, stream, a); \
-      else if (a.W == 3) OMK_LAUNCH((conv1d_bwd_cl_kernel<T_, VEC_, TL, 3, TG_>), grid, block, 0, stream, a); \
-      else OMK_LAUNCH((conv1d_bwd_cl_kernel<T_, VEC_, TL, 2, TG_>), grid, block, 0, stream, a); } while (0)
-    // 2 channels per lane: 86 VGPRs / 5 waves per SIMD; the silu' recompute makes this kernel VALU- and latency-heavy
-    // (4 channels: 154 VGPRs, 383 us; 2 channels: ~290 us on the 1.3B shape)
-    // the scalar-position kernel (conv1d_bwd_cl4_kernel) when every row offset fits 31 bits; the round-3 kernel otherwise
-    const int64_t far = (int64_t)a.L * 2 * (a.xsl > a.dosl ? (a.xsl > a.dxsl ? a.xsl : a.dxsl) : (a.dosl > a.dxsl ? a.dosl : a.dxsl));
-    if (far < ((int64_t)1 << 31) && a.xsc == 1 && a.dosc == 1 && a.dxsc == 1) {
+  const ConvBwdPlan pl = conv_bwd_plan(p);
+  a.part = pl.fold ? (float*)p->workspace : nullptr;
+  const char* t = dtype_name(pl.dt);
+  const KernelId id = pl.family == CONV_CL4  ? kernel_id("conv1d_bwd_cl4<t=%s,w=%d,wf=%d>", t, pl.W, (int)pl.wf)
+                      : pl.family == CONV_CL ? kernel_id("conv1d_bwd_cl<t=%s,w=%d>", t, pl.W)
+                                             : kernel_id("conv1d_bwd_generic<t=%s>", t);
+  auto go = [&](auto kern) { omk_launch(id, kern, pl.grid, dim3(256), 0, stream, a); };
+  if (pl.family == CONV_GENERIC) OMK_DISPATCH_DTYPE(pl.dt, T, go(conv1d_bwd_generic_kernel<T>));
+  else OMK_DISPATCH_DTYPE(pl.dt, T, conv_width(pl.W, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    if constexpr (sizeof(T) == 2) {
+      // strips of 64 tokens, 8 tokens in flight: 402 -> 373 us per call on the 1.3B slice against 32 / 4 (halo re-reads of W - 1 rows
+      // per strip and twice the loads in flight); 128-token strips gain nothing more
+      if (pl.family == CONV_CL) return go(conv1d_bwd_cl_kernel<T, 2, CONV_BWD_TL, W, 8>);
       // (measured and not kept, profiles/r06_stream_kernels.txt: 8 / 16 strips per workgroup, 32- and 16-token strips, 8 / 16 tokens requested
       // per group -- 189 ... 194 us all, 16 waves per workgroup 220 ... 262)
-      const bool wf = p->weight.dtype == OMK_F32 && a.wsk == 1 && a.wsc == a.W && ((uintptr_t)p->weight.data & 15) == 0 &&
-                      (!present(p->bias) || (p->bias.dtype == OMK_F32 && ((uintptr_t)p->bias.data & 7) == 0));
-      const int CVB = (a.C / 2 + 63) / 64, NTS = (a.L + 4 * TL - 1) / (4 * TL);
-      dim3 grid((unsigned)((int64_t)a.B * NTS * CVB)), blk(256);
-      const size_t pbytes = conv_bwd_part_bytes(a.B, a.C, a.L, a.W);
-      a.part = (p->workspace && p->workspace_bytes >= pbytes) ? (float*)p->workspace : nullptr;   // (none: fp32 atomics into dw / db)
-#define CONV_BWD_4G(T_, W_) do { if (wf) OMK_LAUNCH((conv1d_bwd_cl4_kernel<T_, TL, W_, TGX, 4, true>), grid, blk, 0, stream, a); \
-        else OMK_LAUNCH((conv1d_bwd_cl4_kernel<T_, TL, W_, TGX, 4, false>), grid, blk, 0, stream, a); } while (0)
-#define CONV_BWD_4(T_) do { if (a.W == 4) CONV_BWD_4G(T_, 4); else if (a.W == 3) CONV_BWD_4G(T_, 3); else CONV_BWD_4G(T_, 2); } while (0)
-      if (p->x.dtype == OMK_BF16) CONV_BWD_4(bf16_t); else CONV_BWD_4(f16_t);
-      if (a.part) {
-        const int64_t ncol = (int64_t)a.C * (a.W + 1);
-        OMK_LAUNCH(conv1d_bwd_fold_kernel, dim3((unsigned)((ncol + 63) / 64)), dim3(1024), 0, stream, a.part, a.B * NTS, a.C, a.W, a.dw, a.db);
-      }
-#undef CONV_BWD_4G
-#undef CONV_BWD_4
-    } else if (p->x.dtype == OMK_BF16) CONV_BWD_V(bf16_t, 2, 8); else CONV_BWD_V(f16_t, 2, 8);
-#undef CONV_BWD_V
-  } else {
-    int64_t n = (int64_t)a.B * a.C;
-    dim3 grid((unsigned)((n + 255) / 256));
-    OMK_DISPATCH_DTYPE(p->x.dtype, T, OMK_LAUNCH((conv1d_bwd_generic_kernel<T>), grid, block, 0, stream, a));
-  }
-  if (a.dinit) {
-    int64_t m = (int64_t)a.B * a.C * (a.W - 1);
-    dim3 g2((unsigned)((m + 255) / 256));
-    OMK_DISPATCH_DTYPE(p->x.dtype, T, OMK_LAUNCH((conv1d_dinit_kernel<T>), g2, block, 0, stream, a));
-  }
+      pl.wf ? go(conv1d_bwd_cl4_kernel<T, CONV_BWD_TL, W, TGX, CONV_BWD_NS, true>) : go(conv1d_bwd_cl4_kernel<T, CONV_BWD_TL, W, TGX, CONV_BWD_NS, false>);
+    }
+  }));
+  if (pl.fold) omk_launch(kernel_id("conv1d_bwd_fold"), conv1d_bwd_fold_kernel, pl.fold_grid, dim3(1024), 0, stream, a.part, a.B * pl.tiles, a.C, a.W, a.dw, a.db);
+  if (pl.dinit) OMK_DISPATCH_DTYPE(pl.dt, T, omk_launch(kernel_id("conv1d_dinit<t=%s>", t), conv1d_dinit_kernel<T>, pl.dinit_grid, dim3(256), 0, stream, a));
   return finish_launch("causal_conv1d_bwd");
 }
 

@@ -7,6 +7,7 @@
 // spills.  Every byte is touched once with 16-byte loads/stores; weight-gradient partials go to a [nparts][cols]
 // workspace (nparts <= 1024) that a second tiny kernel folds.
 // Algorithmic bytes per row of `cols`: add+norm fwd = cols * (sx + sres_in + sx + sres_out); gated fwd = 3 * cols * sx.
+#include <algorithm>
 #include <cstdlib>
 #include "omk_common.h"
 
@@ -764,21 +765,74 @@ static int norm_blocks(int64_t rows, int ngroups, const VecPlan& pl) {
   if (per_group < 1) per_group = 1;
   return (int)(per_group * ngroups);
 }
-static int norm_parts(int64_t rows, int ngroups, const VecPlan& pl) {   // partial dw rows per group
-  return (norm_blocks(rows, ngroups, pl) / ngroups) * (NORM_WAVES / pl.wpr);
+static int norm_parts(int blocks, int ngroups, const VecPlan& pl) {   // partial dw rows of the gated backward on norm_blocks() workgroups
+  return (blocks / ngroups) * (NORM_WAVES / pl.wpr);
 }
 static bool rows_ok8(const OmkTensor& t) { return !present(t) || (aligned16(t) && t.stride[1] == 1 && t.stride[0] % 8 == 0); }
 
+// the forward launches' (vec, nchunk, wpr) -> template constants ladder
 #define OMK_PLAN_SWITCH(plan, ...)                                                                                   \
   if (plan.vec == 8 && plan.wpr == 1) { constexpr int VEC = 8, NCHUNK = 4, WPR = 1; __VA_ARGS__; }                   \
   else if (plan.vec == 8 && plan.nchunk == 1) { constexpr int VEC = 8, NCHUNK = 1, WPR = 4; __VA_ARGS__; }           \
   else if (plan.vec == 8 && plan.nchunk == 2) { constexpr int VEC = 8, NCHUNK = 2, WPR = 4; __VA_ARGS__; }           \
   else if (plan.vec == 8) { constexpr int VEC = 8, NCHUNK = 4, WPR = 4; __VA_ARGS__; }                               \
   else { constexpr int VEC = 1, NCHUNK = 32, WPR = 4; __VA_ARGS__; }
+// the same ladder for the backward launches, as a function: f(VecConst<VEC, NCHUNK, WPR>{}) for what plan_vec() chose -- inside a generic
+// lambda a kernel that exists for VEC 8 only (the lean backward) can stand under `if constexpr`
+template <int V, int NC, int WP> struct VecConst { static constexpr int VEC = V, NCHUNK = NC, WPR = WP; };
+template <class F> static void plan_switch(const VecPlan& pl, F&& f) {
+  if (pl.vec == 8 && pl.wpr == 1) f(VecConst<8, 4, 1>{});
+  else if (pl.vec == 8 && pl.nchunk == 1) f(VecConst<8, 1, 4>{});
+  else if (pl.vec == 8 && pl.nchunk == 2) f(VecConst<8, 2, 4>{});
+  else if (pl.vec == 8) f(VecConst<8, 4, 4>{});
+  else f(VecConst<1, 32, 4>{});
+}
+
+// ---- who decides in the backward: add_bwd_plan() and gated_bwd_plan(), pure functions of the descriptor (and of the OMK_NORM_BLOCKS hook).
+// The launches read the plan only, the workspace queries ask the same functions (tests/test_stream_dispatch.py holds the table call by call).
+enum NormFamily { NORM_GENERAL, NORM_LEAN, NORM_W8 };   // (add_norm: general only; NORM_W8: norm_gated_bwd_w8_kernel)
+struct NormPlan {
+  VecPlan v; int ngroups; NormFamily family;
+  int grid, nparts;        // workgroups; partial dw (and db) rows they leave in the workspace
+  bool red_dw, red_db;     // the reduce_parts launches that follow (a frozen weight: none)
+  size_t ws_bytes;         // what the workspace query answers
+};
+static bool add_bwd_plan(const OmkAddNormBwd* p, NormPlan* pl) {
+  *pl = {};
+  const bool can8 = rows_ok8(p->dy) && rows_ok8(p->xsum) && rows_ok8(p->dx) && rows_ok8(p->dresidual_out) && rows_ok8(p->dresidual_in);
+  if (!plan_vec(p->dy.shape[1], can8, &pl->v)) return false;
+  pl->ngroups = 1;
+  pl->grid = pl->nparts = norm_blocks(p->dy.shape[0], 1, pl->v);   // (one partial row per workgroup)
+  pl->red_dw = present(p->dweight); pl->red_db = p->has_bias && present(p->dbias);
+  pl->ws_bytes = (size_t)pl->nparts * p->dy.shape[1] * 4 * 2;      // (dw and db)
+  return true;
+}
+static bool gated_bwd_plan(const OmkNormGatedBwd* p, NormPlan* pl) {
+  *pl = {};
+  const int64_t rows = p->x.shape[0], cols = p->x.shape[1], gs = p->group_size > 0 ? p->group_size : cols;
+  if (gs <= 0 || cols % gs) return false;
+  const bool can8 = rows_ok8(p->x) && rows_ok8(p->dy) && rows_ok8(p->z) && rows_ok8(p->dx) && rows_ok8(p->dz) && gs % 8 == 0;
+  if (!plan_vec(gs, can8, &pl->v)) return false;
+  pl->ngroups = (int)(cols / gs);
+  const int blocks = norm_blocks(rows, pl->ngroups, pl->v), general = norm_parts(blocks, pl->ngroups, pl->v);
+  // the reference's mode (gate first) on full bf16 segments (every lane's columns exist): the software-pipelined kernel
+  const bool lean = present(p->z) && present(p->dz) && !p->norm_before_gate && pl->v.vec == 8 && gs == (int64_t)pl->v.wpr * pl->v.nchunk * 64 * 8 &&
+                    p->x.dtype == OMK_BF16;
+  if (lean && pl->ngroups == 1 && cols == NORM_W8_COLS) {
+    pl->family = NORM_W8;
+    pl->grid = pl->nparts = rows < NORM_W8_BLOCKS ? (int)rows : NORM_W8_BLOCKS;
+  } else {
+    pl->family = lean ? NORM_LEAN : NORM_GENERAL;
+    pl->grid = blocks; pl->nparts = general;
+  }
+  pl->red_dw = present(p->dweight);
+  // (whichever kernel takes the call; norm_gated_bwd_w8_kernel never needs more than the general form for >= 512 rows)
+  pl->ws_bytes = std::max((size_t)general, (size_t)NORM_W8_BLOCKS) * p->x.shape[1] * 4;
+  return true;
+}
 
 static void launch_reduce(const float* part, int nparts, int64_t cols, float* out, omk_stream stream) {
-  dim3 rg((unsigned)((cols + RP_COLS - 1) / RP_COLS)), rb(RP_COLS * RP_GROUPS);
-  OMK_LAUNCH(reduce_parts_kernel, rg, rb, 0, stream, part, nparts, (int)cols, out);
+  omk_launch(kernel_id("reduce_parts"), reduce_parts_kernel, dim3((unsigned)((cols + RP_COLS - 1) / RP_COLS)), dim3(RP_COLS * RP_GROUPS), 0, stream, part, nparts, (int)cols, out);
 }
 
 }  // namespace omk
@@ -833,19 +887,13 @@ extern "C" int omk_add_norm_fwd(const OmkAddNormFwd* p, omk_stream stream) {
   return finish_launch("add_norm_fwd");
 }
 
-static bool add_bwd_plan(const OmkAddNormBwd* p, VecPlan* plan) {
-  bool can8 = rows_ok8(p->dy) && rows_ok8(p->xsum) && rows_ok8(p->dx) && rows_ok8(p->dresidual_out) && rows_ok8(p->dresidual_in);
-  return plan_vec(p->dy.shape[1], can8, plan);
-}
-
 extern "C" size_t omk_add_norm_bwd_workspace_bytes(const OmkAddNormBwd* p) {
-  if (!p) return 0;
-  VecPlan plan;
-  if (!add_bwd_plan(p, &plan)) return 0;
-  return (size_t)norm_blocks(p->dy.shape[0], 1, plan) * p->dy.shape[1] * 4 * 2;   // (one partial row per workgroup, dw and db)
+  NormPlan pl;
+  return p && add_bwd_plan(p, &pl) ? pl.ws_bytes : 0;
 }
 
 extern "C" int omk_add_norm_bwd(const OmkAddNormBwd* p, omk_stream stream) {
+  kernels_reset();
   OMK_REQUIRE(p && present(p->dy) && present(p->xsum) && present(p->weight) && present(p->rstd) && present(p->dx),
               "add_norm_bwd: dy, xsum, weight, rstd, dx required");
   const int64_t rows = p->dy.shape[0], cols = p->dy.shape[1];
@@ -854,34 +902,33 @@ extern "C" int omk_add_norm_bwd(const OmkAddNormBwd* p, omk_stream stream) {
   OMK_REQUIRE(p->xsum.dtype == p->dy.dtype || p->xsum.dtype == OMK_F32, "add_norm_bwd: xsum dtype");
   OMK_REQUIRE(!present(p->dweight) || p->dweight.dtype == OMK_F32, "add_norm_bwd: dweight must be f32");
   if (rows == 0) return OMK_OK;
-  VecPlan plan;
-  if (!add_bwd_plan(p, &plan)) return fail(OMK_EUNSUPPORTED, "add_norm_bwd: cols too large");
-  OMK_REQUIRE(p->workspace && p->workspace_bytes >= omk_add_norm_bwd_workspace_bytes(p), "add_norm_bwd: workspace too small");
-  const int nparts = norm_blocks(rows, 1, plan);
+  NormPlan pl;
+  if (!add_bwd_plan(p, &pl)) return fail(OMK_EUNSUPPORTED, "add_norm_bwd: cols too large");
+  OMK_REQUIRE(p->workspace && p->workspace_bytes >= pl.ws_bytes, "add_norm_bwd: workspace too small");
   NormBwdArgs a = {};
   a.dy = p->dy.data; a.dro = p->dresidual_out.data; a.xsum = p->xsum.data; a.w = p->weight.data;
   a.rstd = (const float*)p->rstd.data; a.mean = p->is_rms_norm ? nullptr : (const float*)p->mean.data;
   a.dx = p->dx.data; a.dri = p->dresidual_in.data;
-  // a frozen weight (dweight absent): no partial rows, no reduction launch
-  a.dw_part = present(p->dweight) ? (float*)p->workspace : nullptr;
-  a.db_part = (p->has_bias && present(p->dbias)) ? (float*)p->workspace + (size_t)nparts * cols : nullptr;
+  a.dw_part = pl.red_dw ? (float*)p->workspace : nullptr;
+  a.db_part = pl.red_db ? (float*)p->workspace + (size_t)pl.nparts * cols : nullptr;
   a.dys = p->dy.stride[0]; a.dros = present(p->dresidual_out) ? p->dresidual_out.stride[0] : 0; a.xss = p->xsum.stride[0];
   a.dxs = p->dx.stride[0]; a.dris = present(p->dresidual_in) ? p->dresidual_in.stride[0] : 0;
   a.rows = rows; a.cols = (int)cols; a.ngroups = 1; a.wdt = p->weight.dtype; a.rms = p->is_rms_norm;
   const int xdt = p->dy.dtype, sdt = p->xsum.dtype;
   const int ridt = present(p->dresidual_in) ? p->dresidual_in.dtype : xdt;
   OMK_REQUIRE(ridt == xdt || ridt == OMK_F32, "add_norm_bwd: dresidual_in dtype");
-  dim3 grid(norm_blocks(rows, 1, plan)), block(NORM_THREADS);
-#define LAUNCH_B(TX, TS, TRI) OMK_PLAN_SWITCH(plan, OMK_LAUNCH((add_norm_bwd_kernel<TX, TS, TRI, VEC, NCHUNK, WPR>), grid, block, 0, stream, a))
-  OMK_DISPATCH_DTYPE(xdt, TX, {
-    if (sdt == xdt && ridt == xdt) { LAUNCH_B(TX, TX, TX); }
-    else if (sdt == xdt) { LAUNCH_B(TX, TX, float); }
-    else if (ridt == xdt) { LAUNCH_B(TX, float, TX); }
-    else { LAUNCH_B(TX, float, float); }
-  });
-#undef LAUNCH_B
-  if (a.dw_part) launch_reduce(a.dw_part, nparts, cols, (float*)p->dweight.data, stream);
-  if (a.db_part) launch_reduce(a.db_part, nparts, cols, (float*)p->dbias.data, stream);
+  const KernelId id = kernel_id("add_norm_bwd<tx=%s,ts=%s,tri=%s,vec=%d,nchunk=%d,wpr=%d,grid=%d>", dtype_name(xdt), dtype_name(sdt), dtype_name(ridt),
+                                pl.v.vec, pl.v.nchunk, pl.v.wpr, pl.grid);
+  auto go = [&](auto kern) { omk_launch(id, kern, dim3(pl.grid), dim3(NORM_THREADS), 0, stream, a); };
+  OMK_DISPATCH_DTYPE(xdt, TX, plan_switch(pl.v, [&](auto c) {
+    using C = decltype(c);
+    if (sdt == xdt && ridt == xdt) go(add_norm_bwd_kernel<TX, TX, TX, C::VEC, C::NCHUNK, C::WPR>);
+    else if (sdt == xdt) go(add_norm_bwd_kernel<TX, TX, float, C::VEC, C::NCHUNK, C::WPR>);
+    else if (ridt == xdt) go(add_norm_bwd_kernel<TX, float, TX, C::VEC, C::NCHUNK, C::WPR>);
+    else go(add_norm_bwd_kernel<TX, float, float, C::VEC, C::NCHUNK, C::WPR>);
+  }));
+  if (a.dw_part) launch_reduce(a.dw_part, pl.nparts, cols, (float*)p->dweight.data, stream);
+  if (a.db_part) launch_reduce(a.db_part, pl.nparts, cols, (float*)p->dbias.data, stream);
   return finish_launch("add_norm_bwd");
 }
 
@@ -929,61 +976,41 @@ extern "C" int omk_norm_gated_fwd(const OmkNormGatedFwd* p, omk_stream stream) {
   return finish_launch("norm_gated_fwd");
 }
 
-static bool gated_bwd_plan(const OmkNormGatedBwd* p, VecPlan* plan, int* ng) {
-  const int64_t cols = p->x.shape[1];
-  const int64_t gs = p->group_size > 0 ? p->group_size : cols;
-  if (gs <= 0 || cols % gs) return false;
-  *ng = (int)(cols / gs);
-  bool can8 = rows_ok8(p->x) && rows_ok8(p->dy) && rows_ok8(p->z) && rows_ok8(p->dx) && rows_ok8(p->dz) && gs % 8 == 0;
-  return plan_vec(gs, can8, plan);
-}
-
 extern "C" size_t omk_norm_gated_bwd_workspace_bytes(const OmkNormGatedBwd* p) {
-  if (!p) return 0;
-  VecPlan plan; int ng;
-  if (!gated_bwd_plan(p, &plan, &ng)) return 0;
-  const size_t general = (size_t)norm_parts(p->x.shape[0], ng, plan) * p->x.shape[1] * 4;
-  const size_t w8 = (size_t)NORM_W8_BLOCKS * p->x.shape[1] * 4;     // (norm_gated_bwd_w8_kernel: never more than the general form needs for >= 512 rows)
-  return general > w8 ? general : w8;
+  NormPlan pl;
+  return p && gated_bwd_plan(p, &pl) ? pl.ws_bytes : 0;
 }
 
 extern "C" int omk_norm_gated_bwd(const OmkNormGatedBwd* p, omk_stream stream) {
+  kernels_reset();
   OMK_REQUIRE(p && present(p->dy) && present(p->x) && present(p->weight) && present(p->dx), "norm_gated_bwd: dy, x, weight, dx required");
   const int64_t rows = p->x.shape[0], cols = p->x.shape[1];
   OMK_REQUIRE(!present(p->dweight) || p->dweight.dtype == OMK_F32, "norm_gated_bwd: dweight must be f32");
   OMK_REQUIRE(p->dy.dtype == p->x.dtype && p->dx.dtype == p->x.dtype, "norm_gated_bwd: dtype mismatch");
   if (present(p->z)) OMK_REQUIRE(present(p->dz) && p->z.dtype == p->x.dtype && p->dz.dtype == p->x.dtype, "norm_gated_bwd: z/dz");
   if (rows == 0) return OMK_OK;
-  VecPlan plan; int ng;
-  if (!gated_bwd_plan(p, &plan, &ng)) return fail(OMK_EUNSUPPORTED, "norm_gated_bwd: unsupported group size");
-  OMK_REQUIRE(p->workspace && p->workspace_bytes >= omk_norm_gated_bwd_workspace_bytes(p), "norm_gated_bwd: workspace too small");
-  const int nparts = norm_parts(rows, ng, plan);
+  NormPlan pl;
+  if (!gated_bwd_plan(p, &pl)) return fail(OMK_EUNSUPPORTED, "norm_gated_bwd: unsupported group size");
+  OMK_REQUIRE(p->workspace && p->workspace_bytes >= pl.ws_bytes, "norm_gated_bwd: workspace too small");
   NormBwdArgs a = {};
   a.dy = p->dy.data; a.x = p->x.data; a.z = p->z.data; a.w = p->weight.data; a.dx = p->dx.data; a.dz = p->dz.data;
-  a.dw_part = present(p->dweight) ? (float*)p->workspace : nullptr;   // frozen weight: no partial rows, no reduction launch
+  a.dw_part = pl.red_dw ? (float*)p->workspace : nullptr;   // frozen weight: no partial rows, no reduction launch
   a.dys = p->dy.stride[0]; a.xs = p->x.stride[0]; a.zs = present(p->z) ? p->z.stride[0] : 0; a.dxs = p->dx.stride[0];
   a.dzs = present(p->dz) ? p->dz.stride[0] : 0;
-  a.rows = rows; a.cols = (int)cols; a.ngroups = ng; a.wdt = p->weight.dtype; a.rms = 1; a.eps = p->eps; a.norm_before_gate = p->norm_before_gate;
-  dim3 grid(norm_blocks(rows, ng, plan)), block(NORM_THREADS);
-  const int64_t gsz = cols / ng;
-  const bool lean = present(p->z) && present(p->dz) && !p->norm_before_gate && plan.vec == 8 && gsz == (int64_t)plan.wpr * plan.nchunk * 64 * 8 &&
-                    p->x.dtype == OMK_BF16;
-  const bool w8 = lean && ng == 1 && cols == NORM_W8_COLS;
-  if (w8) {
-    int nb = rows < NORM_W8_BLOCKS ? (int)rows : NORM_W8_BLOCKS;
-    OMK_LAUNCH(norm_gated_bwd_w8_kernel, dim3((unsigned)nb), dim3(512), 0, stream, a);
-    if (a.dw_part) launch_reduce(a.dw_part, nb, cols, (float*)p->dweight.data, stream);
-    return finish_launch("norm_gated_bwd");
-  }
-  if (lean) {
-    // (measured and not kept, profiles/r06_stream_kernels.txt: the next row's requests in a second staging set -- 150 registers, three waves per
-    // SIMD: 300 us against 290; the five streams with trivial arithmetic take 244 us on the same box, one-shot or persistent alike)
-    if (plan.wpr == 1) OMK_LAUNCH((norm_gated_bwd_lean_kernel<bf16_t, 8, 4, 1>), grid, block, 0, stream, a);
-    else if (plan.nchunk == 1) OMK_LAUNCH((norm_gated_bwd_lean_kernel<bf16_t, 8, 1, 4>), grid, block, 0, stream, a);
-    else if (plan.nchunk == 2) OMK_LAUNCH((norm_gated_bwd_lean_kernel<bf16_t, 8, 2, 4>), grid, block, 0, stream, a);
-    else OMK_LAUNCH((norm_gated_bwd_lean_kernel<bf16_t, 8, 4, 4>), grid, block, 0, stream, a);
-  } else
-  OMK_DISPATCH_DTYPE(p->x.dtype, TX, OMK_PLAN_SWITCH(plan, OMK_LAUNCH((norm_gated_bwd_kernel<TX, VEC, NCHUNK, WPR>), grid, block, 0, stream, a)));
-  if (a.dw_part) launch_reduce(a.dw_part, nparts, cols, (float*)p->dweight.data, stream);
+  a.rows = rows; a.cols = (int)cols; a.ngroups = pl.ngroups; a.wdt = p->weight.dtype; a.rms = 1; a.eps = p->eps; a.norm_before_gate = p->norm_before_gate;
+  const char* t = dtype_name(p->x.dtype);
+  const KernelId id = pl.family == NORM_W8     ? kernel_id("norm_gated_bwd_w8")
+                      : pl.family == NORM_LEAN ? kernel_id("norm_gated_bwd_lean<t=%s,nchunk=%d,wpr=%d,grid=%d>", t, pl.v.nchunk, pl.v.wpr, pl.grid)
+                                               : kernel_id("norm_gated_bwd<t=%s,vec=%d,nchunk=%d,wpr=%d,grid=%d>", t, pl.v.vec, pl.v.nchunk, pl.v.wpr, pl.grid);
+  auto go = [&](auto kern) { omk_launch(id, kern, dim3(pl.grid), dim3(pl.family == NORM_W8 ? 512 : NORM_THREADS), 0, stream, a); };
+  if (pl.family == NORM_W8) go(norm_gated_bwd_w8_kernel);
+  // (lean: measured and not kept, profiles/r06_stream_kernels.txt: the next row's requests in a second staging set -- 150 registers, three waves per
+  // SIMD: 300 us against 290; the five streams with trivial arithmetic take 244 us on the same box, one-shot or persistent alike)
+  else if (pl.family == NORM_LEAN) plan_switch(pl.v, [&](auto c) {
+    using C = decltype(c);
+    if constexpr (C::VEC == 8) go(norm_gated_bwd_lean_kernel<bf16_t, 8, C::NCHUNK, C::WPR>);
+  });
+  else OMK_DISPATCH_DTYPE(p->x.dtype, TX, plan_switch(pl.v, [&](auto c) { using C = decltype(c); go(norm_gated_bwd_kernel<TX, C::VEC, C::NCHUNK, C::WPR>); }));
+  if (a.dw_part) launch_reduce(a.dw_part, pl.nparts, cols, (float*)p->dweight.data, stream);
   return finish_launch("norm_gated_bwd");
 }

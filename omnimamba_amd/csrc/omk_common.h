@@ -12,8 +12,10 @@ namespace omk {
 // ---- thread-local error text --------------------------------------------------------------------------
 char* err_buf();
 int fail(int code, const char* fmt, ...);
-// which scan kernels the last scan call of this thread launched -- omk_ssd_scan_fwd / _bwd or omk_selective_scan_fwd / _bwd, each resets
-// the list on entry (omk_ssd_last_kernels: measurement tools tie a profile to the kernel that was timed, the dispatch tests read it)
+// which kernels the last recording call of this thread launched.  Recording calls: omk_ssd_scan_fwd / _bwd, omk_selective_scan_fwd / _bwd and the
+// backward ops of conv1d.hip and norms.hip (omk_causal_conv1d_bwd, omk_add_norm_bwd, omk_norm_gated_bwd); each resets the list on entry and notes
+// every launch, so the string names the LAST such call (omk_ssd_last_kernels: measurement tools tie a profile to the kernel that was timed, the
+// dispatch tests read it)
 void kernels_reset();
 void kernels_note(const char* fmt, ...);
 #define OMK_REQUIRE(cond, ...) \
@@ -36,6 +38,7 @@ inline bool is_dense(const OmkTensor& t) {
   return true;
 }
 inline size_t dtype_size(int dt) { return (dt == OMK_F32 || dt == OMK_I32) ? 4 : (dt == OMK_U8 || dt == OMK_F8E4M3) ? 1 : 2; }
+inline const char* dtype_name(int dt) { return dt == OMK_F32 ? "f32" : dt == OMK_BF16 ? "bf16" : dt == OMK_F16 ? "f16" : "?"; }   // (in kernel ids)
 inline bool aligned16(const OmkTensor& t) { return ((uintptr_t)t.data & 15) == 0; }
 // ABI 8 slot indices (state_batch_indices / conv_state_indices): absent, or contiguous int32 (B).  The values are never read on the host.
 inline bool indices_ok(const OmkTensor& t, int64_t B) {
@@ -49,7 +52,7 @@ inline bool strides_multiple_of(const OmkTensor& t, int64_t elems) {
 }
 int finish_launch(const char* what);
 
-// ---- the one way a scan kernel is launched: its id goes to omk_ssd_last_kernels(), the dynamic LDS limit is raised, then the launch
+// ---- the one way a recorded kernel is launched: its id goes to omk_ssd_last_kernels(), the dynamic LDS limit is raised, then the launch
 struct KernelId { char s[96]; };
 inline KernelId kernel_id(const char* fmt, ...) {
   KernelId k;

@@ -52,38 +52,63 @@ def test_conv1d_fwd_bwd(dev, dtype, W, layout, C, L):
             assert rel(ir.grad, idd.grad) < gtol
 
 
+def recorded_backwards(monkeypatch):
+    """What omk_ssd_last_kernels() says behind every omk_causal_conv1d_bwd call the ops make from here on: read right behind the call and on
+    the thread that made it -- the record is per thread, and the autograd engine runs a GPU backward on a thread of its own."""
+    from omnimamba_amd import causal_conv1d as CC
+    calls, run = [], CC.K.run
+
+    def run_and_note(lib, fn_name, params, ref):
+        run(lib, fn_name, params, ref)
+        if fn_name == "omk_causal_conv1d_bwd":
+            calls.append(lib.omk_ssd_last_kernels().decode())
+
+    monkeypatch.setattr(CC.K, "run", run_and_note)
+    return calls
+
+
 @pytest.mark.parametrize("W", [2, 3, 4])
-def test_conv1d_long_strips_both_prologues_agree(dev, W):
-    """The scalar-position kernels of long channel-last rows take a short prologue for contiguous fp32 (C, W) weights (16-byte requests, strips of
-    16 tokens in the forward) and the general run-time-dtype prologue for everything else: the same op with the same weights as a strided view and
-    as bf16-representable values in a bf16 tensor must give the same bits (forward, final states) and the same gradients."""
+@pytest.mark.parametrize("C,off,kernels", [(12, 4, "generic"), (16, 8, "scalar positions")])
+def test_conv1d_weight_forms_agree(dev, monkeypatch, W, C, off, kernels):
+    """The same op with the same weights as contiguous fp32, as a strided fp32 view and as bf16-representable values in a bf16 tensor must give
+    the same bits (forward, final states) and the same gradients, on long channel-last bf16 rows.
+    generic: C 12 is no multiple of 8 and the view starts 8 bytes into a row, so conv1d_fwd_generic_kernel and conv1d_bwd_generic_kernel run,
+    which read the weights one element at a time whatever their form.
+    scalar positions: C 16, a view 8 elements into the row, L >= 256: conv1d_fwd_cl8_kernel and conv1d_bwd_cl4_kernel, which take a short prologue
+    for contiguous fp32 (C, W) weights (wf=1: 16-byte requests, strips of 16 tokens in the forward) and the general run-time-dtype prologue for the
+    other two forms (wf=0, strips of 64).  Each variant asserts the kernels the library recorded for its backward call (the forward records none)."""
     from omnimamba_amd.causal_conv1d import causal_conv1d_fn
     torch.manual_seed(1)
-    B, C, L = 2, 12, 600
-    base = torch.randn(B, L, C + 4).bfloat16().to(dev)
+    B, L = 2, 600
+    base = torch.randn(B, L, C + off).bfloat16().to(dev)
     w = torch.randn(C, W).bfloat16().float().to(dev)                 # bf16-representable values
     b = torch.randn(C).bfloat16().float().to(dev)
     init = torch.randn(B, C, W - 1).bfloat16().to(dev)
     wide = torch.zeros(C, 2 * W, device=dev); wide[:, ::2] = w
     variants = {"fp32 contiguous": (w, b), "fp32 strided view": (wide[:, ::2], b), "bf16": (w.bfloat16(), b.bfloat16())}
-    res = {}
+    res, calls = {}, recorded_backwards(monkeypatch)
     for name, (wv, bv) in variants.items():
-        x = base[:, :, 4:].transpose(1, 2).detach().requires_grad_()
+        calls.clear()
+        x = base[:, :, off:].transpose(1, 2).detach().requires_grad_()
         wr, br = wv.detach().requires_grad_(), bv.detach().requires_grad_()
         ir = init.detach().requires_grad_()
         out, fin = causal_conv1d_fn(x, wr, br, initial_states=ir, return_final_states=True, activation="silu")
         g = torch.ones_like(out) * 0.5
         out.backward(g)
+        wf = int(name == "fp32 contiguous")
+        want = {"generic": "conv1d_bwd_generic<t=bf16>;conv1d_dinit<t=bf16>",
+                "scalar positions": f"conv1d_bwd_cl4<t=bf16,w={W},wf={wf}>;conv1d_bwd_fold;conv1d_dinit<t=bf16>"}[kernels]
+        assert calls == [want], name
         res[name] = (out.detach().float().cpu(), fin.float().cpu(), x.grad.float().cpu(), wr.grad.float().cpu(), br.grad.float().cpu(), ir.grad.float().cpu())
     ref = res["fp32 contiguous"]
     for name in ("fp32 strided view", "bf16"):
         got = res[name]
         assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]), name                    # forward: bit for bit
         assert torch.equal(got[2], ref[2]) and torch.equal(got[5], ref[5]), name                    # dx, dinit: the same arithmetic
-        for i in (3, 4):                                                                             # dw, db: atomics, order free (bf16: rounded)
+        for i in (3, 4):                                                                             # dw, db: order free without a fold (bf16: rounded)
             tol = 1e-2 if name == "bf16" else 1e-5
             assert rel(got[i], ref[i].double()) < tol, (name, i)
-    o0 = O.causal_conv1d_ref(base[:, :, 4:].transpose(1, 2).cpu(), w.cpu(), b.cpu(), initial_states=init.cpu(), activation="silu")
+    o0 = O.causal_conv1d_ref(base[:, :, off:].transpose(1, 2).cpu(), w.cpu(), b.cpu(), initial_states=init.cpu(), activation="silu")
     assert rel(ref[0], o0) < 6e-3
 
 
@@ -156,15 +181,19 @@ def test_conv1d_channel_blocks_and_bwd_folds(dev, monkeypatch, C, W, dtype):
         e, bnd = rel(got, want), op_bound(want, got.dtype)
         assert e <= bnd, (what, e, bnd)
 
+    t, calls = {torch.bfloat16: "bf16", torch.float16: "f16"}[dtype], recorded_backwards(monkeypatch)
     for fold in ("parts", "atomics"):
         if fold == "atomics":
             without_workspace(monkeypatch)
         for use_init in (False, True):
+            calls.clear()
             xr = xdev.detach().requires_grad_()
             wr, br = w.clone().to(dev).requires_grad_(), b.clone().to(dev).requires_grad_()
             ir = init.clone().to(dev).requires_grad_() if use_init else None
             out, fin = causal_conv1d_fn(xr, wr, br, initial_states=ir, return_final_states=True, activation="silu")
             out.backward(gout.to(dev))
+            assert calls == [f"conv1d_bwd_cl4<t={t},w={W},wf=1>" + (";conv1d_bwd_fold" if fold == "parts" else "")
+                             + (f";conv1d_dinit<t={t}>" if use_init else "")], (fold, use_init)
             xd, wd, bd = x.double().requires_grad_(), w.double().requires_grad_(), b.double().requires_grad_()
             idd = init.double().requires_grad_() if use_init else None
             od, fd = O.causal_conv1d_ref(xd, wd, bd, initial_states=idd, return_final_states=True, activation="silu", compute_dtype=torch.float64)
