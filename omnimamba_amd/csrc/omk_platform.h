@@ -386,6 +386,24 @@ __device__ __forceinline__ float fma_f32(float a, float b, float c) { return __b
 __device__ __forceinline__ f32x2 fma_f32x2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 constexpr float LOG2E = 1.4426950408889634f;
 __device__ __forceinline__ float sigmoid_fast(float x) { return rcp_fast(1.f + exp2_fast(-x * LOG2E)); }
+// softplus(v) = log1p(exp(v)) for v <= 20 from ONE hardware exp2, and sigmoid(v) = softplus'(v) in `sig`: e = exp(v), u = 1 + e;
+// log1p(e) = log(u) e / (u - 1) repairs the rounding of 1 + e (classic compensation; the bare log(1 + e) has an ABSOLUTE error of
+// 6e-8, i.e. 6e-5 of a softplus of 1e-3 and all of one below 6e-8), sigmoid(v) = e / u.  u == 1: e is below half an ulp of 1 and is
+// the answer.  Callers take v itself above 20.
+__device__ __forceinline__ float softplus_fast(float v, float& sig) {
+  const float e = exp2_fast(v * LOG2E), u = 1.f + e;
+  sig = e * rcp_fast(u);
+  return u == 1.f ? e : log2_fast(u) * 0.6931471805599453f * e * rcp_fast(u - 1.f);
+}
+// The value alone, without the reciprocal (the scans apply it once per token on their critical path): with c = e - (u - 1), the exact
+// residue of the rounding of 1 + e, log1p(e) = log(u) + log1p(c / u) = log(u) + c to within c e / u <= 3e-8 of the result while e < 1; from
+// e = 1 on c / u is below 6e-8 of a result above 0.69 and is left out.  u == 1 gives 0 + e.
+__device__ __forceinline__ float softplus_fast(float v) {
+  const float e = exp2_fast(v * LOG2E), u = 1.f + e;
+  return fmaf(0.6931471805599453f, log2_fast(u), e < 1.f ? e - (u - 1.f) : 0.f);
+}
+// sigmoid(raw) = 1 - exp(-softplus(raw)) from a softplus still in registers; below 1e-3 the difference from 1 would cancel
+__device__ __forceinline__ float sigmoid_of_softplus(float sp) { return sp < 1e-3f ? sp * (1.f - 0.5f * sp) : 1.f - exp2_fast(-sp * LOG2E); }
 // Wave totals of N per-lane values (N a power of two <= 64) with N - 1 + log2(64 / N) shuffles instead of the 6 N
 // DPP steps (plus their wait states) of N wave_sum calls: each halving step hands half of the values to the partner
 // lane.  On return v[0] of lane L is the total of the value with index L >> (6 - log2 N).

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
 #pragma unroll
     for (int i = 0; i < SSC_LC; i++) {
       float v = dl[i] + db;
-      if (a.softplus) v = v > 20.f ? v : 0.6931471805599453f * log2_fast(1.f + exp2_fast(v * LOG2E));
+      if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
       dl[i] = (t0 + i < a.L) ? v : 0.f;     // tokens past the end: a = 1, b = 0 (the identity pair)
       u[i] *= dl[i];                          // delta_t u_t
       y[i] = 0.f;
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(512) void selscan_fwd_shared_kernel(SsArgs a) {
 #pragma unroll
     for (int i = 0; i < SSC_LC; i++) {
       float v = dl[i] + db;
-      if (a.softplus) v = v > 20.f ? v : 0.6931471805599453f * log2_fast(1.f + exp2_fast(v * LOG2E));
+      if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
       dl[i] = (t0 + i < a.L) ? v : 0.f;     // tokens past the end: a = 1, b = 0 (the identity pair)
       u[i] *= dl[i];                          // delta_t u_t
       y[i] = 0.f;
@@ -539,7 +539,6 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
   __shared__ __attribute__((aligned(16))) float sC[SCL_TB * SCL_SB];
   __shared__ float tu[LC ? SCL_TB * SCL_S : 1], td[LC ? SCL_TB * SCL_S : 1], tz[LC ? SCL_TB * SCL_S : 1], to[LC ? SCL_TB * SCL_S : 1];
   constexpr uint32_t ES = sizeof(T);
-  constexpr float LN2 = 0.6931471805599453f;
   const int lane = threadIdx.x;
   const int dpg = a.Dm / a.G, tpg = (dpg + 63) / 64;
   const int tg = blockIdx.x % tpg, g = (blockIdx.x / tpg) % a.G, b = blockIdx.x / (tpg * a.G);
@@ -603,7 +602,7 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
   };
   auto token = [&](float uu, float draw, float zv, const Rows& rows, bool valid) -> float {
     float dl = draw + db;
-    if (a.softplus) dl = dl > 20.f ? dl : LN2 * log2_fast(1.f + exp2_fast(dl * LOG2E));
+    if (a.softplus) dl = dl > 20.f ? dl : softplus_fast(dl);
     dl = valid ? dl : 0.f;
     const float du = dl * uu;
     // real register pairs: as {v, v} the compiler feeds v_pk_* the low half twice out of (v, whatever register follows) -- and when that
@@ -1045,7 +1044,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
 #pragma unroll
           for (int i = 0; i < LC; i++) {
             float v = dl[i] + db;
-            if (a.softplus) v = v > 20.f ? v : LN2 * log2_fast(1.f + exp2_fast(v * LOG2E));
+            if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
             dl[i] = (t0 + i < a.L) ? v : 0.f;     // tokens past the end: a = 1, b = 0, dy = 0 (identity pairs in both directions)
             dlu[i] = dl[i] * u[i];
             gB[i] = 0.f; ddl[i] = 0.f; ypre[i] = 0.f;
@@ -1141,13 +1140,16 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
           // ---- per-token outputs of this channel: every state index is in
           // u and softplus'(raw delta) from what is still in registers instead of second reads of their rows (the counters show those
           // coming from HBM, + 0.4 GB at batch 64): u = (delta u) / delta, sigmoid(raw) = 1 - exp(-softplus(raw)).  Only a token
-          // whose delta underflowed to exactly 0 has lost its u: then (rare, wave-uniform branch) the row is read again.
+          // whose delta underflowed has lost its u: then (rare, wave-uniform branch) the row is read again.  Underflowed = below 1e-30,
+          // not only exactly 0: softplus(v) = e^v stays nonzero down to the smallest fp32 number, where delta u is denormal (bits of u gone,
+          // or flushed) and 1 / delta overflows.
           float u[LC];
           bool lost = false;
 #pragma unroll
           for (int i = 0; i < LC; i++) {
-            u[i] = dl[i] != 0.f ? dlu[i] * rcp_fast(dl[i]) : 0.f;       // (tokens past the end: delta = 0, u = 0)
-            lost = lost || (dl[i] == 0.f && t0 + i < a.L);
+            const bool tiny = fabsf(dl[i]) < 1e-30f;
+            u[i] = tiny ? 0.f : dlu[i] * rcp_fast(dl[i]);               // (tokens past the end: delta = 0, u = 0)
+            lost = lost || (tiny && t0 + i < a.L);
           }
           if (__builtin_expect(ballot_any(lost), 0)) ssc_load_row<T, LC>(urow, t0, a.L, u);
           if (zrow) {
@@ -1166,7 +1168,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
           for (int i = 0; i < LC; i++) {
             dDl = fmaf(dy[i], u[i], dDl);
             ddl[i] = fmaf(gB[i], u[i], ddl[i]);
-            if (a.softplus) ddl[i] *= dl[i] < 1e-3f ? dl[i] * (1.f - 0.5f * dl[i]) : 1.f - exp2_fast(-dl[i] * LOG2E);   // sigmoid(raw) = 1 - exp(-softplus(raw))
+            if (a.softplus) ddl[i] *= sigmoid_of_softplus(dl[i]);   // sigmoid(raw) = 1 - exp(-softplus(raw))
             if (t0 + i >= a.L) ddl[i] = 0.f;
             ddbl += ddl[i];
             gB[i] = fmaf(gB[i], dl[i], Dv * dy[i]);   // du
@@ -1282,7 +1284,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
   const uint32_t usl_ = ES * (uint32_t)a.usl, dsl_ = ES * (uint32_t)a.dsl, zsl_ = hasz ? ES * (uint32_t)a.zsl : 0u, gsl_ = ES * (uint32_t)q.gsl;
   auto softplus_of = [&](uint32_t raw, int t) -> float {   // delta of token t (zero behind the end of the sequence: the identity step)
     float v = raw_to_f32<T>(raw) + db;
-    if (a.softplus) v = v > 20.f ? v : LN2 * log2_fast(1.f + exp2_fast(v * LOG2E));
+    if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
     return t < a.L ? v : 0.f;
   };
   // The token loops are REAL loops (one token per iteration, the 16 states unrolled inside): unrolled over a sub-tile the compiler kept the
@@ -1358,7 +1360,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
       if (hasz) buf_st_t<T>(DZr, go * fmaf(Dv, u_, ych) * sg * (1.f + zv * (1.f - sg)), dzvo, ES * (uint32_t)t * (uint32_t)q.dzsl);
       buf_st_t<T>(DUr, fmaf(dlt, sbg, Dv * dy), duvo, ES * (uint32_t)t * (uint32_t)q.dusl);
       float ddr = fmaf(sgap, LN2, u_ * sbg);
-      if (a.softplus) ddr *= 1.f - exp2_fast(-dlt * LOG2E);     // softplus'(x) = sigmoid(x) = 1 - exp(-softplus(x))
+      if (a.softplus) ddr *= sigmoid_of_softplus(dlt);     // softplus'(x) = sigmoid(x) = 1 - exp(-softplus(x))
       ddr = t < a.L ? ddr : 0.f;
       dba += ddr;
       buf_st_t<T>(DDr, ddr, ddvo, ES * (uint32_t)t * (uint32_t)q.ddsl);

@@ -48,9 +48,7 @@ __global__ __launch_bounds__(256) void ssd_dt_prep_kernel(DtPrepArgs a) {
         // softplus and its derivative from ONE hardware exp2: e = exp(v), u = 1 + e; log1p(e) = log(u) e / (u - 1) repairs the
         // rounding of 1 + e (classic compensation), sigmoid(v) = e / u.  The libm forms (expf, log1pf, a second expf) were ~150
         // instructions per element: the 2 M elements of the 1.3B shape kept this launch VALU bound at 17 us.
-        const float e = exp2_fast(v * LOG2E), u = 1.f + e;
-        d = e * rcp_fast(u);
-        v = u == 1.f ? e : log2_fast(u) * 0.6931471805599453f * e * rcp_fast(u - 1.f);
+        v = softplus_fast(v, d);
       }
       if (v < a.lo) { v = a.lo; d = 0.f; }
       if (v > a.hi) { v = a.hi; d = 0.f; }
@@ -109,9 +107,7 @@ __global__ __launch_bounds__(256) void ssd_dt_prep_vec_kernel(DtPrepArgs a) {
       for (int e = 0; e < 2; e++) {
         float v = raw[j][e] + bias[e], d = 1.f;
         if (a.softplus && v <= 20.f) {
-          const float ex = exp2_fast(v * LOG2E), u = 1.f + ex;
-          d = ex * rcp_fast(u);
-          v = u == 1.f ? ex : log2_fast(u) * 0.6931471805599453f * ex * rcp_fast(u - 1.f);
+          v = softplus_fast(v, d);
         }
         if (v < a.lo) { v = a.lo; d = 0.f; }
         if (v > a.hi) { v = a.hi; d = 0.f; }

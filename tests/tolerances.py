@@ -90,3 +90,48 @@ def op_bound(ref, dtype, arith=OP_ARITH):
     exact answer to `dtype`, measured on this slice, plus the fp32 arithmetic allowance, with 10 % slack."""
     q = 0.0 if dtype in (torch.float32, torch.float64) else rel(ref.to(dtype), ref)
     return 1.1 * math.sqrt(q * q + arith * arith)
+
+
+SLICE_FLOOR = 0.1
+
+
+def slice_check(name, got, ref, dtype, keep, arith=OP_ARITH, bound=None, groups=None):
+    """op_bound on every slice of one output (the selective scan; module docstring for the rule).  The first `keep` dimensions index
+    the slices, the others are reduced: out / du / ddelta / dz (B, D, L) keep 2 = a (batch, channel) row over L; input-dependent
+    dB / dC (B, G, N, L) keep 3; dA and constant dB / dC (D, N) keep 1; states (B, D, N) keep 2; dD / ddelta_bias (D) keep 1 = each
+    element.  `ref` is the unrounded fp64 answer, `dtype` the dtype the kernel stored (fp32 sums: q = 0).
+
+    The relative error of slice s is |got_s - ref_s| / max(|ref_s|, SLICE_FLOOR * RMS over the tensor's slices of |ref_s|): a
+    slice that is small by cancellation (or belongs to a channel whose regime makes it small) is judged on an absolute scale and
+    none is left out.  q_s, the one rounding of ref_s to `dtype`, is measured with the same denominator; for a slice of ONE element of
+    a 16-bit dtype it is half an ulp instead (the measured rounding of a single number can be anything down to 0, and a sum that is off
+    by 1e-6 may round the other way).  `groups` (a tensor of ids over the last slice dimension, i.e. per channel): the RMS of the floor
+    is taken inside each group where that is SMALLER than the tensor's -- channels of different decay regimes in one launch, whose
+    slices differ by orders of magnitude, are each judged on their own scale and never on a larger one than without groups.
+    `bound`: a flat number per slice in place of op_bound (two launches that must agree).  Fails naming the tensor, the slice, its error, q and bound; returns
+    (worst error, q of that slice, its bound, share of slices that met the floor)."""
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    assert got.shape == ref.shape, (name, tuple(got.shape), tuple(ref.shape))
+    assert torch.isfinite(got).all(), f"{name}: not finite"
+    lead = tuple(ref.shape[:keep])
+    g2, r2 = got.reshape(*lead, -1), ref.reshape(*lead, -1)
+    norms = r2.norm(dim=-1)
+    floor = SLICE_FLOOR * norms.pow(2).mean().sqrt()
+    if groups is not None:
+        gl, floor = groups.expand(lead), floor.expand(lead).clone()
+        for gid in groups.unique():
+            m = gl == gid
+            floor[m] = torch.minimum(floor[m], SLICE_FLOOR * norms[m].pow(2).mean().sqrt())
+    den = torch.maximum(norms, floor).clamp_min(1e-300)
+    err = (g2 - r2).norm(dim=-1) / den
+    if dtype in (torch.float32, torch.float64):
+        q = torch.zeros_like(err)
+    else:
+        q = 0.5 * torch.finfo(dtype).eps * norms / den if r2.shape[-1] == 1 else (r2.to(dtype).double() - r2).norm(dim=-1) / den
+    lim = torch.full_like(err, bound) if bound is not None else 1.1 * (q * q + arith * arith).sqrt()
+    share = (norms < floor).double().mean().item()
+    i = int((err / lim).argmax())
+    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), lead)) if lead else ()
+    e, qq, b = err.flatten()[i].item(), q.flatten()[i].item(), lim.flatten()[i].item()
+    assert e <= b, f"{name}: slice {idx} error {e:.3e} q {qq:.3e} bound {b:.3e} ({int((err > lim).sum())} of {err.numel()} slices over)"
+    return e, qq, b, share
