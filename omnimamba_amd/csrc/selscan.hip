@@ -60,6 +60,22 @@ __device__ __forceinline__ void ss_store_tile(T* g, int64_t sd, int64_t sl, int 
   }
 }
 
+// channel tile of a workgroup: blockIdx.x = (batch, group, tile of W adjacent channels of the group); thread c owns channel d0 + c
+// (a thread behind the group's last channel is not live and reads channel d0)
+struct SsTile { int g, b, d0, nd, d; bool live; };
+__device__ __forceinline__ SsTile ss_tile(const SsArgs& a, int W) {
+  SsTile t;
+  const int dpg = a.Dm / a.G;                       // channels per group
+  const int tiles_per_group = (dpg + W - 1) / W;
+  const int tg = blockIdx.x % tiles_per_group;
+  t.g = (blockIdx.x / tiles_per_group) % a.G; t.b = blockIdx.x / (tiles_per_group * a.G);
+  t.d0 = t.g * dpg + tg * W;
+  t.nd = (dpg - tg * W) < W ? (dpg - tg * W) : W;
+  t.live = (int)threadIdx.x < t.nd;
+  t.d = t.d0 + (t.live ? (int)threadIdx.x : 0);
+  return t;
+}
+
 template <class T, int NREG>
 __global__ void selscan_fwd_kernel(SsArgs a) {
   OMK_DYN_SMEM(smem);
@@ -70,6 +86,8 @@ __global__ void selscan_fwd_kernel(SsArgs a) {
   T* so = sz + SS_TL * DT;
   float* sB = (float*)(so + SS_TL * DT);   // [TL][N]
   float* sC = sB + SS_TL * a.N;
+  // (the decode of ss_tile spelled out: the recurrence below is written without fmaf, so which products the compiler fuses, and with it
+  // register use and code size of this kernel, is sensitive to how the code around it is split; selscan_bwd_kernel does the same)
   const int dpg = a.Dm / a.G;                       // channels per group
   const int tiles_per_group = (dpg + DT - 1) / DT;
   const int tg = blockIdx.x % tiles_per_group, g = (blockIdx.x / tiles_per_group) % a.G, b = blockIdx.x / (tiles_per_group * a.G);
@@ -154,6 +172,9 @@ __global__ void selscan_fwd_kernel(SsArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 constexpr int SSC_LC_MAX = 16;   // tokens per lane and pass: 16 (fewer scans per token) or 8 (half the registers: more waves per SIMD)
 
+// one step of the wave scans of affine pairs (not on the emulator); both scans below use it
+#define OMK_AFF_STEP(ctrl) \
+  "v_fmac_f32_dpp %0, %0, %1 " ctrl "\n\tv_mul_f32_dpp %1, %1, %1 " ctrl "\n\ts_nop 0\n\t"
 __device__ __forceinline__ void wave_scan_affine(float& p, float& x) {
 #ifdef OMK_EMU
   for (int off = 1; off < 64; off <<= 1) {
@@ -166,8 +187,6 @@ __device__ __forceinline__ void wave_scan_affine(float& p, float& x) {
   // __builtin_amdgcn_update_dpp the compiler built every step from two moves of the identity, two v_mov_dpp, a nop, the fmac and
   // the mul (7 instructions x 6 steps of a VALU-bound loop).  Hand-placed wait states: a DPP read needs two after the VALU write
   // of its source (x: mul + nop; p: nop + fmac); inline assembly gets no hazard recogniser.
-#define OMK_AFF_STEP(ctrl) \
-  "v_fmac_f32_dpp %0, %0, %1 " ctrl "\n\tv_mul_f32_dpp %1, %1, %1 " ctrl "\n\ts_nop 0\n\t"
   asm volatile("s_nop 1\n\t"
                OMK_AFF_STEP("row_shr:1 row_mask:0xf bank_mask:0xf")
                OMK_AFF_STEP("row_shr:2 row_mask:0xf bank_mask:0xf")
@@ -176,9 +195,35 @@ __device__ __forceinline__ void wave_scan_affine(float& p, float& x) {
                OMK_AFF_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")
                OMK_AFF_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")
                : "+v"(x), "+v"(p));
-#undef OMK_AFF_STEP
 #endif
 }
+// the chunked backward's reverse scan
+__device__ __forceinline__ void wave_scan_affine_rev(float& p, float& x) {
+  // suffix composition: lane j <- pairs of lanes j .. 63, the pair of the LOWER lane applied last
+#ifdef OMK_EMU
+  for (int off = 1; off < 64; off <<= 1) {
+    const float ps = shfl_down(p, off), xs = shfl_down(x, off);
+    if (lane_id() + off < 64) { x = fmaf(p, xs, x); p = p * ps; }
+  }
+#else
+  // (steps as in wave_scan_affine: the DPP modifier on the fmac / mul themselves, lanes without a source are not written)
+  asm volatile("s_nop 1\n\t"
+               OMK_AFF_STEP("row_shl:1 row_mask:0xf bank_mask:0xf")
+               OMK_AFF_STEP("row_shl:2 row_mask:0xf bank_mask:0xf")
+               OMK_AFF_STEP("row_shl:4 row_mask:0xf bank_mask:0xf")
+               OMK_AFF_STEP("row_shl:8 row_mask:0xf bank_mask:0xf")
+               : "+v"(x), "+v"(p));
+  // lanes 16 / 32 / 48 hold the totals of rows 1 / 2 / 3; row r still needs rows r + 1 .. 3
+  const float p1 = wave_read_lane(p, 16), x1 = wave_read_lane(x, 16), p2 = wave_read_lane(p, 32), x2 = wave_read_lane(x, 32);
+  const float p3 = wave_read_lane(p, 48), x3 = wave_read_lane(x, 48);
+  const float p23 = p2 * p3, x23 = fmaf(p2, x3, x2), p123 = p1 * p23, x123 = fmaf(p1, x23, x1);
+  const int row = lane_id() >> 4;
+  const float ps = row == 0 ? p123 : row == 1 ? p23 : row == 2 ? p3 : 1.f;
+  const float xs = row == 0 ? x123 : row == 1 ? x23 : row == 2 ? x3 : 0.f;
+  x = fmaf(p, xs, x); p = p * ps;
+#endif
+}
+#undef OMK_AFF_STEP
 
 // SSC_LC consecutive elements of a unit-stride row starting at t0 (tokens >= L read as 0); 16-byte vectors when possible
 template <class T, int SSC_LC>
@@ -217,18 +262,105 @@ __device__ __forceinline__ void ssc_store_row(T* row, int t0, int L, const float
   }
 }
 
+// ---- fragments shared by the chunked kernels (forward, shared-row forward, backward) and, the first, by the lanes kernels
+// delta of one token: + bias, softplus (the value itself above 20: softplus_fast is for v <= 20), zero behind the end of the sequence --
+// there a = 1, b = 0 (the identity pair / step)
+__device__ __forceinline__ float ss_delta(float raw, float db, int softplus, bool valid) {
+  float v = raw + db;
+  if (softplus) v = v > 20.f ? v : softplus_fast(v);
+  return valid ? v : 0.f;
+}
+// the lane's chunk of tokens t0 .. t0 + LC: dl[] raw delta -> delta, dlu[] = delta_t u_t (dlu may be u itself)
+template <int LC>
+__device__ __forceinline__ void ssc_delta_chunk(float (&dl)[LC], const float (&u)[LC], float (&dlu)[LC], float db, int softplus, int t0, int L) {
+#pragma unroll
+  for (int i = 0; i < LC; i++) {
+    dl[i] = ss_delta(dl[i], db, softplus, t0 + i < L);
+    dlu[i] = dl[i] * u[i];
+  }
+}
+// the chunk's decay is exp2(A2 * sum of delta): one product per n instead of a running one
+template <int LC>
+__device__ __forceinline__ float ssc_delta_sum(const float (&dl)[LC]) {
+  float sdl = 0.f;
+#pragma unroll
+  for (int i = 0; i < LC; i++) sdl += dl[i];
+  return sdl;
+}
+// LDS image of a staged B / C row of a pass (64 * LC tokens of T): the 16-byte piece v of lane j's tokens at slot v * 64 + j, so a
+// ds_read_b128 of a wave is 1 KB contiguous.  ssc_slot = the element offset of that piece (also the fp32 accumulator rows of the backward)
+template <class T>
+__device__ __forceinline__ int ssc_slot(int v, int j) { return (v * 64 + j) * (int)(16 / sizeof(T)); }
+// the fill, one 16-byte piece: tokens tq .. of a global row (src) -> dst, its slot of the image (tokens >= L are zeros)
+template <class T>
+__device__ __forceinline__ void ssc_copy_piece(const T* src, int tq, int L, T* dst) {
+  constexpr int VEC = 16 / sizeof(T);
+  if (tq + VEC <= L && (((uintptr_t)src) & 15) == 0) {
+    *reinterpret_cast<vec_t<T, VEC>*>(dst) = *reinterpret_cast<const vec_t<T, VEC>*>(src);
+  } else {
+#pragma unroll
+    for (int e = 0; e < VEC; e++) dst[e] = tq + e < L ? src[e] : T{};
+  }
+}
+// piece q of the tokens tile0 .. of a global row -> its slot of the row's image img
+template <class T, int LC>
+__device__ __forceinline__ void ssc_stage_piece(const T* row, int q, int tile0, int L, T* img) {
+  constexpr int VEC = 16 / sizeof(T);
+  const int e0 = q * VEC, tq = tile0 + e0;
+  ssc_copy_piece<T>(row + tq, tq, L, img + ssc_slot<T>((e0 % LC) / VEC, e0 / LC));
+}
+// the read-back: the lane's LC tokens of a staged B row and (WITH_C) of a staged C row, piece by piece in turn.  pB / pC = the row's image
+// at the lane's first piece, image + ssc_slot(0, lane): the kernels keep that lane offset out of their n loops
+template <class T, int LC, bool WITH_C = true>
+__device__ __forceinline__ void ssc_read_rows(const T* pB, const T* pC, float (&Bv)[LC], float (&Cv)[LC]) {
+  constexpr int VEC = 16 / sizeof(T);
+#pragma unroll
+  for (int v = 0; v < LC / VEC; v++) {
+    float wb[VEC], wc[VEC];
+    load_vec<T, VEC>(pB + ssc_slot<T>(v, 0), wb);
+    if (WITH_C) load_vec<T, VEC>(pC + ssc_slot<T>(v, 0), wc);
+#pragma unroll
+    for (int e = 0; e < VEC; e++) { Bv[v * VEC + e] = wb[e]; Cv[v * VEC + e] = WITH_C ? wc[e] : 0.f; }
+  }
+}
+// from the lane's folded pair (P, X) to the state at the start of its chunk: scan across the wave, apply the state *carry in front of the
+// pass, hand the state at the end of the chunk (xend) to the next lane.  *carry is an LDS slot another lane of the wave may have written
+// just before: it is read behind the scan, whose shuffles order the two
+__device__ __forceinline__ float ssc_chunk_start(float P, float X, const float* carry, int lane, float& xend) {
+  wave_scan_affine(P, X);
+  const float cin = *carry;
+  xend = fmaf(P, cin, X);                 // state at the end of this lane's chunk
+  float x = shfl_up(xend, 1);
+  if (lane == 0) x = cin;
+  return x;
+}
+// epilogue of the chunked forward: + D u, gate, store   (the kernel's u[] holds delta u: the raw u is re-read -- it is still in L1)
+// (the shared-row forward has the same lines in place)
+template <class T, int LC>
+__device__ __forceinline__ void ssc_epilogue(const T* urow, const T* zrow, T* orow, int t0, int L, float Dv, float (&y)[LC]) {
+  float ur[LC];
+  ssc_load_row<T, LC>(urow, t0, L, ur);
+  if (zrow) {
+    float zv[LC];
+    ssc_load_row<T, LC>(zrow, t0, L, zv);
+#pragma unroll
+    for (int i = 0; i < LC; i++) y[i] = fmaf(Dv, ur[i], y[i]) * silu_fast(zv[i]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < LC; i++) y[i] = fmaf(Dv, ur[i], y[i]);
+  }
+  ssc_store_row<T, LC>(orow, t0, L, y);
+}
+
 // general form (any B / C kind and dtype, any channel count): every wave pulls its own rows through L1
 template <class T, int SSC_LC>
 __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
-  constexpr bool SHARE = false;
-  constexpr int VEC = 16 / sizeof(T);
   __shared__ float scarry[4][64];   // per wave: state at the start of the pass, per n
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t seq = (int64_t)blockIdx.x * 4 + wv;   // the four waves of a workgroup: adjacent channels of one batch element
   if (seq >= (int64_t)a.B * a.Dm) return;
   const int b = (int)(seq / a.Dm), d = (int)(seq % a.Dm);
   const int g = d / (a.Dm / a.G);
-  T* sBC = nullptr;
   const T* urow = (const T*)a.u + (int64_t)b * a.usb + (int64_t)d * a.usd;
   const T* drow = (const T*)a.delta + (int64_t)b * a.dsb + (int64_t)d * a.dsd;
   const T* zrow = a.z ? (const T*)a.z + (int64_t)b * a.zsb + (int64_t)d * a.zsd : nullptr;
@@ -244,28 +376,14 @@ __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
     float u[SSC_LC], dl[SSC_LC], y[SSC_LC];
     ssc_load_row<T, SSC_LC>(urow, t0, a.L, u);
     ssc_load_row<T, SSC_LC>(drow, t0, a.L, dl);
+    ssc_delta_chunk<SSC_LC>(dl, u, u, db, a.softplus, t0, a.L);   // u[] = delta u from here on
+    const float sdl = ssc_delta_sum<SSC_LC>(dl);
 #pragma unroll
-    for (int i = 0; i < SSC_LC; i++) {
-      float v = dl[i] + db;
-      if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
-      dl[i] = (t0 + i < a.L) ? v : 0.f;     // tokens past the end: a = 1, b = 0 (the identity pair)
-      u[i] *= dl[i];                          // delta_t u_t
-      y[i] = 0.f;
-    }
+    for (int i = 0; i < SSC_LC; i++) y[i] = 0.f;
     // B_t[n] / C_t[n] rows of the lane's tokens: the rows of n + 1 are requested before n is computed (one L2 round trip per n
     // would otherwise sit in front of every scan)
-    auto lds_row = [&](const T* rowp, float (&o)[SSC_LC]) {
-#pragma unroll
-      for (int v = 0; v < SSC_LC / VEC; v++) {
-        float w[VEC];
-        load_vec<T, VEC>(rowp + (v * 64 + lane) * VEC, w);
-#pragma unroll
-        for (int e = 0; e < VEC; e++) o[v * VEC + e] = w[e];
-      }
-    };
     auto load_bc = [&](int n, float (&Bo)[SSC_LC], float (&Co)[SSC_LC]) {
-      if (SHARE && a.Bvar) lds_row(sBC + (size_t)n * (64 * SSC_LC), Bo);
-      else if (a.Bvar) {
+      if (a.Bvar) {
         const int64_t ro = (int64_t)b * a.Bsb + (int64_t)g * a.Bsg + (int64_t)n * a.Bsn;
         if (a.bdt == dtype_of<T>::value) ssc_load_row<T, SSC_LC>((const T*)a.Bm + ro, t0, a.L, Bo);
         else {
@@ -277,8 +395,7 @@ __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
 #pragma unroll
         for (int i = 0; i < SSC_LC; i++) Bo[i] = bc;
       }
-      if (SHARE && a.Cvar) lds_row(sBC + ((size_t)(a.Bvar ? a.N : 0) + n) * (64 * SSC_LC), Co);
-      else if (a.Cvar) {
+      if (a.Cvar) {
         const int64_t ro = (int64_t)b * a.Csb + (int64_t)g * a.Csg + (int64_t)n * a.Csn;
         if (a.cdt == dtype_of<T>::value) ssc_load_row<T, SSC_LC>((const T*)a.Cm + ro, t0, a.L, Co);
         else {
@@ -292,19 +409,13 @@ __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
       }
     };
     float Bn[SSC_LC], Cn[SSC_LC];
-    if (!SHARE) load_bc(0, Bn, Cn);
-    float sdl = 0.f;   // the chunk's decay is exp2(A2 * sum of delta): one product per n instead of a running one
-#pragma unroll
-    for (int i = 0; i < SSC_LC; i++) sdl += dl[i];
+    load_bc(0, Bn, Cn);
     for (int n = 0; n < a.N; n++) {
       const float A2 = load_rt(a.A, (int64_t)d * a.Asd + (int64_t)n * a.Asn, a.adt) * LOG2E;
       float Bv[SSC_LC], Cv[SSC_LC];
-      if (SHARE) load_bc(n, Bv, Cv);
-      else {
 #pragma unroll
-        for (int i = 0; i < SSC_LC; i++) { Bv[i] = Bn[i]; Cv[i] = Cn[i]; }
-        load_bc(n + 1 < a.N ? n + 1 : n, Bn, Cn);
-      }
+      for (int i = 0; i < SSC_LC; i++) { Bv[i] = Bn[i]; Cv[i] = Cn[i]; }
+      load_bc(n + 1 < a.N ? n + 1 : n, Bn, Cn);
       // ---- reduce: the chunk as an affine map x -> P x + X
       float av[SSC_LC];
       float P = exp2_fast(sdl * A2), X = 0.f;
@@ -315,11 +426,8 @@ __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
         X = fmaf(av[i], X, Bv[i]);
       }
       // ---- scan across the wave, then the start state of this lane's chunk
-      wave_scan_affine(P, X);
-      const float cin = carry[n];
-      const float xend = fmaf(P, cin, X);                 // state at the end of this lane's chunk
-      float x = shfl_up(xend, 1);
-      if (lane == 0) x = cin;
+      float xend;
+      float x = ssc_chunk_start(P, X, &carry[n], lane, xend);
       const float cout = wave_read_lane(xend, 63);
       // ---- downsweep
 #pragma unroll
@@ -329,30 +437,16 @@ __global__ __launch_bounds__(256) void selscan_fwd_chunked_kernel(SsArgs a) {
       }
       if (lane == 0) carry[n] = cout;
     }
-    if (!orow) continue;
-    // ---- epilogue: + D u, gate, store   (u[] holds delta u: the raw u is re-read -- it is still in L1)
-    float ur[SSC_LC];
-    ssc_load_row<T, SSC_LC>(urow, t0, a.L, ur);
-    if (zrow) {
-      float zv[SSC_LC];
-      ssc_load_row<T, SSC_LC>(zrow, t0, a.L, zv);
-#pragma unroll
-      for (int i = 0; i < SSC_LC; i++) y[i] = fmaf(Dv, ur[i], y[i]) * (zv[i] * rcp_fast(1.f + exp2_fast(-zv[i] * LOG2E)));
-    } else {
-#pragma unroll
-      for (int i = 0; i < SSC_LC; i++) y[i] = fmaf(Dv, ur[i], y[i]);
-    }
-    ssc_store_row<T, SSC_LC>(orow, t0, a.L, y);
+    if (orow) ssc_epilogue<T, SSC_LC>(urow, zrow, orow, t0, a.L, Dv, y);
   }
   if (a.last && lane < a.N) a.last[((int64_t)b * a.Dm + d) * a.N + lane] = carry[lane];
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // the same scan for the common case -- B and C both (B, G, N, L) rows of u's dtype, A fp32, 8 | channels per group: the eight
-// waves of a workgroup are eight adjacent channels of one (batch, group) and SHARE the B / C rows of a pass through LDS
+// waves of a workgroup are eight adjacent channels of one (batch, group) and share the B / C rows of a pass through LDS
 // (one coalesced fill per pass; the per-wave form pulls every row through the CU's L1 once per channel), A2 = A log2 e of
-// the wave's channel sits in LDS too, and the n loop carries no dtype or layout branches.
-// LDS image of a row: the 16-byte piece v of lane j's tokens at slot v * 64 + j, so a ds_read_b128 of a wave is 1 KB contiguous.
+// the wave's channel sits in LDS too, and the n loop carries no dtype or layout branches.  (LDS image of a row: ssc_slot.)
 // ---------------------------------------------------------------------------------------------------------
 // STATE_ONLY (first pass of the chunked backward): no C rows, no y, no output -- the state in front of every pass of 64 * SSC_LC
 // tokens goes to a.ckpt as (B, D, passes, N) f32
@@ -382,111 +476,70 @@ __global__ __launch_bounds__(512) void selscan_fwd_shared_kernel(SsArgs a) {
     block_sync();   // every wave is done with the rows of the previous pass
     if ((STATE_ONLY || a.ckpt) && lane < a.N) a.ckpt[(((int64_t)b * a.Dm + d) * a.nTB + tile0 / (64 * SSC_LC)) * a.N + lane] = carry[lane];
     for (int i = threadIdx.x; i < (STATE_ONLY ? 1 : 2) * a.N * PPR; i += 512) {
+      // (ssc_stage_piece with its index arithmetic in place, and below the epilogue in place of ssc_epilogue: with either as a call the
+      // packed fp32 form is scheduled differently -- one VGPR and four instructions more, 1 % slower at batch 64)
       const int r = i / PPR, q = i % PPR;
       const T* row = r < a.N ? Bbase + (int64_t)r * a.Bsn : Cbase + (int64_t)(r - a.N) * a.Csn;
       const int e0 = q * VEC, tq = tile0 + e0;
-      T* dst = sBC + (size_t)r * (64 * SSC_LC) + ((e0 % SSC_LC) / VEC * 64 + e0 / SSC_LC) * VEC;
-      const T* src = row + tq;
-      if (tq + VEC <= a.L && (((uintptr_t)src) & 15) == 0) {
-        *reinterpret_cast<vec_t<T, VEC>*>(dst) = *reinterpret_cast<const vec_t<T, VEC>*>(src);
-      } else {
-#pragma unroll
-        for (int e = 0; e < VEC; e++) dst[e] = tq + e < a.L ? src[e] : T{};
-      }
+      ssc_copy_piece<T>(row + tq, tq, a.L, sBC + (size_t)r * (64 * SSC_LC) + ssc_slot<T>((e0 % SSC_LC) / VEC, e0 / SSC_LC));
     }
     float u[SSC_LC], dl[SSC_LC], y[SSC_LC];
     ssc_load_row<T, SSC_LC>(urow, t0, a.L, u);
     ssc_load_row<T, SSC_LC>(drow, t0, a.L, dl);
-    float sdl = 0.f;   // the chunk's decay is exp2(A2 * sum of delta)
+    ssc_delta_chunk<SSC_LC>(dl, u, u, db, a.softplus, t0, a.L);   // u[] = delta u from here on
+    const float sdl = ssc_delta_sum<SSC_LC>(dl);
 #pragma unroll
-    for (int i = 0; i < SSC_LC; i++) {
-      float v = dl[i] + db;
-      if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
-      dl[i] = (t0 + i < a.L) ? v : 0.f;     // tokens past the end: a = 1, b = 0 (the identity pair)
-      u[i] *= dl[i];                          // delta_t u_t
-      y[i] = 0.f;
-      sdl += dl[i];
-    }
+    for (int i = 0; i < SSC_LC; i++) y[i] = 0.f;
     block_sync();   // rows staged
-    const T* pB = sBC + lane * VEC;
+    const T* pB = sBC + ssc_slot<T>(0, lane);
     const T* pC = pB + (size_t)a.N * (64 * SSC_LC);
+    // NU == 2: the elementwise half of the n loop on PACKED fp32 pairs of adjacent tokens (v_pk_mul_f32 / v_pk_fma_f32: two tokens per
+    // issue): delta A2, delta u B and the y accumulation.  The two recurrences (fold, sweep) are serial in the token index and the
+    // exponentials are not packable; the loop is VALU-bound, so instructions are time.
+    constexpr int HP = SSC_LC / 2;
+    f32x2 dl2[HP], u2[HP], y2[HP];
     if (NU == 2) {
-      // the elementwise half of the n loop on PACKED fp32 pairs of adjacent tokens (v_pk_mul_f32 / v_pk_fma_f32: two tokens per
-      // issue): delta A2, delta u B and the y accumulation.  The two recurrences (fold, sweep) are serial in the token index and the
-      // exponentials are not packable; the loop is VALU-bound, so instructions are time.
-      constexpr int HP = SSC_LC / 2;
-      f32x2 dl2[HP], u2[HP], y2[HP];
 #pragma unroll
       for (int j = 0; j < HP; j++) { dl2[j] = f32x2{dl[2 * j], dl[2 * j + 1]}; u2[j] = f32x2{u[2 * j], u[2 * j + 1]}; y2[j] = f32x2{0.f, 0.f}; }
-      for (int n = 0; n < a.N; n++) {
-        const float A2 = sA2[wv][n];
+    }
+    for (int n = 0; n < a.N; n++) {
+      const float A2 = sA2[wv][n];
+      float Bv[SSC_LC], Cv[SSC_LC], av[SSC_LC];   // NU == 1: Bv becomes b_t
+      f32x2 bt2[HP], av2[HP];                     // NU == 2: the same as pairs
+      ssc_read_rows<T, SSC_LC, !STATE_ONLY>(pB + (size_t)n * (64 * SSC_LC), pC + (size_t)n * (64 * SSC_LC), Bv, Cv);
+      // ---- reduce: the chunk as an affine map x -> P x + X
+      float P = exp2_fast(sdl * A2), X = 0.f;
+      if (NU == 2) {
         const f32x2 A22 = {A2, A2};
-        f32x2 bt2[HP], C2[HP], av2[HP];
-#pragma unroll
-        for (int v = 0; v < SSC_LC / VEC; v++) {
-          float wb[VEC], wc[VEC];
-          load_vec<T, VEC>(pB + (size_t)n * (64 * SSC_LC) + v * 64 * VEC, wb);
-          if (!STATE_ONLY) load_vec<T, VEC>(pC + (size_t)n * (64 * SSC_LC) + v * 64 * VEC, wc);
-#pragma unroll
-          for (int e = 0; e < VEC; e += 2) {
-            bt2[(v * VEC + e) / 2] = f32x2{wb[e], wb[e + 1]};
-            C2[(v * VEC + e) / 2] = STATE_ONLY ? f32x2{0.f, 0.f} : f32x2{wc[e], wc[e + 1]};
-          }
-        }
-        float P = exp2_fast(sdl * A2), X = 0.f;
 #pragma unroll
         for (int j = 0; j < HP; j++) {
           const f32x2 e2 = dl2[j] * A22;
           av2[j] = f32x2{exp2_fast(e2[0]), exp2_fast(e2[1])};
-          bt2[j] = bt2[j] * u2[j];                 // b_t = delta_t u_t B_t[n]
+          bt2[j] = f32x2{Bv[2 * j], Bv[2 * j + 1]} * u2[j];                 // b_t = delta_t u_t B_t[n]
           X = fmaf(av2[j][0], X, bt2[j][0]);
           X = fmaf(av2[j][1], X, bt2[j][1]);
         }
-        wave_scan_affine(P, X);
-        const float cin = carry[n];
-        const float xend = fmaf(P, cin, X);
-        float x = shfl_up(xend, 1);
-        if (lane == 0) x = cin;
-        const float cout = wave_read_lane(xend, 63);
-        if (!STATE_ONLY) {
+      } else {
 #pragma unroll
-          for (int j = 0; j < HP; j++) {
-            const float xa = fmaf(av2[j][0], x, bt2[j][0]);
-            x = fmaf(av2[j][1], xa, bt2[j][1]);
-            y2[j] = C2[j] * f32x2{xa, x} + y2[j];
-          }
+        for (int i = 0; i < SSC_LC; i++) {
+          av[i] = exp2_fast(dl[i] * A2);
+          Bv[i] *= u[i];                        // b_t = delta_t u_t B_t[n]
+          X = fmaf(av[i], X, Bv[i]);
         }
-        if (lane == 0) carry[n] = cout;
       }
-#pragma unroll
-      for (int j = 0; j < HP; j++) { y[2 * j] = y2[j][0]; y[2 * j + 1] = y2[j][1]; }
-    } else {
-    for (int n = 0; n < a.N; n++) {
-      const float A2 = sA2[wv][n];
-      float Bv[SSC_LC], Cv[SSC_LC];
-#pragma unroll
-      for (int v = 0; v < SSC_LC / VEC; v++) {
-        float wb[VEC], wc[VEC];
-        load_vec<T, VEC>(pB + (size_t)n * (64 * SSC_LC) + v * 64 * VEC, wb);
-        if (!STATE_ONLY) load_vec<T, VEC>(pC + (size_t)n * (64 * SSC_LC) + v * 64 * VEC, wc);
-#pragma unroll
-        for (int e = 0; e < VEC; e++) { Bv[v * VEC + e] = wb[e]; Cv[v * VEC + e] = STATE_ONLY ? 0.f : wc[e]; }
-      }
-      float av[SSC_LC];
-      float P = exp2_fast(sdl * A2), X = 0.f;
-#pragma unroll
-      for (int i = 0; i < SSC_LC; i++) {
-        av[i] = exp2_fast(dl[i] * A2);
-        Bv[i] *= u[i];                        // b_t = delta_t u_t B_t[n]
-        X = fmaf(av[i], X, Bv[i]);
-      }
-      wave_scan_affine(P, X);
-      const float cin = carry[n];
-      const float xend = fmaf(P, cin, X);     // state at the end of this lane's chunk
-      float x = shfl_up(xend, 1);
-      if (lane == 0) x = cin;
+      // ---- scan across the wave, then the start state of this lane's chunk
+      float xend;
+      float x = ssc_chunk_start(P, X, &carry[n], lane, xend);
       const float cout = wave_read_lane(xend, 63);
-      if (!STATE_ONLY) {
+      // ---- downsweep
+      if (!STATE_ONLY && NU == 2) {
+#pragma unroll
+        for (int j = 0; j < HP; j++) {
+          const float xa = fmaf(av2[j][0], x, bt2[j][0]);
+          x = fmaf(av2[j][1], xa, bt2[j][1]);
+          y2[j] = f32x2{Cv[2 * j], Cv[2 * j + 1]} * f32x2{xa, x} + y2[j];
+        }
+      } else if (!STATE_ONLY) {
 #pragma unroll
         for (int i = 0; i < SSC_LC; i++) {
           x = fmaf(av[i], x, Bv[i]);
@@ -495,15 +548,19 @@ __global__ __launch_bounds__(512) void selscan_fwd_shared_kernel(SsArgs a) {
       }
       if (lane == 0) carry[n] = cout;
     }
-    }
     if (STATE_ONLY) continue;
+    if (NU == 2) {
+#pragma unroll
+      for (int j = 0; j < HP; j++) { y[2 * j] = y2[j][0]; y[2 * j + 1] = y2[j][1]; }
+    }
+    // ---- epilogue: + D u, gate, store (ssc_epilogue, in place)
     float ur[SSC_LC];
     ssc_load_row<T, SSC_LC>(urow, t0, a.L, ur);
     if (zrow) {
       float zv[SSC_LC];
       ssc_load_row<T, SSC_LC>(zrow, t0, a.L, zv);
 #pragma unroll
-      for (int i = 0; i < SSC_LC; i++) y[i] = fmaf(Dv, ur[i], y[i]) * (zv[i] * rcp_fast(1.f + exp2_fast(-zv[i] * LOG2E)));
+      for (int i = 0; i < SSC_LC; i++) y[i] = fmaf(Dv, ur[i], y[i]) * silu_fast(zv[i]);
     } else {
 #pragma unroll
       for (int i = 0; i < SSC_LC; i++) y[i] = fmaf(Dv, ur[i], y[i]);
@@ -533,6 +590,53 @@ __global__ __launch_bounds__(512) void selscan_fwd_shared_kernel(SsArgs a) {
 constexpr int SCL_TB = 16, SCL_S = 68, SCL_SB = 20;
 constexpr uint32_t SCL_OOR = 0x80000000u;   // lane offset behind every range (ranges are < 2^31 bytes): loads return 0, stores are dropped
 
+// ---- the wave-private B / C tile of the lanes kernels (forward and backward): the rows of a block of 16 tokens x 16 states = four elements
+// per lane and array, in the kernel's own LDS arrays sB / sC ([SCL_TB][SCL_SB] floats each).  The lane's 16-lane group follows whichever
+// of (state, token) has unit stride; states >= d_state are zeros in LDS (their A2 is 0: x stays 0, y gets nothing)
+template <class T>
+struct SclBC {
+  static constexpr uint32_t ES = sizeof(T);
+  BufRes Br, Cr;
+  float* sB; float* sC;
+  int N, r4, t16, blo, bls, clo, cls;
+  bool bl, cl;
+  uint32_t Bsl, Csl, bvo, cvo, bks, cks;
+  uint32_t pb[4], pc[4];     // a fetched block on its way to LDS
+  __device__ __forceinline__ SclBC(const SsArgs& a, int b, int g, int lane, float* sB_, float* sC_) : sB(sB_), sC(sC_) {
+    Br = make_buf((const T*)a.Bm + (int64_t)b * a.Bsb + (int64_t)g * a.Bsg, a.xB);
+    Cr = make_buf((const T*)a.Cm + (int64_t)b * a.Csb + (int64_t)g * a.Csg, a.xC);
+    N = a.N; r4 = lane >> 4; t16 = lane & 15;
+    bl = a.Bsl == 1; cl = a.Csl == 1;
+    Bsl = (uint32_t)a.Bsl; Csl = (uint32_t)a.Csl;
+    bvo = ES * (bl ? (uint32_t)r4 * (uint32_t)a.Bsn + (uint32_t)t16 * (uint32_t)a.Bsl : (uint32_t)t16 * (uint32_t)a.Bsn + (uint32_t)r4 * (uint32_t)a.Bsl);
+    cvo = ES * (cl ? (uint32_t)r4 * (uint32_t)a.Csn + (uint32_t)t16 * (uint32_t)a.Csl : (uint32_t)t16 * (uint32_t)a.Csn + (uint32_t)r4 * (uint32_t)a.Csl);
+    bks = ES * 4u * (uint32_t)(bl ? a.Bsn : a.Bsl); cks = ES * 4u * (uint32_t)(cl ? a.Csn : a.Csl);
+    blo = bl ? t16 * SCL_SB + r4 : r4 * SCL_SB + t16; bls = bl ? 4 : 4 * SCL_SB;
+    clo = cl ? t16 * SCL_SB + r4 : r4 * SCL_SB + t16; cls = cl ? 4 : 4 * SCL_SB;
+  }
+  // raw rows of tokens l0 .. l0 + 15 into registers (behind the end of the (batch, group)'s range: zeros)
+  __device__ __forceinline__ void fetch(int l0) {
+    const uint32_t sb0 = ES * (uint32_t)l0 * Bsl, sc0 = ES * (uint32_t)l0 * Csl;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      pb[k] = buf_ld_raw<T>(Br, bvo, sb0 + (uint32_t)k * bks);
+      pc[k] = buf_ld_raw<T>(Cr, cvo, sc0 + (uint32_t)k * cks);
+    }
+  }
+  // the fetched block -> LDS as [token][state] fp32 (between two wave_lds_sync of the kernel)
+  __device__ __forceinline__ void commit() {
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const bool okb = (bl ? r4 + 4 * k : t16) < N, okc = (cl ? r4 + 4 * k : t16) < N;
+      sB[blo + k * bls] = okb ? raw_to_f32<T>(pb[k]) : 0.f;
+      sC[clo + k * cls] = okc ? raw_to_f32<T>(pc[k]) : 0.f;
+    }
+  }
+  // B_t / C_t of the token in slot `row` of the tile: four float4 broadcast reads each
+  __device__ __forceinline__ const f32x4* brow(int row) const { return reinterpret_cast<const f32x4*>(&sB[row * SCL_SB]); }
+  __device__ __forceinline__ const f32x4* crow(int row) const { return reinterpret_cast<const f32x4*>(&sC[row * SCL_SB]); }
+};
+
 template <class T, bool LC>
 __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
   __shared__ __attribute__((aligned(16))) float sB[SCL_TB * SCL_SB];
@@ -540,12 +644,9 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
   __shared__ float tu[LC ? SCL_TB * SCL_S : 1], td[LC ? SCL_TB * SCL_S : 1], tz[LC ? SCL_TB * SCL_S : 1], to[LC ? SCL_TB * SCL_S : 1];
   constexpr uint32_t ES = sizeof(T);
   const int lane = threadIdx.x;
-  const int dpg = a.Dm / a.G, tpg = (dpg + 63) / 64;
-  const int tg = blockIdx.x % tpg, g = (blockIdx.x / tpg) % a.G, b = blockIdx.x / (tpg * a.G);
-  const int d0 = g * dpg + tg * 64;
-  const int nd = (dpg - tg * 64) < 64 ? (dpg - tg * 64) : 64;
-  const bool live = lane < nd;
-  const int d = d0 + (live ? lane : 0);
+  const SsTile ct = ss_tile(a, 64);
+  const int g = ct.g, b = ct.b, d0 = ct.d0, nd = ct.nd, d = ct.d;
+  const bool live = ct.live;
   const int r4 = lane >> 4, t16 = lane & 15;
   f32x2 A2[8], x2[8];
 #pragma unroll
@@ -560,50 +661,22 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
   const BufRes Ur = make_buf((const T*)a.u + (int64_t)b * a.usb, a.xu), Dr = make_buf((const T*)a.delta + (int64_t)b * a.dsb, a.xd);
   const BufRes Zr = make_buf(hasz ? (const T*)a.z + (int64_t)b * a.zsb : nullptr, hasz ? a.xz : 0u);
   const BufRes Or = make_buf((T*)a.out + (int64_t)b * a.osb, a.xo);
-  const BufRes Br = make_buf((const T*)a.Bm + (int64_t)b * a.Bsb + (int64_t)g * a.Bsg, a.xB);
-  const BufRes Cr = make_buf((const T*)a.Cm + (int64_t)b * a.Csb + (int64_t)g * a.Csg, a.xC);
   const uint32_t usl = (uint32_t)a.usl, dsl = (uint32_t)a.dsl, zsl = (uint32_t)a.zsl, osl = (uint32_t)a.osl;
   const uint32_t usd = (uint32_t)a.usd, dsd = (uint32_t)a.dsd, zsd = (uint32_t)a.zsd, osd = (uint32_t)a.osd;
-  // ---- B / C rows of a block: 16 tokens x 16 states = four elements per lane and array.  The lane's 16-lane group follows whichever
-  // of (state, token) has unit stride; states >= d_state are zeros in LDS (their A2 is 0: x stays 0, y gets nothing)
-  const bool bl = a.Bsl == 1, cl = a.Csl == 1;
-  const uint32_t bvo = ES * (bl ? (uint32_t)r4 * (uint32_t)a.Bsn + (uint32_t)t16 * (uint32_t)a.Bsl : (uint32_t)t16 * (uint32_t)a.Bsn + (uint32_t)r4 * (uint32_t)a.Bsl);
-  const uint32_t cvo = ES * (cl ? (uint32_t)r4 * (uint32_t)a.Csn + (uint32_t)t16 * (uint32_t)a.Csl : (uint32_t)t16 * (uint32_t)a.Csn + (uint32_t)r4 * (uint32_t)a.Csl);
-  const uint32_t bks = ES * 4u * (uint32_t)(bl ? a.Bsn : a.Bsl), cks = ES * 4u * (uint32_t)(cl ? a.Csn : a.Csl);
-  const int blo = bl ? t16 * SCL_SB + r4 : r4 * SCL_SB + t16, bls = bl ? 4 : 4 * SCL_SB;
-  const int clo = cl ? t16 * SCL_SB + r4 : r4 * SCL_SB + t16, cls = cl ? 4 : 4 * SCL_SB;
-  uint32_t pb[4], pc[4];
-  auto fetch_bc = [&](int l0) {
-    const uint32_t sb0 = ES * (uint32_t)l0 * (uint32_t)a.Bsl, sc0 = ES * (uint32_t)l0 * (uint32_t)a.Csl;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      pb[k] = buf_ld_raw<T>(Br, bvo, sb0 + (uint32_t)k * bks);
-      pc[k] = buf_ld_raw<T>(Cr, cvo, sc0 + (uint32_t)k * cks);
-    }
-  };
-  auto commit_bc = [&]() {
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const bool okb = (bl ? r4 + 4 * k : t16) < a.N, okc = (cl ? r4 + 4 * k : t16) < a.N;
-      sB[blo + k * bls] = okb ? raw_to_f32<T>(pb[k]) : 0.f;
-      sC[clo + k * cls] = okc ? raw_to_f32<T>(pc[k]) : 0.f;
-    }
-  };
+  SclBC<T> bc(a, b, g, lane, sB, sC);
   // ---- one token of the lane's channel: row = the token's slot in the B / C tile; a slot behind the end of the sequence (valid = false:
   // its loads came back as zeros) is the identity step delta = 0 -- no branch around the body, whose loads the compiler then counts exactly
   struct Rows { f32x4 b[4], c[4]; };   // B_t / C_t of one token as the broadcast reads deliver them
   auto read_rows = [&](int row) -> Rows {
     Rows r;
-    const f32x4* rb = reinterpret_cast<const f32x4*>(&sB[row * SCL_SB]);
-    const f32x4* rc = reinterpret_cast<const f32x4*>(&sC[row * SCL_SB]);
+    const f32x4* rb = bc.brow(row);
+    const f32x4* rc = bc.crow(row);
 #pragma unroll
     for (int q = 0; q < 4; q++) { r.b[q] = rb[q]; r.c[q] = rc[q]; }
     return r;
   };
   auto token = [&](float uu, float draw, float zv, const Rows& rows, bool valid) -> float {
-    float dl = draw + db;
-    if (a.softplus) dl = dl > 20.f ? dl : softplus_fast(dl);
-    dl = valid ? dl : 0.f;
+    const float dl = ss_delta(draw, db, a.softplus, valid);
     const float du = dl * uu;
     // real register pairs: as {v, v} the compiler feeds v_pk_* the low half twice out of (v, whatever register follows) -- and when that
     // neighbour is the destination of a load still in flight, every packed op waits for the load
@@ -628,7 +701,7 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
     }
     const f32x2 ys = ya + yb;
     float y = fmaf(Dv, uu, ys[0] + ys[1]);
-    if (hasz) y *= zv * rcp_fast(1.f + exp2_fast(-zv * LOG2E));
+    if (hasz) y *= silu_fast(zv);
     return y;
   };
   auto checkpoint = [&](int l0) {   // state in front of token l0 (a multiple of a.TLB): what the chunked backward restarts from
@@ -662,11 +735,11 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
       su += ustep; sd += dstep; sz += zstep;
       OMK_OPAQUE_S(su); OMK_OPAQUE_S(sd); OMK_OPAQUE_S(sz);
     }
-    fetch_bc(0);
+    bc.fetch(0);
     OMK_VM_DRAIN();   // (nothing of the prologue pending at the loop header: the loop's own wait counts stay exact)
     for (int l0 = 0; l0 < a.L; l0 += SCL_TB) {
       wave_lds_sync();   // the previous block's broadcast reads before the new rows
-      commit_bc();
+      bc.commit();
       wave_lds_sync();
       checkpoint(l0);
       // the rows of token k + 1 are requested in front of token k's arithmetic (the scheduling fence behind it would otherwise pin every
@@ -674,7 +747,7 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
       Rows rows = read_rows(0);
 #pragma unroll
       for (int k = 0; k < SCL_TB; k++) {
-        if (k == SCL_TB / 2) fetch_bc(l0 + SCL_TB);   // half a block ahead: 32 younger operations, inside what s_waitcnt can count
+        if (k == SCL_TB / 2) bc.fetch(l0 + SCL_TB);   // half a block ahead: 32 younger operations, inside what s_waitcnt can count
         Rows next = rows;
         if (k + 1 < SCL_TB) next = read_rows(k + 1);
         const float y = token(raw_to_f32<T>(pu[k]), raw_to_f32<T>(pd[k]), raw_to_f32<T>(pz[k]), rows, l0 + k < a.L);
@@ -712,7 +785,7 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
       }
     };
     fetch_tiles(0);
-    fetch_bc(0);
+    bc.fetch(0);
     for (int l0 = 0; l0 < a.L; l0 += SCL_TB) {
       const int nl = (a.L - l0) < SCL_TB ? (a.L - l0) : SCL_TB;
       wave_lds_sync();
@@ -722,9 +795,9 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
         td[tlo + 4 * k] = raw_to_f32<T>(pd[k]);
         if (hasz) tz[tlo + 4 * k] = raw_to_f32<T>(pz[k]);
       }
-      commit_bc();
+      bc.commit();
       fetch_tiles(l0 + SCL_TB);
-      fetch_bc(l0 + SCL_TB);
+      bc.fetch(l0 + SCL_TB);
       wave_lds_sync();
       checkpoint(l0);
       if (nl == SCL_TB) {   // a full block as one straight run of 16 tokens (the tile reads of a token overlap its neighbours' arithmetic)
@@ -786,35 +859,6 @@ __global__ __launch_bounds__(64) void selscan_fwd_lanes_kernel(SsArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 constexpr int SSR_LC = 8, SSR_TP = 64 * SSR_LC;
 
-__device__ __forceinline__ void wave_scan_affine_rev(float& p, float& x) {
-  // suffix composition: lane j <- pairs of lanes j .. 63, the pair of the LOWER lane applied last
-#ifdef OMK_EMU
-  for (int off = 1; off < 64; off <<= 1) {
-    const float ps = shfl_down(p, off), xs = shfl_down(x, off);
-    if (lane_id() + off < 64) { x = fmaf(p, xs, x); p = p * ps; }
-  }
-#else
-  // (steps as in wave_scan_affine: the DPP modifier on the fmac / mul themselves, lanes without a source are not written)
-#define OMK_AFF_STEP(ctrl) \
-  "v_fmac_f32_dpp %0, %0, %1 " ctrl "\n\tv_mul_f32_dpp %1, %1, %1 " ctrl "\n\ts_nop 0\n\t"
-  asm volatile("s_nop 1\n\t"
-               OMK_AFF_STEP("row_shl:1 row_mask:0xf bank_mask:0xf")
-               OMK_AFF_STEP("row_shl:2 row_mask:0xf bank_mask:0xf")
-               OMK_AFF_STEP("row_shl:4 row_mask:0xf bank_mask:0xf")
-               OMK_AFF_STEP("row_shl:8 row_mask:0xf bank_mask:0xf")
-               : "+v"(x), "+v"(p));
-#undef OMK_AFF_STEP
-  // lanes 16 / 32 / 48 hold the totals of rows 1 / 2 / 3; row r still needs rows r + 1 .. 3
-  const float p1 = wave_read_lane(p, 16), x1 = wave_read_lane(x, 16), p2 = wave_read_lane(p, 32), x2 = wave_read_lane(x, 32);
-  const float p3 = wave_read_lane(p, 48), x3 = wave_read_lane(x, 48);
-  const float p23 = p2 * p3, x23 = fmaf(p2, x3, x2), p123 = p1 * p23, x123 = fmaf(p1, x23, x1);
-  const int row = lane_id() >> 4;
-  const float ps = row == 0 ? p123 : row == 1 ? p23 : row == 2 ? p3 : 1.f;
-  const float xs = row == 0 ? x123 : row == 1 ? x23 : row == 2 ? x3 : 0.f;
-  x = fmaf(p, xs, x); p = p * ps;
-#endif
-}
-
 constexpr int SSB_TL = 16, SSB_DT = 64, SSB_N = 16;
 
 struct SsBwdArgs {
@@ -844,6 +888,8 @@ __global__ __launch_bounds__(SSB_DT) void selscan_bwd_kernel(SsBwdArgs q) {
   T* sdu = sg + TL * DT;
   T* sdd = sdu + TL * DT;
   T* sdz = sdd + TL * DT;
+  // (the decode of ss_tile, the channel loads and the staging stay spelled out: this kernel's sums are written without fmaf, which
+  // products the compiler fuses depends on how the code around them is split, and another choice moves ddelta and dz by an ulp)
   const int dpg = a.Dm / a.G;
   const int tiles_per_group = (dpg + DT - 1) / DT;
   const int tg = blockIdx.x % tiles_per_group, g = (blockIdx.x / tiles_per_group) % a.G, b = blockIdx.x / (tiles_per_group * a.G);
@@ -979,7 +1025,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, NW = blockDim.x >> 6;
   const int NS = nOct > 1 ? 16 : 64;                            // stride over n of the per-(tile, wave) arrays (nOct > 1 only with N <= 16)
   float* sAcc = (float*)smem;                                   // [2][NB][TP]: dB rows, dC rows of the pass
-  T* sBC = (T*)(sAcc + (size_t)2 * NB * TP);                    // [2][NB][TP]: B rows, C rows (16-byte piece v of lane j at slot v * 64 + j)
+  T* sBC = (T*)(sAcc + (size_t)2 * NB * TP);                    // [2][NB][TP]: B rows, C rows (the LDS image of ssc_slot)
   float* sA2 = (float*)(sBC + (size_t)2 * NB * TP);             // per (tile, wave, n): A log2 e
   float* sG = sA2 + nOct * NW * NS;                             //                      adjoint carry between passes
   float* sdA = sG + nOct * NW * NS;                             //                      dA sum
@@ -1008,17 +1054,9 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
       const int nbn = a.N - nb0 < NB ? a.N - nb0 : NB;
       // ---- B / C rows of this block of state indices (the accumulators are zero: start of the kernel or the flush below)
       for (int i = threadIdx.x; i < 2 * nbn * PPR; i += blockDim.x) {
-        const int r = i / PPR, pc = i % PPR, k = r / nbn, nl = r % nbn;
+        const int r = i / PPR, k = r / nbn, nl = r % nbn;
         const T* row = k == 0 ? Bbase + (int64_t)(nb0 + nl) * a.Bsn : Cbase + (int64_t)(nb0 + nl) * a.Csn;
-        const int e0 = pc * VEC, tq = tile0 + e0;
-        T* dst = sBC + ((size_t)k * NB + nl) * TP + ((e0 % LC) / VEC * 64 + e0 / LC) * VEC;
-        const T* src = row + tq;
-        if (tq + VEC <= a.L && (((uintptr_t)src) & 15) == 0) {
-          *reinterpret_cast<vec_t<T, VEC>*>(dst) = *reinterpret_cast<const vec_t<T, VEC>*>(src);
-        } else {
-#pragma unroll
-          for (int e = 0; e < VEC; e++) dst[e] = tq + e < a.L ? src[e] : T{};
-        }
+        ssc_stage_piece<T, LC>(row, i % PPR, tile0, a.L, sBC + ((size_t)k * NB + nl) * TP);
       }
       block_sync();   // rows staged, accumulators zeroed
 #pragma unroll 1
@@ -1039,25 +1077,18 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
             float zv[LC];
             ssc_load_row<T, LC>(zrow, t0, a.L, zv);
 #pragma unroll
-            for (int i = 0; i < LC; i++) dy[i] *= zv[i] * rcp_fast(1.f + exp2_fast(-zv[i] * LOG2E));
+            for (int i = 0; i < LC; i++) dy[i] *= silu_fast(zv[i]);
           }
+          ssc_delta_chunk<LC>(dl, u, dlu, db, a.softplus, t0, a.L);   // (tokens past the end: dy = 0 too -- identity pairs in both directions)
 #pragma unroll
-          for (int i = 0; i < LC; i++) {
-            float v = dl[i] + db;
-            if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
-            dl[i] = (t0 + i < a.L) ? v : 0.f;     // tokens past the end: a = 1, b = 0, dy = 0 (identity pairs in both directions)
-            dlu[i] = dl[i] * u[i];
-            gB[i] = 0.f; ddl[i] = 0.f; ypre[i] = 0.f;
-          }
+          for (int i = 0; i < LC; i++) { gB[i] = 0.f; ddl[i] = 0.f; ypre[i] = 0.f; }
           // the state in front of this pass, one n per lane
           if (lane < a.N) sH[wv * 64 + lane] = a.ckpt[(((int64_t)b * a.Dm + d) * a.nTB + pass) * a.N + lane];
         }
-        float sdl = 0.f;
-#pragma unroll
-        for (int i = 0; i < LC; i++) sdl += dl[i];
-        const T* pB = sBC + lane * VEC;
+        const float sdl = ssc_delta_sum<LC>(dl);
+        const T* pB = sBC + ssc_slot<T>(0, lane);
         const T* pC = pB + (size_t)NB * TP;
-        float* aB = sAcc + lane * 4;
+        float* aB = sAcc + ssc_slot<float>(0, lane);
         float* aC = aB + (size_t)NB * TP;
         // dB / dC rows are sums over the channels (= waves) of the workgroup.  LDS float atomics run at a few cycles per LANE on this
         // chip (measured: 16 ds_add_f32 per wave and state index made the kernel 5x slower), so the waves walk the state indices in
@@ -1071,14 +1102,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
             const int n = nb0 + nl;
             const float A2 = sA2[ixb + n], An = A2 * LN2;
             float Bv[LC], Cv[LC];
-#pragma unroll
-            for (int v = 0; v < LC / VEC; v++) {
-              float wb[VEC], wc[VEC];
-              load_vec<T, VEC>(pB + (size_t)nl * TP + v * 64 * VEC, wb);
-              load_vec<T, VEC>(pC + (size_t)nl * TP + v * 64 * VEC, wc);
-#pragma unroll
-              for (int e = 0; e < VEC; e++) { Bv[v * VEC + e] = wb[e]; Cv[v * VEC + e] = wc[e]; }
-            }
+            ssc_read_rows<T, LC>(pB + (size_t)nl * TP, pC + (size_t)nl * TP, Bv, Cv);
             // ---- forward: x_{t-1} of every token of the lane's chunk
             float av[LC], hp[LC];
             const float Pc = exp2_fast(sdl * A2);
@@ -1088,11 +1112,8 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
               av[i] = exp2_fast(dl[i] * A2);
               X = fmaf(av[i], X, dlu[i] * Bv[i]);
             }
-            wave_scan_affine(P, X);
-            const float cin = sH[wv * 64 + n];
-            const float xend = fmaf(P, cin, X);
-            float x = shfl_up(xend, 1);
-            if (lane == 0) x = cin;
+            float xend;
+            float x = ssc_chunk_start(P, X, &sH[wv * 64 + n], lane, xend);
             {
               float* rc = aC + (size_t)nl * TP;
               f32x4 c0 = *(const f32x4*)rc, c1 = *(const f32x4*)(rc + 256);
@@ -1158,7 +1179,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
             ssc_load_row<T, LC>(zrow, t0, a.L, zv);
 #pragma unroll
             for (int i = 0; i < LC; i++) {
-              const float sig = rcp_fast(1.f + exp2_fast(-zv[i] * LOG2E));
+              const float sig = sigmoid_fast(zv[i]);
               go[i] = go[i] * fmaf(Dv, u[i], ypre[i]) * sig * (1.f + zv[i] * (1.f - sig));
             }
             ssc_store_row<T, LC>((T*)q.dz + (int64_t)b * q.dzsb + (int64_t)d * q.dzsd, t0, a.L, go);
@@ -1184,7 +1205,7 @@ __global__ __launch_bounds__(1024) void selscan_bwd_chunked_kernel(SsBwdArgs q) 
       // ---- the block's dB / dC rows -> HBM; the thread that reads a slot zeroes it for the next block
       for (int i = threadIdx.x; i < 2 * nbn * TP; i += blockDim.x) {
         const int r = i / TP, t = i % TP, k = r / nbn, nl = r % nbn;
-        float* slot = sAcc + ((size_t)k * NB + nl) * TP + ((t % LC) / 4 * 64 + t / LC) * 4 + t % 4;
+        float* slot = sAcc + ((size_t)k * NB + nl) * TP + ssc_slot<float>((t % LC) / 4, t / LC) + t % 4;
         const float v = *slot;
         *slot = 0.f;
         if (tile0 + t < a.L) {
@@ -1241,12 +1262,9 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
   constexpr uint32_t ES = sizeof(T);
   constexpr float LN2 = 0.6931471805599453f;
   const int lane = threadIdx.x;
-  const int dpg = a.Dm / a.G, tpg = (dpg + 63) / 64;
-  const int tg = blockIdx.x % tpg, g = (blockIdx.x / tpg) % a.G, b = blockIdx.x / (tpg * a.G);
-  const int d0 = g * dpg + tg * 64;
-  const int nd = (dpg - tg * 64) < 64 ? (dpg - tg * 64) : 64;
-  const bool live = lane < nd;
-  const int d = d0 + (live ? lane : 0);
+  const SsTile ct = ss_tile(a, 64);
+  const int g = ct.g, b = ct.b, d0 = ct.d0, d = ct.d;
+  const bool live = ct.live;
   float A2[16], G[16], dAa[16];
 #pragma unroll
   for (int n = 0; n < 16; n++) {
@@ -1262,31 +1280,17 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
   const BufRes Gr = make_buf((const T*)q.dout + (int64_t)b * q.gsb, q.xg);
   const BufRes DUr = make_buf((T*)q.du + (int64_t)b * q.dusb, q.xdu), DDr = make_buf((T*)q.ddelta + (int64_t)b * q.ddsb, q.xdd);
   const BufRes DZr = make_buf(hasz ? (T*)q.dz + (int64_t)b * q.dzsb : nullptr, hasz ? q.xdz : 0u);
-  const BufRes Br = make_buf((const T*)a.Bm + (int64_t)b * a.Bsb + (int64_t)g * a.Bsg, a.xB);
-  const BufRes Cr = make_buf((const T*)a.Cm + (int64_t)b * a.Csb + (int64_t)g * a.Csg, a.xC);
   const uint32_t lch = (uint32_t)(d0 + lane);
   const uint32_t uvo = live ? ES * lch * (uint32_t)a.usd : SCL_OOR, dvo = live ? ES * lch * (uint32_t)a.dsd : SCL_OOR;
   const uint32_t zvo = (live && hasz) ? ES * lch * (uint32_t)a.zsd : SCL_OOR, gvo = live ? ES * lch * (uint32_t)q.gsd : SCL_OOR;
   const uint32_t duvo = live ? ES * lch * (uint32_t)q.dusd : SCL_OOR, ddvo = live ? ES * lch * (uint32_t)q.ddsd : SCL_OOR;
   const uint32_t dzvo = (live && hasz) ? ES * lch * (uint32_t)q.dzsd : SCL_OOR;
-  // B / C rows of a tile: 16 tokens x 16 states = four elements per lane and array (the forward's scheme)
-  const int r4 = lane >> 4, t16 = lane & 15;
-  const bool bl = a.Bsl == 1, cl = a.Csl == 1;
-  const uint32_t bvo = ES * (bl ? (uint32_t)r4 * (uint32_t)a.Bsn + (uint32_t)t16 * (uint32_t)a.Bsl : (uint32_t)t16 * (uint32_t)a.Bsn + (uint32_t)r4 * (uint32_t)a.Bsl);
-  const uint32_t cvo = ES * (cl ? (uint32_t)r4 * (uint32_t)a.Csn + (uint32_t)t16 * (uint32_t)a.Csl : (uint32_t)t16 * (uint32_t)a.Csn + (uint32_t)r4 * (uint32_t)a.Csl);
-  const uint32_t bks = ES * 4u * (uint32_t)(bl ? a.Bsn : a.Bsl), cks = ES * 4u * (uint32_t)(cl ? a.Csn : a.Csl);
-  const int blo = bl ? t16 * SCL_SB + r4 : r4 * SCL_SB + t16, bls = bl ? 4 : 4 * SCL_SB;
-  const int clo = cl ? t16 * SCL_SB + r4 : r4 * SCL_SB + t16, cls = cl ? 4 : 4 * SCL_SB;
+  SclBC<T> bc(a, b, g, lane, sB, sC);   // B / C rows of a tile of 16 tokens
   float* dBb = q.dB + (int64_t)b * q.dBsb + (int64_t)g * q.dBsg;
   float* dCb = q.dC + (int64_t)b * q.dCsb + (int64_t)g * q.dCsg;
   const int nT = (a.L + SBL_T - 1) / SBL_T;
 
   const uint32_t usl_ = ES * (uint32_t)a.usl, dsl_ = ES * (uint32_t)a.dsl, zsl_ = hasz ? ES * (uint32_t)a.zsl : 0u, gsl_ = ES * (uint32_t)q.gsl;
-  auto softplus_of = [&](uint32_t raw, int t) -> float {   // delta of token t (zero behind the end of the sequence: the identity step)
-    float v = raw_to_f32<T>(raw) + db;
-    if (a.softplus) v = v > 20.f ? v : softplus_fast(v);
-    return t < a.L ? v : 0.f;
-  };
   // The token loops are REAL loops (one token per iteration, the 16 states unrolled inside): unrolled over a sub-tile the compiler kept the
   // rows and inputs of all eight tokens alive at once -- 512 registers + 378 spilled, 6.6 k cycles per token.  A token's inputs are
   // requested one iteration ahead (they hit L2: the tile's rows were touched by the sweep before).
@@ -1297,7 +1301,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
     constexpr bool PARK = decltype(park_c)::value;
     auto step = [&](int k, uint32_t cu) OMK_ALWAYS_INLINE_LAMBDA {
       const float dlt = sDl[(k0 + k) * 64 + lane], du_ = dlt * raw_to_f32<T>(cu);
-      const f32x4* rb = reinterpret_cast<const f32x4*>(&sB[(k0 + k) * SCL_SB]);
+      const f32x4* rb = bc.brow(k0 + k);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const f32x4 b4 = rb[j];
@@ -1337,8 +1341,8 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
       float sbg = 0.f, sgap = 0.f, ych = 0.f;
       float red[32];
       const float dlu = dlt * u_;
-      const f32x4* rb = reinterpret_cast<const f32x4*>(&sB[k * SCL_SB]);
-      const f32x4* rc = reinterpret_cast<const f32x4*>(&sC[k * SCL_SB]);
+      const f32x4* rb = bc.brow(k);
+      const f32x4* rc = bc.crow(k);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const f32x4 pv = sP[(kk * 4 + j) * 64 + lane], b4 = rb[j], c4 = rc[j];
@@ -1403,15 +1407,7 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
   for (int ti = nT - 1; ti >= 0; ti--) {
     const int l0 = ti * SBL_T;
     // ---- B / C rows of the tile into the wave-private LDS tile, the checkpoint in front of the tile
-    uint32_t pb[4], pc[4];
-    {
-      const uint32_t sb0 = ES * (uint32_t)l0 * (uint32_t)a.Bsl, sc0 = ES * (uint32_t)l0 * (uint32_t)a.Csl;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        pb[k] = buf_ld_raw<T>(Br, bvo, sb0 + (uint32_t)k * bks);
-        pc[k] = buf_ld_raw<T>(Cr, cvo, sc0 + (uint32_t)k * cks);
-      }
-    }
+    bc.fetch(l0);
     float hs[16], h[16];
     {
       const float* cp = a.ckpt + (((int64_t)b * a.nTB + ti) * a.N) * a.Dm + d;
@@ -1424,14 +1420,9 @@ __global__ __launch_bounds__(64) void selscan_bwd_lanes_kernel(SsBwdArgs q) {
 #pragma unroll
     for (int k = 0; k < SBL_T; k++) rdl[k] = buf_ld_raw<T>(Dr, dvo, dsl_ * (uint32_t)(l0 + k));
     wave_lds_sync();   // the previous tile's broadcast reads before the new rows
+    bc.commit();
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const bool okb = (bl ? r4 + 4 * k : t16) < a.N, okc = (cl ? r4 + 4 * k : t16) < a.N;
-      sB[blo + k * bls] = okb ? raw_to_f32<T>(pb[k]) : 0.f;
-      sC[clo + k * cls] = okc ? raw_to_f32<T>(pc[k]) : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < SBL_T; k++) sDl[k * 64 + lane] = softplus_of(rdl[k], l0 + k);
+    for (int k = 0; k < SBL_T; k++) sDl[k * 64 + lane] = ss_delta(raw_to_f32<T>(rdl[k]), db, a.softplus, l0 + k < a.L);
     wave_lds_sync();
     // second sub-tile first: the first one's forward steps lead to its start state
 #pragma unroll
