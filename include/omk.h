@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 15
+#define OMK_ABI_VERSION 16
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
@@ -508,7 +508,21 @@ int omk_sample(const OmkSample* p, omk_stream stream);
  * [0, vocab) is skipped, history_lens[b] is clamped to [0, history_cap].  A non-positive or NaN temperature counts as 1, a non-positive
  * penalty as 1, min_p applies with top_k == 0 only.  active[b] == 0 (optional; the padding rows of a bucket): the row writes nothing and
  * none of its settings has any effect (they may hold anything; its history and penalty are not read).  Its entries are still loaded: every
- * required array holds `batch` valid entries, inactive rows included.  OMK_EUNSUPPORTED: a history with a vocabulary too large for the kernel's id map (penalise a copy instead). */
+ * required array holds `batch` valid entries, inactive rows included.  OMK_EUNSUPPORTED: a history with a vocabulary too large for the kernel's id map (penalise a copy instead).
+ * ---- ABI 16: per-row logit edits (logit_bias, banned ids, allowed token sets), fused into the same launch as a third instantiation -------
+ * Row b carries a list of edit_lens[b] entries (edit_ids[b][j], edit_vals[b][j]) and a mode edit_mode[b].  Every branch sees, in every one
+ * of its passes, the row e instead of the raw row x (T the dtype of the logits):
+ *   p_i = the repetition-penalised x_i, rounded to T, as above (x_i when token i is not in the history or the penalty is off)
+ *   i listed:      e_i = round_T(float(p_i) + edit_vals[b][j]), j the LOWEST entry index with edit_ids[b][j] == i (the first entry wins)
+ *   i not listed:  e_i = -inf when edit_mode[b] == 1 (allow-only: the list is the set of tokens that may be drawn), p_i otherwise
+ * `logits` is never written.  Nothing in the arrays is trusted, the kernel defines it: edit_lens[b] is clamped to [0, edit_cap]; an id
+ * outside [0, vocab) is skipped; an edit_mode other than 1 counts as 0; an allow-only row whose list holds no valid id is unconstrained
+ * (mode 0 with an empty list).  A value of -inf bans the token.  A value of +inf or NaN, and a row left without a finite logit, give an
+ * unspecified id in [0, vocab) in bounded time.  Inactive rows read none of it.  Absent edit_ids, or edit_cap == 0: the launch is the ABI
+ * 14 launch, instruction for instruction.  edit_ids without edit_vals or edit_lens: OMK_EINVAL.  OMK_EUNSUPPORTED: edit_cap above 512, or
+ * edits with a vocabulary too large for the id map (65 536 tokens) -- edit a copy instead.  LDS of a workgroup: 44 792 B static, the id
+ * map (vocab rounded up to 16 B: bit 0 of a byte = the token is in the history, bit 1 = it is listed, bits 2 - 7 = entry index / 8 of the
+ * first entry that lists it), 8 B per entry of edit_cap rounded up to 8, one word: at most 114 436 B of the 163 840 B of a workgroup.      */
 typedef struct {
   OmkTensor logits;          /* (batch, vocab) f32 / bf16 / f16, unit last stride; read only */
   OmkTensor out_ids;         /* out (batch) int64, dense (dtype field ignored) */
@@ -524,8 +538,20 @@ typedef struct {
   const void* active;        /* optional device int32 (batch); NULL = every row */
   int64_t history_stride;    /* elements between the rows of history */
   int64_t history_cap;       /* width of history */
+  const void* edit_ids;      /* ABI 16, optional: device int64 (batch, edit_cap), row b at edit_ids + b * edit_stride */
+  const void* edit_vals;     /* ABI 16: device f32, the layout of edit_ids; required with edit_ids */
+  const void* edit_lens;     /* ABI 16: device int32 (batch); required with edit_ids */
+  const void* edit_mode;     /* ABI 16, optional: device int32 (batch), 1 = allow-only; NULL = 0 everywhere */
+  int64_t edit_stride;       /* ABI 16: elements between the rows of edit_ids and of edit_vals */
+  int64_t edit_cap;          /* ABI 16: width of edit_ids and edit_vals, at most 512; 0 = no edits */
 } OmkSampleRows;
 int omk_sample_rows(const OmkSampleRows* p, omk_stream stream);
+/* Which launch omk_sample_rows takes for *p, decided by the code that launches (nothing is launched here): OMK_SAMPLE_ROWS_*, or the
+ * negative omk_status the call would be refused with (omk_last_error says why). */
+#define OMK_SAMPLE_ROWS_PLAIN 0   /* no id map: no penalty with a history, no edits */
+#define OMK_SAMPLE_ROWS_PENALTY 1 /* the id map of the histories (ABI 14) */
+#define OMK_SAMPLE_ROWS_EDIT 2    /* the id map and the rows' edit lists (ABI 16) */
+int omk_sample_rows_form(const OmkSampleRows* p);
 
 /* ---- ABI 15: log-probabilities of the tokens a decode step sampled, the top_n most likely tokens of every row and the sampled token's rank ----
  * One launch, one workgroup per row, a launch of its own behind the sampler (the sampler kernels are not touched); nothing is read from

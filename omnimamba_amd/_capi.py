@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 15
+OMK_ABI_VERSION = 16
 OMK_MAX_DIMS = 5
 OMK_EUNSUPPORTED = -4   # omk_status: the kernel does not take this call (the caller may have another way)
 NL_FORM_GENERIC, NL_FORM_FAST, NL_FORM_BATCHED, NL_FORM_MATRIX = 0, 1, 2, 3   # omk_norm_linear_form (ABI 12)
@@ -99,7 +99,9 @@ Sample = _S("OmkSample", [("logits", _t), ("out_ids", _t), ("step_counter", C.c_
 # ABI 14: one set of settings per row, all of them device arrays (include/omk.h)
 SampleRows = _S("OmkSampleRows", [("logits", _t), ("out_ids", _t)]
                 + [(n, C.c_void_p) for n in ("top_k", "top_p", "temperature", "min_p", "seeds", "steps", "penalty", "history", "history_lens", "active")]
-                + [("history_stride", _i64), ("history_cap", _i64)])
+                + [("history_stride", _i64), ("history_cap", _i64)]
+                + [(n, C.c_void_p) for n in ("edit_ids", "edit_vals", "edit_lens", "edit_mode")] + [("edit_stride", _i64), ("edit_cap", _i64)])   # ABI 16: per-row logit edits
+SAMPLE_ROWS_PLAIN, SAMPLE_ROWS_PENALTY, SAMPLE_ROWS_EDIT = 0, 1, 2   # omk_sample_rows_form (ABI 16)
 # ABI 15: log-probabilities of the sampled tokens, the top_n tokens of every row, the sampled token's rank (include/omk.h)
 TokenLogprobs = _S("OmkTokenLogprobs", [(n, _t) for n in ("logits", "logprob", "rank", "top_ids", "top_logprobs")]
                    + [("ids", C.c_void_p), ("active", C.c_void_p), ("top_n", _i)])
@@ -116,7 +118,7 @@ SYMBOLS = [
     "omk_selective_state_update", "omk_selective_state_extend", "omk_norm_linear", "omk_norm_linear_form", "omk_lora_add", "omk_lora_up_bwd",
     "omk_selective_scan_fwd", "omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_selective_scan_bwd_workspace_bytes", "omk_selective_scan_bwd",
     "omk_ssd_scan_fwd_workspace_bytes", "omk_ssd_scan_fwd_window_states_bytes", "omk_ssd_scan_fwd", "omk_ssd_scan_bwd_workspace_bytes", "omk_ssd_scan_bwd",
-    "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample", "omk_sample_rows", "omk_token_logprobs",
+    "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample", "omk_sample_rows", "omk_sample_rows_form", "omk_token_logprobs",
 ]
 
 
@@ -133,7 +135,7 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if s.endswith("_workspace_bytes") or s.endswith("_window_states_bytes"):
             fn.restype = C.c_size_t
             fn.argtypes = [C.c_void_p]
-        elif s in ("omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_norm_linear_form"):
+        elif s in ("omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_norm_linear_form", "omk_sample_rows_form"):
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p]
         elif s == "omk_lora_up_bwd_parts":

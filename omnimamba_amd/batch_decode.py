@@ -32,7 +32,7 @@ import torch
 from . import generation as G
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
 from . import sampling as _sampling
-from .sampling import SamplingParams, TokenLogprobs, pack_rows, sample_rows
+from .sampling import SamplingParams, TokenLogprobs, edit_list, has_edits, pack_edits, pack_rows, sample_rows
 
 
 @dataclass
@@ -107,16 +107,28 @@ class _Bucket:
             self.samp["out"] = torch.zeros(self.nb, dtype=torch.long, device=dev)
         return self.samp
 
+    def row_edits(self, width):
+        """Static per-row edit tensors (nb, width) of sample_rows next to the row settings: rewritten when the rows (or what is banned in
+        them) change; made anew when a call needs another width."""
+        st = self.row_settings()
+        if "edit_ids" not in st or st["edit_ids"].shape[1] != width:
+            st.update(pack_edits([SamplingParams()] * self.nb, self.input_ids.device, width=width))
+        return st
+
 
 class _RowSampler:
     """decode_ragged(sampling=...): every draw of the call through ONE row-wise launch (sampling.sample_rows), request i with
     params[i].  The n-th id request i samples is drawn at stream position params[i].step0 + n of its seed, whichever rows share the
     launch.  With a repetition penalty somewhere the pool owns a history buffer (max_batch, cap) int64: a slot's history is its request's
     input_ids followed by its sampled ids.  Its length is ids_len[i] + count[i] on the host; the device copy the kernel reads is the
-    bucket's static history_lens, advanced on the device between row changes."""
+    bucket's static history_lens, advanced on the device between row changes.  With logit edits somewhere (logit_bias, allowed or banned
+    ids, min_new_tokens) every draw carries the rows' edit lists, `width` entries wide: the longest list of the call and one entry for the
+    EOS ban of min_new_tokens, which is in a row's list while its request has sampled fewer ids than that."""
 
-    def __init__(self, c, params, requests, lens, dev):
-        self.c, self.params, self.dev = c, params, dev
+    def __init__(self, c, params, requests, lens, dev, eos=None):
+        self.c, self.params, self.dev, self.eos = c, params, dev, eos
+        self.edit = any(has_edits(p) or p.min_new_tokens > 0 for p in params)
+        self.width = 1 + max(len(edit_list(p)[0]) for p in params) if self.edit else 0
         self.count = [0] * len(params)             # ids sampled so far, per request
         self.ids_len = [r[0].shape[1] for r in requests]
         self.requests = requests
@@ -138,9 +150,18 @@ class _RowSampler:
         w = max(1, max(self.ids_len[i] + self.count[i] for i in reqs))
         return self.hist[:, :w].index_select(0, rows)
 
+    def _bans(self, reqs):
+        """Per request of `reqs`: the ids banned on top of its own settings in its next draw -- EOS until it has sampled min_new_tokens ids."""
+        return [[self.eos] if self.count[i] < self.params[i].min_new_tokens else [] for i in reqs]
+
+    def _edits(self, reqs):
+        return pack_edits([self.params[i] for i in reqs], self.dev, self._bans(reqs), width=self.width)
+
     def admit(self, reqs, slots, logits):
         """The first id of the requests `reqs` (just admitted into `slots`) from their prefill / extend logits (len(reqs), vocab)."""
         pk = self._settings(reqs)
+        if self.edit:
+            pk.update(self._edits(reqs))
         if self.pen:
             rows = torch.tensor(slots, dtype=torch.long).to(self.dev, non_blocking=True)
             for i, s in zip(reqs, slots):
@@ -160,9 +181,14 @@ class _RowSampler:
         """One id for every live row of bucket `bk` from the step's logits (bk.nb, vocab); rows: the slots of the bucket's rows (device)."""
         st, nl = bk.row_settings(), len(live)
         key = (bk.nb, tuple(i for i, _, _ in live))
+        if self.edit:
+            st = bk.row_edits(self.width)
+            key += (tuple(bool(b) for b in self._bans([i for i, _, _ in live])),)
         if key != self.prev:
             reqs = [i for i, _, _ in live]
             pk = self._settings(reqs)
+            if self.edit:
+                pk.update(self._edits(reqs))
             for k, v in pk.items():
                 st[k][:nl].copy_(v)
             st["active"].copy_(torch.tensor([1] * nl + [0] * (bk.nb - nl), dtype=torch.int32), non_blocking=True)
@@ -171,6 +197,8 @@ class _RowSampler:
                                          non_blocking=True)
             self.prev = key
         kw = {k: st[k] for k in ("top_k", "top_p", "temperature", "min_p", "seeds", "steps", "active", "out")}
+        if self.edit:
+            kw.update({k: st[k] for k in ("edit_ids", "edit_vals", "edit_lens", "edit_mode")})
         if self.pen:
             toks = sample_rows(logits, **kw, penalty=st["penalty"], history=self._rows_history(rows, [i for i, _, _ in live]),
                                history_lens=st["history_lens"])[:nl]
@@ -394,6 +422,11 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     position step0 + n of its seed, so its ids do not depend on which requests share its steps, on max_batch or on the admission
     order.  Every draw (prefill, extend, grouped or not, and the step) is one row-wise launch (sampling.sample_rows); top_k, top_p,
     min_p and temperature are not read.  A follow-up turn continues its stream when it is given step0 = the ids drawn so far.
+    Constraints (SamplingParams.logit_bias, allowed_token_ids, banned_token_ids, min_new_tokens): when a request of the call has any, every
+    draw of the call carries the rows' edit lists and the row-wise launch applies them behind the repetition penalty (sampling.sample_rows,
+    omk_sample_rows ABI 16); the lists live in static per-bucket tensors that are rewritten only when the rows change.  min_new_tokens bans
+    eos_token_id (required then) until the request has sampled that many ids in this call; the rows are repacked on the step where the ban
+    ends.  The requests without constraints draw the ids they draw without constrained neighbours; logprobs stay those of the raw logits.
 
     logprobs: None -- off.  An int N in [0, 64] for every request, or a list with one entry per request (an int, or None for a request
     that wants no record): the call returns ONE MORE element behind what it returns otherwise (ids_list, logprobs_list) or (ids_list,
@@ -435,6 +468,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
         sampling = [sampling] * n if isinstance(sampling, SamplingParams) else list(sampling)
         if len(sampling) != n or not all(isinstance(p, SamplingParams) for p in sampling):
             raise ValueError(f"decode_ragged: sampling is one SamplingParams or a list of {n}, one per request")
+        if eos_token_id is None and any(p.min_new_tokens > 0 for p in sampling):
+            raise ValueError("decode_ragged: min_new_tokens > 0 needs an eos_token_id to keep out of the first ids")
     dev = requests[0][1].device
     if hasattr(model, "prepare_decode"):
         model.prepare_decode(task)
@@ -448,7 +483,7 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             c["buckets"][nb] = _Bucket(model, c["pool"], nb, c["max_seqlen"], task, cg, c["mempool"])
         return c["buckets"][nb]
 
-    rs = None if sampling is None else _RowSampler(c, sampling, requests, lens, dev)
+    rs = None if sampling is None else _RowSampler(c, sampling, requests, lens, dev, eos_token_id)
     # the first id(s) of the requests `reqs` admitted into `slots`, from their prefill / extend logits
     draw = lambda lg, reqs, slots: (sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature) if rs is None
                                     else rs.admit(reqs, slots, lg))

@@ -82,7 +82,7 @@ __device__ __forceinline__ T block_incl_scan(T v, T* buf, int tid) {
 struct RowCfg {
   int top_k; float top_p, inv_temp, min_p;
   unsigned long long seed, step; uint32_t c0;
-  float pen;   // PEN only: what the logits marked in the id map are multiplied with (negative ones) / divided by
+  float pen;   // SM_PEN / SM_EDIT only: what the logits marked in the id map are multiplied with (negative ones) / divided by
   int64_t* out;   // where the row's id goes
   __device__ __forceinline__ void philox_counter(uint32_t (&cc)[4]) const {
     cc[0] = c0; cc[1] = (uint32_t)step; cc[2] = (uint32_t)(step >> 32); cc[3] = 0u;
@@ -104,11 +104,52 @@ struct BatchCfg {
   __device__ __forceinline__ void put(int64_t id) const { out[row] = id; }
 };
 
-// One row of logits -> one id, by the whole workgroup: the one implementation behind omk_sample and omk_sample_rows.  PEN: `pmap` (LDS, one
-// byte per token) marks the ids of the row's history; the loader penalises a marked logit and rounds it to T as the in-place torch version
-// does, so every pass sees the same penalised row.  ALIASED picks the layout of the large LDS buffers, Cfg is RowCfg or BatchCfg.
-template <class T, bool PEN, bool ALIASED, class Cfg>
-__device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg a, const unsigned char* pmap) {
+// What the row loader consults besides the row itself: nothing, the id map of the history, or the id map and the row's edit list.
+constexpr int SM_NONE = 0, SM_PEN = 1, SM_EDIT = 2;
+// A byte of the id map.  Bit 0: the token is in the row's history.  SM_EDIT only -- bit 1: the token is in the row's edit list; bits 2 - 7:
+// the BUCKET (entry index / EDIT_BUCKET) of the first entry that names it.  The loader reads the EDIT_BUCKET entries of that bucket and
+// takes the first match: the first entry wins, in 8 LDS reads whatever the length of the list.  (Scanning the whole list instead, as first
+// written, was a chain of dependent LDS reads per listed token and pass: +43 us a launch at 16 entries, 7 ms at 512 --
+// profiles/sample_rows_edits.txt section 3.)
+constexpr unsigned MAP_HIST = 1u, MAP_EDIT = 2u;
+constexpr int EDIT_BUCKET = 8;
+// SM_EDIT: the row's edit list as the preamble of sample_rows_kernel left it in LDS, whole buckets of it.  ids[j] is -1 where the entry's id
+// is outside [0, V) and behind the row's length; allow: the row is allow-only and its list holds a valid id (uniform over the workgroup).
+struct RowEdits { const int* ids; const float* vals; bool allow; };
+
+#ifdef OMK_EMU
+__device__ __forceinline__ uint32_t lds_cas_u32(uint32_t* p, uint32_t expect, uint32_t v) { const uint32_t o = *p; if (o == expect) *p = v; return o; }
+#else
+__device__ __forceinline__ uint32_t lds_cas_u32(uint32_t* p, uint32_t expect, uint32_t v) {
+  __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  return expect;
+}
+#endif
+// Mark token `id` as listed by entry j: the byte keeps the lowest bucket among the entries that name the token (entries race for a byte, and
+// a byte shares its word with three other tokens: a compare-and-swap on the word; every failure is another entry's success, so at most as
+// many rounds as the list has entries).
+__device__ __forceinline__ void map_mark_edit(unsigned char* map, int id, int j) {
+  uint32_t* const w = (uint32_t*)map + (id >> 2);
+  const int sh = 8 * (id & 3);
+  const uint32_t mine = MAP_EDIT | ((uint32_t)(j / EDIT_BUCKET) << 2);
+  uint32_t old = *w;
+  for (;;) {
+    const uint32_t ob = (old >> sh) & 0xffu;
+    if ((ob & MAP_EDIT) && (ob >> 2) <= (mine >> 2)) return;
+    const uint32_t now = (old & ~(0xffu << sh)) | (((ob & MAP_HIST) | mine) << sh);
+    const uint32_t seen = lds_cas_u32(w, old, now);
+    if (seen == old) return;
+    old = seen;
+  }
+}
+
+// One row of logits -> one id, by the whole workgroup: the one implementation behind omk_sample and omk_sample_rows.  MODE >= SM_PEN: `pmap`
+// (LDS, one byte per token) marks the ids of the row's history; the loader penalises a marked logit and rounds it to T as the in-place torch
+// version does, so every pass sees the same penalised row.  SM_EDIT: behind the penalty the loader adds the value of the first entry of `ed`
+// that names the token (one more rounding to T), and an allow-only row reads -inf for every token its list does not name.  ALIASED picks the
+// layout of the large LDS buffers, Cfg is RowCfg or BatchCfg.
+template <class T, int MODE, bool ALIASED, class Cfg>
+__device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg a, const unsigned char* pmap, const RowEdits ed = {}) {
   // hist / hm8 / hc8: the counters of the radix passes, eight copies of every counter, picked by the lane: the keys of a row share their top
   // byte(s), and 64 lanes adding to ONE LDS address are 64 serial atomics (copy c of digit d lives at 8 d + c: the copies of a digit sit in
   // different banks).  sc64 / sc32 / scf: the buffers of the block scans.  Two layouts:
@@ -142,7 +183,20 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   auto ld = [&](int i) -> float {
     float v = to_f32(rowp[i]);
-    if constexpr (PEN) { if (pmap[i]) v = to_f32(from_f32<T>(v < 0.f ? v * a.pen : v / a.pen)); }
+    if constexpr (MODE == SM_PEN) { if (pmap[i]) v = to_f32(from_f32<T>(v < 0.f ? v * a.pen : v / a.pen)); }
+    if constexpr (MODE == SM_EDIT) {
+      const unsigned m = pmap[i];
+      if (m & MAP_HIST) v = to_f32(from_f32<T>(v < 0.f ? v * a.pen : v / a.pen));
+      if (m & MAP_EDIT) {
+        // the first entry of the token's bucket that names it (there is one): from the back without an exit, so the reads do not wait for
+        // the compares
+        const int base = (int)(m >> 2) * EDIT_BUCKET;
+        int jf = base;
+#pragma unroll
+        for (int u = EDIT_BUCKET - 1; u >= 0; u--) if (ed.ids[base + u] == i) jf = base + u;
+        v = to_f32(from_f32<T>(v + ed.vals[jf]));
+      } else if (ed.allow) v = -INFINITY;
+    }
     return v;
   };
   // one pass over the row, thread-strided (coalesced), four requests in flight per lane
@@ -429,8 +483,12 @@ template <class T>
 __global__ __launch_bounds__(SNT) void sample_kernel(SampleArgs a) {
   const int row = blockIdx.x;
   const BatchCfg c = {a.top_k, a.top_p, a.inv_temp, a.min_p, a.seed, a.counter, a.offset, a.out, row};
-  sample_row<T, false, false>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, nullptr);
+  sample_row<T, SM_NONE, false>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, nullptr);
 }
+
+// SM_EDIT: bytes of the id map (the edit list behind it starts on a 16-byte boundary) and entries of the list's LDS copy (whole buckets)
+__host__ __device__ constexpr size_t edit_map_bytes(int V) { return (size_t)((V + 15) / 16) * 16; }
+__host__ __device__ constexpr int edit_lds_entries(int ecap) { return (ecap + EDIT_BUCKET - 1) / EDIT_BUCKET * EDIT_BUCKET; }
 
 struct SampleRowsArgs {
   const void* logits; int64_t ls;
@@ -439,11 +497,15 @@ struct SampleRowsArgs {
   const unsigned long long* seeds; const int64_t* steps;
   const float* penalty; const int64_t* history; const int* history_lens; const int* active;
   int64_t hs; int hcap;
+  const int64_t* edit_ids; const float* edit_vals; const int* edit_lens; const int* edit_mode;   // SM_EDIT only
+  int64_t es; int ecap;
 };
 
 // omk_sample_rows: row b's settings come from the device arrays.  Nothing in them is trusted: see the clamps (include/omk.h).
-// PEN: dynamic LDS holds the id map of the row's history, (V rounded up to 4) bytes.
-template <class T, bool PEN>
+// MODE >= SM_PEN: dynamic LDS holds the id map of the row's history, (V rounded up to 4) bytes.  SM_EDIT: the map (V rounded up to 16 bytes),
+// behind it the row's edit list in whole buckets (edit_lds_entries(ecap) ids as int32, as many values) and one word that says whether any of
+// its ids was valid.
+template <class T, int MODE>
 __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
   const int row = blockIdx.x, tid = threadIdx.x;
   // The row's entries are all requested in ONE round of scalar loads, the active flag among them: nothing of the passes over the row
@@ -463,7 +525,8 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
   c.min_p = c.top_k == 0 ? mp : 0.f;
   c.seed = sd; c.step = st; c.c0 = 0u; c.pen = 1.f; c.out = a.out + row;
   const unsigned char* pmap = nullptr;
-  if constexpr (PEN) {
+  RowEdits ed = {};
+  if constexpr (MODE == SM_PEN) {
     OMK_DYN_SMEM(dyn);
     unsigned char* const map = (unsigned char*)dyn;
     const float pen = a.penalty[row];
@@ -478,7 +541,43 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
     block_sync();
     pmap = map;
   }
-  sample_row<T, PEN, true>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, pmap);
+  if constexpr (MODE == SM_EDIT) {
+    OMK_DYN_SMEM(dyn);
+    unsigned char* const map = (unsigned char*)dyn;
+    const int ecap8 = edit_lds_entries(a.ecap);
+    int* const eids = (int*)(dyn + edit_map_bytes(a.V));
+    float* const evals = (float*)(eids + ecap8);
+    uint32_t* const any_valid = (uint32_t*)(evals + ecap8);
+    // (the penalty and the history are optional here: a launch with edits alone marks no history)
+    const float pen = a.penalty ? a.penalty[row] : 1.f;
+    int hl = a.history ? a.history_lens[row] : 0;
+    int el = a.edit_lens[row];
+    const int em = a.edit_mode ? a.edit_mode[row] : 0;
+    hl = hl < 0 ? 0 : (hl > a.hcap ? a.hcap : hl);
+    el = el < 0 ? 0 : (el > a.ecap ? a.ecap : el);
+    if (!(pen > 0.f) || pen == 1.f) hl = 0;     // off: no history mark
+    else c.pen = pen;
+    for (int i = tid; i < (a.V + 3) / 4; i += SNT) ((uint32_t*)map)[i] = 0u;
+    if (tid == 0) *any_valid = 0u;
+    block_sync();
+    const int64_t* hrow = a.history + (int64_t)row * a.hs;
+    for (int j = tid; j < hl; j += SNT) { const int64_t id = hrow[j]; if (id >= 0 && id < (int64_t)a.V) map[id] = (unsigned char)MAP_HIST; }
+    block_sync();   // (the history marks are whole-byte stores: they are done before the words of the map are swapped)
+    const int64_t* irow = a.edit_ids + (int64_t)row * a.es;
+    const float* vrow = a.edit_vals + (int64_t)row * a.es;
+    for (int j = tid; j < ecap8; j += SNT) {   // (whole buckets: the entries behind the row's length read as "no token")
+      const int64_t id = j < el ? irow[j] : -1;
+      const bool ok = id >= 0 && id < (int64_t)a.V;
+      eids[j] = ok ? (int)id : -1;
+      evals[j] = j < el ? vrow[j] : 0.f;
+      if (ok) { map_mark_edit(map, (int)id, j); *any_valid = 1u; }
+    }
+    block_sync();
+    ed.ids = eids; ed.vals = evals;
+    ed.allow = em == 1 && uniform_i((int)*any_valid) != 0;   // allow-only without a valid id: unconstrained
+    pmap = map;
+  }
+  sample_row<T, MODE, true>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, pmap, ed);
 }
 
 }  // namespace omk
@@ -510,9 +609,13 @@ extern "C" int omk_sample(const OmkSample* p, omk_stream stream) {
 // the id map of the penalty launch: one byte per token in dynamic LDS, next to the 44 KB the branches share
 constexpr int64_t SAMPLE_PEN_MAX_V = 65536;
 
-// Raise the dynamic-LDS limit of the penalty instantiation when a launch needs more than the device was already granted, not on every
-// step (the attribute belongs to a function on a device).  0 = granted.
-template <class T> static int grant_map_lds(size_t smem) {
+// the edit list of the SM_EDIT launch: 8 bytes per entry in dynamic LDS behind the id map.  44 800 B static + 65 536 B of map + 8 x 512 B + one
+// word = 114 436 B of the 163 840 B a workgroup may hold.  64 buckets: what the six bits of a map byte name.
+constexpr int64_t SAMPLE_EDIT_MAX = 64 * EDIT_BUCKET;
+
+// Raise the dynamic-LDS limit of an instantiation with an id map when a launch needs more than the device was already granted, not on
+// every step (the attribute belongs to a function on a device).  0 = granted.
+template <class T, int MODE> static int grant_map_lds(size_t smem) {
 #ifdef OMK_EMU
   return 0;
 #else
@@ -521,13 +624,23 @@ template <class T> static int grant_map_lds(size_t smem) {
   int d = -1;
   const bool known = hipGetDevice(&d) == hipSuccess && d >= 0 && d < MAXDEV;
   if (known && granted[d].load(std::memory_order_relaxed) >= smem) return 0;
-  if (OMK_SET_MAX_DYN_SMEM((sample_rows_kernel<T, true>), smem)) return 1;
+  if (OMK_SET_MAX_DYN_SMEM((sample_rows_kernel<T, MODE>), smem)) return 1;
   if (known) granted[d].store(smem, std::memory_order_relaxed);
   return 0;
 #endif
 }
 
-extern "C" int omk_sample_rows(const OmkSampleRows* p, omk_stream stream) {
+// THE selector of omk_sample_rows: every check of a call, the kernel arguments and which instantiation takes it -- omk_sample_rows launches
+// what this says, omk_sample_rows_form reports it.  Returns OMK_SAMPLE_ROWS_* or the negative omk_status of a call that is refused.
+namespace {
+struct SampleRowsPlan {
+  SampleRowsArgs a;
+  bool empty;      // no row: nothing to launch
+  size_t smem;     // dynamic LDS
+};
+}  // namespace
+
+static int sample_rows_plan(const OmkSampleRows* p, SampleRowsPlan& pl) {
   OMK_REQUIRE(p && present(p->logits) && present(p->out_ids), "sample_rows: logits and out_ids required");
   OMK_REQUIRE(p->logits.ndim == 2 && p->logits.stride[1] == 1, "sample_rows: logits must be (batch, vocab) with unit last stride");
   OMK_REQUIRE(p->out_ids.ndim == 1 && p->out_ids.shape[0] == p->logits.shape[0] && p->out_ids.stride[0] == 1, "sample_rows: out_ids must be dense int64 (batch)");
@@ -536,28 +649,62 @@ extern "C" int omk_sample_rows(const OmkSampleRows* p, omk_stream stream) {
               "sample_rows: top_k, top_p, temperature, min_p, seeds and steps are required device arrays of (batch) entries");
   OMK_REQUIRE(!p->history || p->history_lens, "sample_rows: history needs history_lens");
   OMK_REQUIRE(!p->history || (p->history_cap >= 0 && p->history_cap < (1ll << 31)), "sample_rows: history_cap");
-  if (p->logits.shape[0] == 0) return OMK_OK;
+  OMK_REQUIRE(!p->edit_ids || (p->edit_vals && p->edit_lens), "sample_rows: edit_ids needs edit_vals and edit_lens");
+  OMK_REQUIRE(!p->edit_ids || (p->edit_cap >= 0 && p->edit_cap < (1ll << 31)), "sample_rows: edit_cap");
+  pl = SampleRowsPlan{};
+  SampleRowsArgs& a = pl.a;
+  const bool pen = p->penalty && p->history && p->history_cap > 0;   // (no penalty array, or no history: nothing to penalise)
+  const bool edit = p->edit_ids && p->edit_cap > 0;                  // (no edit array, or no room in it: today's launch)
+  const int form = edit ? OMK_SAMPLE_ROWS_EDIT : (pen ? OMK_SAMPLE_ROWS_PENALTY : OMK_SAMPLE_ROWS_PLAIN);
+  if (p->logits.shape[0] == 0) { pl.empty = true; return form; }
   OMK_REQUIRE(p->logits.shape[1] > 0 && p->logits.shape[1] < (1ll << 31), "sample_rows: vocabulary size");
-  SampleRowsArgs a = {};
   a.logits = p->logits.data; a.ls = p->logits.stride[0];
   a.out = (int64_t*)p->out_ids.data; a.V = (int)p->logits.shape[1];
   a.top_k = (const int*)p->top_k; a.top_p = (const float*)p->top_p; a.temperature = (const float*)p->temperature; a.min_p = (const float*)p->min_p;
   a.seeds = (const unsigned long long*)p->seeds; a.steps = (const int64_t*)p->steps; a.active = (const int*)p->active;
-  const bool pen = p->penalty && p->history && p->history_cap > 0;   // (no penalty array, or no history: nothing to penalise)
+  if (form == OMK_SAMPLE_ROWS_PLAIN) return form;
+  if (a.V > SAMPLE_PEN_MAX_V)
+    return fail(OMK_EUNSUPPORTED, "sample_rows: the id map of the repetition penalty and the edits holds %lld tokens, the vocabulary has %d", (long long)SAMPLE_PEN_MAX_V, a.V);
+  if (pen) {
+    a.penalty = (const float*)p->penalty; a.history = (const int64_t*)p->history; a.history_lens = (const int*)p->history_lens;
+    a.hs = p->history_stride; a.hcap = (int)p->history_cap;
+  }
+  pl.smem = (size_t)((a.V + 3) / 4) * 4;
+  if (!edit) return form;
+  if (p->edit_cap > SAMPLE_EDIT_MAX)
+    return fail(OMK_EUNSUPPORTED, "sample_rows: the edit list of a row holds %lld entries, edit_cap is %lld", (long long)SAMPLE_EDIT_MAX, (long long)p->edit_cap);
+  a.edit_ids = (const int64_t*)p->edit_ids; a.edit_vals = (const float*)p->edit_vals; a.edit_lens = (const int*)p->edit_lens;
+  a.edit_mode = (const int*)p->edit_mode; a.es = p->edit_stride; a.ecap = (int)p->edit_cap;
+  pl.smem = edit_map_bytes(a.V) + (size_t)edit_lds_entries(a.ecap) * 8 + 4;
+  return form;
+}
+
+extern "C" int omk_sample_rows_form(const OmkSampleRows* p) {
+  SampleRowsPlan pl;
+  return sample_rows_plan(p, pl);
+}
+
+extern "C" int omk_sample_rows(const OmkSampleRows* p, omk_stream stream) {
+  SampleRowsPlan pl;
+  const int form = sample_rows_plan(p, pl);
+  if (form < 0) return form;
+  if (pl.empty) return OMK_OK;
+  const SampleRowsArgs& a = pl.a;
+  const size_t smem = pl.smem;
   dim3 grid((unsigned)p->logits.shape[0]), block(SNT);
   const int dt = p->logits.dtype;
-  if (!pen) {
-    OMK_DISPATCH_DTYPE(dt, T, OMK_LAUNCH((sample_rows_kernel<T, false>), grid, block, 0, stream, a));
-    return finish_launch("sample_rows");
+  if (form == OMK_SAMPLE_ROWS_PLAIN) {
+    OMK_DISPATCH_DTYPE(dt, T, OMK_LAUNCH((sample_rows_kernel<T, SM_NONE>), grid, block, 0, stream, a));
+  } else if (form == OMK_SAMPLE_ROWS_PENALTY) {
+    OMK_DISPATCH_DTYPE(dt, T, {
+      if (grant_map_lds<T, SM_PEN>(smem)) return fail(OMK_ELAUNCH, "sample_rows: cannot reserve %zu bytes of LDS for the id map", smem);
+      OMK_LAUNCH((sample_rows_kernel<T, SM_PEN>), grid, block, smem, stream, a);
+    });
+  } else {
+    OMK_DISPATCH_DTYPE(dt, T, {
+      if (grant_map_lds<T, SM_EDIT>(smem)) return fail(OMK_ELAUNCH, "sample_rows: cannot reserve %zu bytes of LDS for the id map and the edit list", smem);
+      OMK_LAUNCH((sample_rows_kernel<T, SM_EDIT>), grid, block, smem, stream, a);
+    });
   }
-  if (a.V > SAMPLE_PEN_MAX_V)
-    return fail(OMK_EUNSUPPORTED, "sample_rows: the id map of the repetition penalty holds %lld tokens, the vocabulary has %d", (long long)SAMPLE_PEN_MAX_V, a.V);
-  a.penalty = (const float*)p->penalty; a.history = (const int64_t*)p->history; a.history_lens = (const int*)p->history_lens;
-  a.hs = p->history_stride; a.hcap = (int)p->history_cap;
-  const size_t smem = (size_t)((a.V + 3) / 4) * 4;
-  OMK_DISPATCH_DTYPE(dt, T, {
-    if (grant_map_lds<T>(smem)) return fail(OMK_ELAUNCH, "sample_rows: cannot reserve %zu bytes of LDS for the id map", smem);
-    OMK_LAUNCH((sample_rows_kernel<T, true>), grid, block, smem, stream, a);
-  });
   return finish_launch("sample_rows");
 }

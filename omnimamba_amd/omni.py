@@ -215,7 +215,8 @@ class OmniMambaPath(nn.Module):
         are the suggested values for MMU prompts; DESIGN.md 4.5 says what was measured).
         sampling: one sampling.SamplingParams for every request or a list with one per request -- each request sampled with its own
         settings, repetition penalty and random stream in the shared steps (decode_ragged); temperature, top_k and
-        top_p are not read then.
+        top_p are not read then.  Its logit_bias, allowed_token_ids, banned_token_ids and min_new_tokens constrain what the request may
+        emit (yes/no, A-D, digits only; min_new_tokens needs eos_token_id), applied inside the same launch.
         logprobs: an int N in [0, 64] for every request, or a list with one entry (N or None) per request: the call returns one more
         element, per request a sampling.TokenLogprobs aligned with its sampled ids -- the log-probability and rank of each sampled id and
         the N most likely tokens of each step, of the raw logits (decode_ragged).  None: off."""
@@ -239,6 +240,7 @@ class OmniMambaPath(nn.Module):
         prefilled, so they change nothing here.  extend_batch > 1: up to that many conversations that find a free slot at the same moment
         are extended by one right-padded pass (decode_ragged; off by default, DESIGN.md 4.6 says what was measured).
         sampling: as in mmu_generate_batch; a conversation continues its random stream with step0 = the ids its earlier turns sampled.
+        Constraints (allowed or banned ids, logit_bias, min_new_tokens) hold from the turn's first id on; min_new_tokens counts this turn's ids.
         logprobs: as in mmu_generate_batch; the call then returns (ids, states, logprobs), the records covering this turn's sampled ids."""
         from .batch_decode import decode_ragged
         if len(states) != len(input_ids_list):

@@ -2,8 +2,9 @@
 (/root/reference/models/stage2/generation.py:87-121).  One launch, no host scalar after it: usable inside a captured decode step."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Mapping, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -11,6 +12,7 @@ from . import _capi as K
 from ._lib import get_lib
 
 MAX_TOP_K = 64
+MAX_EDITS = 512      # entries of one row's edit list the fused launch holds (SAMPLE_EDIT_MAX of sample.hip); longer lists edit a copy
 
 
 def applies(logits: torch.Tensor, top_k: int, min_p: float = 0.0, top_p: float = 0.0) -> bool:
@@ -50,7 +52,12 @@ def sample_device(logits: torch.Tensor, top_k: int = 1, top_p: float = 0.0, temp
 class SamplingParams:
     """How ONE request is sampled.  seed and step0 name its random stream: the n-th id the request samples is drawn at stream position
     step0 + n of seed, whatever batch it shares a step with (a follow-up turn continues its stream by passing the number of ids drawn so
-    far as step0).  The rules are omk_sample's own; repetition_penalty 1.0 means off."""
+    far as step0).  The rules are omk_sample's own; repetition_penalty 1.0 means off.
+
+    Constraints on what the request may emit (off by default; the rule is omk_sample_rows', ABI 16, applied behind the repetition penalty):
+    logit_bias -- a mapping or pairs id -> float added to the token's logit (finite, or -inf: a ban); allowed_token_ids -- only these ids
+    may be drawn; banned_token_ids -- never drawn; min_new_tokens -- the call's eos_token_id is banned until the request has sampled that
+    many ids in the call.  logit_bias is kept as a tuple of (id, value) pairs, the id sets as tuples."""
     top_k: int = 1
     top_p: float = 0.0
     min_p: float = 0.0
@@ -58,8 +65,26 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     seed: int = 0
     step0: int = 0
+    logit_bias: Union[None, Mapping[int, float], Sequence[Tuple[int, float]]] = None
+    allowed_token_ids: Optional[Sequence[int]] = None
+    banned_token_ids: Optional[Sequence[int]] = None
+    min_new_tokens: int = 0
 
     def __post_init__(self):
+        bias = self.logit_bias
+        bias = tuple((int(i), float(v)) for i, v in (bias.items() if isinstance(bias, Mapping) else (bias or ())))
+        for i, v in bias:
+            if math.isnan(v) or v == math.inf:
+                raise ValueError(f"SamplingParams: logit_bias values are finite or -inf, got {v} for id {i}")
+        object.__setattr__(self, "logit_bias", bias)
+        if self.allowed_token_ids is not None:
+            allowed = tuple(int(i) for i in self.allowed_token_ids)
+            if not allowed:
+                raise ValueError("SamplingParams: allowed_token_ids is None or a non-empty sequence of ids")
+            object.__setattr__(self, "allowed_token_ids", allowed)
+        object.__setattr__(self, "banned_token_ids", tuple(int(i) for i in (self.banned_token_ids or ())))
+        if int(self.min_new_tokens) < 0:
+            raise ValueError(f"SamplingParams: min_new_tokens must be >= 0, got {self.min_new_tokens}")
         if not 0 <= int(self.top_k) <= MAX_TOP_K:
             raise ValueError(f"SamplingParams: top_k must be in [0, {MAX_TOP_K}], got {self.top_k}")
         if not self.temperature > 0.0:
@@ -92,6 +117,81 @@ def pack_rows(params_list: Sequence[SamplingParams], device) -> dict:
     return {"top_k": k, "top_p": f[0], "temperature": f[1], "min_p": f[2], "penalty": f[3], "seeds": i[0], "steps": i[1]}
 
 
+def has_edits(p: SamplingParams) -> bool:
+    """Whether the request's own settings edit its logits (min_new_tokens aside: that is the caller's extra ban)."""
+    return bool(p.logit_bias) or p.allowed_token_ids is not None or bool(p.banned_token_ids)
+
+
+def edit_list(p: SamplingParams, extra_bans: Sequence[int] = ()) -> Tuple[list, int]:
+    """The (id, value) entries of one request's edit list and its mode, by the merge rule: extra_bans first with -inf; a banned id -inf; with an
+    allowed set the list is the allowed ids, each with its bias or 0 (banned ones -inf; a bias outside the set is dropped), mode 1; without
+    one the bias keys and the banned ids, mode 0.  Every id once: its first entry, and of a repeated bias key the first value."""
+    bias = {}
+    for i, v in p.logit_bias:
+        bias.setdefault(i, v)
+    banned = set(p.banned_token_ids) | set(extra_bans)
+    keys = list(extra_bans) + (list(p.allowed_token_ids) if p.allowed_token_ids is not None else [i for i, _ in p.logit_bias] + list(p.banned_token_ids))
+    out, seen = [], set()
+    for i in keys:
+        if i not in seen:
+            seen.add(i)
+            out.append((i, -math.inf if i in banned else bias.get(i, 0.0)))
+    return out, int(p.allowed_token_ids is not None)
+
+
+def pack_edits(params_list: Sequence[SamplingParams], device, extra_bans: Optional[Sequence[Sequence[int]]] = None, width: int = 0) -> dict:
+    """The edit tensors of sample_rows for a list of SamplingParams, row b from params_list[b] (edit_list): a dict with edit_ids (int64 (n, E)),
+    edit_vals (float32 (n, E)), edit_lens and edit_mode (int32 (n,)).  E is the longest list (at least 1, at least `width`); extra_bans[b]:
+    ids that go to the front of row b's list with -inf (an allow-only row stays allow-only: a banned id that is not in its set is -inf
+    either way)."""
+    n = len(params_list)
+    lists = [edit_list(p, () if extra_bans is None else extra_bans[b]) for b, p in enumerate(params_list)]
+    E = max([1, int(width)] + [len(l) for l, _ in lists])
+    ids = torch.zeros(n, E, dtype=torch.int64)
+    vals = torch.zeros(n, E, dtype=torch.float32)
+    for b, (l, _) in enumerate(lists):
+        if l:
+            ids[b, :len(l)] = torch.tensor([i for i, _ in l], dtype=torch.int64)
+            vals[b, :len(l)] = torch.tensor([v for _, v in l], dtype=torch.float32)
+    lens = torch.tensor([len(l) for l, _ in lists], dtype=torch.int32)
+    mode = torch.tensor([m for _, m in lists], dtype=torch.int32)
+    return {"edit_ids": ids.to(device), "edit_vals": vals.to(device), "edit_lens": lens.to(device), "edit_mode": mode.to(device)}
+
+
+def apply_logit_edits(logits: torch.Tensor, edit_ids: Optional[torch.Tensor] = None, edit_vals: Optional[torch.Tensor] = None,
+                      edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None, *, penalty: Optional[torch.Tensor] = None,
+                      history: Optional[torch.Tensor] = None, history_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rule of omk_sample_rows (include/omk.h, ABI 14 and 16) in torch, on a copy: the repetition penalty over history[b, :history_lens[b]]
+    (rounded to the dtype of the logits), then the edits -- a listed token gets round(float(p) + the value of its FIRST entry), an unlisted
+    token of an allow-only row whose list holds a valid id gets -inf.  Lengths are clamped, ids outside [0, vocab) skipped, as the kernel
+    does.  What sample_rows draws from when the library declines the fused launch, and the statement the tests check that launch against."""
+    n, V = logits.shape
+    dev = logits.device
+    work = logits
+    if penalty is not None and history is not None:
+        # a mask of the history ids -- every write is True, so duplicates and the order of the writes do not matter; dead entries go to a
+        # spare column
+        cap = history.shape[1]
+        live = (torch.arange(cap, device=dev)[None] < history_lens[:, None]) & (history >= 0) & (history < V)
+        mask = torch.zeros(n, V + 1, dtype=torch.bool, device=dev).scatter_(1, torch.where(live, history, torch.full_like(history, V)), True)[:, :V]
+        pen = torch.where(penalty > 0, penalty, torch.ones_like(penalty))[:, None]
+        lf = logits.float()
+        work = torch.where(mask, torch.where(lf < 0, lf * pen, lf / pen).to(logits.dtype), logits)
+    if edit_ids is None or edit_ids.shape[1] == 0:
+        return work.clone() if work is logits else work
+    cap = edit_ids.shape[1]
+    pos = torch.arange(cap, device=dev)[None].expand(n, cap)
+    live = (pos < edit_lens[:, None]) & (edit_ids >= 0) & (edit_ids < V)
+    # the first entry of every listed token: the lowest entry index per column (a minimum: the order of the writes does not matter)
+    first = torch.full((n, V + 1), cap, dtype=torch.int64, device=dev).scatter_reduce_(
+        1, torch.where(live, edit_ids, torch.full_like(edit_ids, V)), pos.contiguous(), "amin")[:, :V]
+    listed = first < cap
+    add = edit_vals.float().gather(1, first.clamp(max=cap - 1))
+    allow = (edit_mode == 1 if edit_mode is not None else torch.zeros(n, dtype=torch.bool, device=dev)) & listed.any(1)
+    edited = (work.float() + add).to(logits.dtype)
+    return torch.where(listed, edited, torch.where(allow[:, None], torch.full_like(work, float("-inf")), work))
+
+
 def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev, what: str = "sample_rows"):
     if t is None:
         return None
@@ -103,14 +203,40 @@ def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev, what: str = "
 def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: Optional[torch.Tensor], temperature: Optional[torch.Tensor],
                 min_p: Optional[torch.Tensor], seeds: Optional[torch.Tensor], steps: Optional[torch.Tensor], penalty: Optional[torch.Tensor] = None,
                 history: Optional[torch.Tensor] = None, history_lens: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, edit_ids: Optional[torch.Tensor] = None, edit_vals: Optional[torch.Tensor] = None,
+                edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(batch, vocab) -> (batch,) int64 ids in ONE launch, row b sampled with its own settings: top_k (int32), top_p, temperature, min_p
     (float32), seeds and steps (int64; the seed's 64 bits) -- device tensors of (batch,).  Row b draws what
     sample_device(logits[b:b+1], ..., seed=seeds[b], offset=steps[b]) draws: its id does not depend on its place in the batch.
     penalty (float32) with history (int64 (batch, cap), unit last stride) and history_lens (int32): the repetition penalty of
     generation.modify_logit_for_repetition_penalty over history[b, :history_lens[b]], fused (logits is not written).  active (int32):
-    rows with 0 write nothing.  No host read: capturable, the tensors may be rewritten between replays."""
+    rows with 0 write nothing.  edit_ids (int64 (batch, cap), unit last stride) with edit_vals (float32, the same shape and strides) and
+    edit_lens (int32), optionally edit_mode (int32): per-row logit edits behind the penalty, fused (pack_edits makes them, apply_logit_edits
+    states the rule).  No host read: capturable, the tensors may be rewritten between replays.  A vocabulary too large for the kernel's id
+    map, or more than MAX_EDITS entries per row: the penalty and the edits are applied to a copy with torch and the plain launch draws."""
+    p, out = _rows_call(logits, top_k=top_k, top_p=top_p, temperature=temperature, min_p=min_p, seeds=seeds, steps=steps, penalty=penalty, history=history,
+                   history_lens=history_lens, active=active, out=out, edit_ids=edit_ids, edit_vals=edit_vals, edit_lens=edit_lens, edit_mode=edit_mode)
     lib = get_lib()
+    if K.try_run(lib, "omk_sample_rows", p, logits):
+        return out
+    work = apply_logit_edits(logits, edit_ids, edit_vals, edit_lens, edit_mode, penalty=penalty, history=history, history_lens=history_lens)
+    p.logits = K.T(work)
+    p.penalty = p.history = p.history_lens = p.edit_ids = p.edit_vals = p.edit_lens = p.edit_mode = None
+    p.edit_cap = 0
+    K.run(lib, "omk_sample_rows", p, logits)
+    return out
+
+
+def sample_rows_form(logits: torch.Tensor, **kw) -> int:
+    """Which launch sample_rows(logits, **kw) takes -- K.SAMPLE_ROWS_PLAIN / _PENALTY / _EDIT, or the negative omk_status the library refuses
+    the call with.  The launch's own decision (omk_sample_rows_form); nothing is launched."""
+    import ctypes
+    return int(get_lib().omk_sample_rows_form(ctypes.byref(_rows_call(logits, **kw)[0])))
+
+
+def _rows_call(logits, *, top_k, top_p, temperature, min_p, seeds, steps, penalty=None, history=None, history_lens=None, active=None, out=None,
+               edit_ids=None, edit_vals=None, edit_lens=None, edit_mode=None):
+    """(the OmkSampleRows of a sample_rows call, its output tensor)"""
     n, dev = logits.shape[0], logits.device
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=dev)
@@ -125,24 +251,19 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
         if history.dtype != torch.int64 or history.device != dev or history.dim() != 2 or history.shape[0] != n or (history.shape[1] > 1 and history.stride(1) != 1):
             raise ValueError("sample_rows: history must be int64 (batch, cap) with unit last stride on the device of logits")
         p.history, p.history_stride, p.history_cap = history.data_ptr(), history.stride(0), history.shape[1]
+    if edit_ids is not None:
+        if edit_ids.dtype != torch.int64 or edit_ids.device != dev or edit_ids.dim() != 2 or edit_ids.shape[0] != n or (edit_ids.shape[1] > 1 and edit_ids.stride(1) != 1):
+            raise ValueError("sample_rows: edit_ids must be int64 (batch, cap) with unit last stride on the device of logits")
+        if edit_vals is not None and (edit_vals.dtype != torch.float32 or edit_vals.device != dev or edit_vals.shape != edit_ids.shape or edit_vals.stride() != edit_ids.stride()):
+            raise ValueError("sample_rows: edit_vals must be float32 with the shape and strides of edit_ids on the device of logits")
+        p.edit_ids, p.edit_stride, p.edit_cap = edit_ids.data_ptr(), edit_ids.stride(0), edit_ids.shape[1]
+        p.edit_vals = None if edit_vals is None else edit_vals.data_ptr()
+        p.edit_lens, p.edit_mode = _ptr(edit_lens, torch.int32, n, "edit_lens", dev), _ptr(edit_mode, torch.int32, n, "edit_mode", dev)
     p.out_ids.data = out.data_ptr()
     p.out_ids.ndim = 1
     p.out_ids.shape[0] = n
     p.out_ids.stride[0] = out.stride(0)
-    if K.try_run(lib, "omk_sample_rows", p, logits):
-        return out
-    # the vocabulary does not fit the kernel's id map: penalise a copy with torch (a mask of the history ids -- every write is True, so
-    # duplicates and the order of the writes do not matter; dead entries go to a spare column) and draw without history
-    V, cap = logits.shape[1], history.shape[1]
-    live = (torch.arange(cap, device=dev)[None] < history_lens[:, None]) & (history >= 0) & (history < V)
-    mask = torch.zeros(n, V + 1, dtype=torch.bool, device=dev).scatter_(1, torch.where(live, history, torch.full_like(history, V)), True)[:, :V]
-    pen = torch.where(penalty > 0, penalty, torch.ones_like(penalty))[:, None]
-    lf = logits.float()
-    work = torch.where(mask, torch.where(lf < 0, lf * pen, lf / pen).to(logits.dtype), logits)
-    p.logits = K.T(work)
-    p.penalty = p.history = p.history_lens = None
-    K.run(lib, "omk_sample_rows", p, logits)
-    return out
+    return p, out
 
 
 # ---- log-probabilities behind the sampler (omk_token_logprobs, ABI 15) ------------------------------------------------------------------
