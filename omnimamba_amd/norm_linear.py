@@ -98,7 +98,7 @@ def conv_tail_applies(x, weight, norm_weight, conv_state, conv_weight, conv_bias
 def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=None, residual_out_dtype=None, z=None,
                 group_size=None, norm_before_gate=False, lora_a=None, lora_b=None, lora_scale=0.0, out_dtype=None,
                 conv_state=None, conv_weight=None, conv_bias=None, conv_offset=0, conv_silu=True, conv_state_indices=None,
-                weight_scale=None):
+                weight_scale=None, out=None, residual_out=None):
     """out = norm(x [+ residual] | gated by z) @ weight^T [+ bias] [+ lora_scale * (n @ lora_a^T) @ lora_b^T].
     x: (B, in).  Returns out, or (out, residual_out) when `residual_out_dtype` is given (residual_out = x + residual).
     conv_state (B, C, S) + conv_weight (C, W): output columns [conv_offset, conv_offset + C) additionally go through
@@ -106,9 +106,12 @@ def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=No
     conv_state_indices (B,) int32 (int64 is cast: one extra launch): sequence b rolls conv_state row conv_state_indices[b] of a pool
     with any number of rows; a negative index marks a padding sequence -- its conv state is neither read nor written and its conv
     columns of out are zeros.  The values are never read on the host.
-    weight_scale (out,) fp32: the per-row scale of a `float8_e4m3fn` weight (required with one, refused without)."""
+    weight_scale (out,) fp32: the per-row scale of a `float8_e4m3fn` weight (required with one, refused without).
+    out (B, out) / residual_out (B, in): write into these tensors instead of fresh ones (rows may be strided, e.g. column slices of a wider
+    buffer; their dtypes stand in for `out_dtype` / `residual_out_dtype`)."""
     lib, p, x, out, ro = _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, group_size, norm_before_gate, lora_a, lora_b,
-                                 lora_scale, out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale)
+                                 lora_scale, out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale,
+                                 out, residual_out)
     K.run(lib, "omk_norm_linear", p, x)
     return out if ro is None else (out, ro)
 
@@ -116,21 +119,22 @@ def norm_linear(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=No
 def form(x, weight, bias=None, *, norm_weight=None, eps=1e-5, residual=None, residual_out_dtype=None, z=None,
          group_size=None, norm_before_gate=False, lora_a=None, lora_b=None, lora_scale=0.0, out_dtype=None,
          conv_state=None, conv_weight=None, conv_bias=None, conv_offset=0, conv_silu=True, conv_state_indices=None,
-         weight_scale=None) -> int:
+         weight_scale=None, out=None, residual_out=None) -> int:
     """Which kernel `norm_linear` runs for these arguments: GENERIC, FAST, BATCHED or MATRIX, or the negative omk_status with which the
     library refuses the call.  The launch's own decision (omk_norm_linear_form); nothing is launched."""
     import ctypes
     lib, p, _, _, _ = _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, group_size, norm_before_gate, lora_a, lora_b,
-                              lora_scale, out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale)
+                              lora_scale, out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale,
+                              out, residual_out)
     return int(lib.omk_norm_linear_form(ctypes.byref(p)))
 
 
 def _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, group_size, norm_before_gate, lora_a, lora_b, lora_scale,
-            out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale):
-    """The call's descriptor (and its freshly allocated outputs): what `norm_linear` hands to the library and `form` asks about."""
+            out_dtype, conv_state, conv_weight, conv_bias, conv_offset, conv_silu, conv_state_indices, weight_scale, out=None, residual_out=None):
+    """The call's descriptor and its outputs (the caller's, or freshly allocated): what `norm_linear` hands to the library and `form` asks about."""
     lib = get_lib()
     require_device(lib, x, weight, bias, norm_weight, residual, z, lora_a, lora_b, conv_state, conv_weight, conv_bias, conv_state_indices,
-                   weight_scale)
+                   weight_scale, out, residual_out)
     if conv_state_indices is not None and conv_state is None:
         raise ValueError("conv_state_indices need conv_state")
     idx = slot_indices(conv_state_indices, x.shape[0], x.device, "conv_state_indices")
@@ -139,8 +143,11 @@ def _params(x, weight, bias, norm_weight, eps, residual, residual_out_dtype, z, 
     if z is not None and (z.dtype != x.dtype or z.stride(-1) != 1):
         z = z.to(x.dtype).contiguous()
     B = x.shape[0]
-    out = torch.empty(B, weight.shape[0], dtype=out_dtype or x.dtype, device=x.device)
-    ro = None if residual_out_dtype is None else torch.empty(B, x.shape[1], dtype=residual_out_dtype, device=x.device)
+    if out is None:
+        out = torch.empty(B, weight.shape[0], dtype=out_dtype or x.dtype, device=x.device)
+    ro = residual_out
+    if ro is None and residual_out_dtype is not None:
+        ro = torch.empty(B, x.shape[1], dtype=residual_out_dtype, device=x.device)
     p = K.NormLinear(x=K.T(x), residual=K.T(residual), z=K.T(z), norm_weight=K.T(norm_weight), weight=K.T(weight), bias=K.T(bias),
                      lora_a=K.T(lora_a), lora_b=K.T(lora_b), residual_out=K.T(ro), out=K.T(out),
                      conv_state=K.T(conv_state), conv_weight=K.T(conv_weight), conv_bias=K.T(conv_bias),

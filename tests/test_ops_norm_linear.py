@@ -48,7 +48,7 @@ def test_uniform_dtype_variant(dev, In, Out, dtype, rdtype, with_lora, with_z):
     """The templated kernel the 1.3B decode takes (one dtype for activations, weights, norm weight and LoRA; fp32 or that
     dtype for the residual): against the fp64 composition, and against the generic kernel on the same inputs (the norm weight's
     values in the other dtype: a mix the templated kernel does not take)."""
-    from omnimamba_amd.norm_linear import norm_linear
+    from omnimamba_amd.norm_linear import norm_linear, form, FAST, GENERIC
     x, res, z = torch.randn(1, In).to(dtype), torch.randn(1, In).to(rdtype), torch.randn(1, In).to(dtype)
     nw, W, bias = (torch.rand(In) + 0.5).bfloat16().to(dtype), (torch.randn(Out, In) * 0.05).to(dtype), torch.randn(Out).to(dtype)
     la, lb = (torch.randn(8, In) * 0.05).to(dtype), (torch.randn(Out, 8) * 0.05).to(dtype)
@@ -59,8 +59,10 @@ def test_uniform_dtype_variant(dev, In, Out, dtype, rdtype, with_lora, with_z):
         kw.update(residual=res.to(dev), residual_out_dtype=rdtype)
     if with_lora:
         kw.update(lora_a=la.to(dev), lora_b=lb.to(dev), lora_scale=4.0)
-    r = norm_linear(x.to(dev), W.to(dev), bias.to(dev), **kw)
     other = torch.bfloat16 if dtype == torch.float32 else torch.float32
+    assert form(x.to(dev), W.to(dev), bias.to(dev), **kw) == FAST                                        # the templated kernel ...
+    assert form(x.to(dev), W.to(dev), bias.to(dev), **dict(kw, norm_weight=nw.to(other).to(dev))) == GENERIC   # ... and the run-time-dtype one
+    r = norm_linear(x.to(dev), W.to(dev), bias.to(dev), **kw)
     g = norm_linear(x.to(dev), W.to(dev), bias.to(dev), **dict(kw, norm_weight=nw.to(other).to(dev)))
     out, outg = (r, g) if with_z else (r[0], g[0])
     xd = x.double()
@@ -109,7 +111,10 @@ def test_conv_tail(dev, dtype, W, S):
 def test_batched_variant(dev, B, In, Out, dtype, rdtype, mode):
     """Two to eight sequences per call (decode batches): every weight vector is used for all sequences while it is in
     registers.  Against the fp64 composition per sequence; with the conv tail, two consecutive steps."""
-    from omnimamba_amd.norm_linear import norm_linear, applies
+    from omnimamba_amd.norm_linear import norm_linear, applies, form, BATCHED, MATRIX
+    # the selector's rule: bf16 weights (LoRA rank 8 in aligned rows, or none) and fp32 weights at five to eight sequences with LoRA and up to
+    # 2048 features run on the matrix pipe, the other fp32 cases on the vector pipe
+    kernel = MATRIX if dtype == torch.bfloat16 or (B > 4 and "lora" in mode and In <= 2048) else BATCHED
     C, off, W, S = 64, 16, 4, 4
     nw, Wt, bias = (torch.rand(In) + 0.5).to(dtype), (torch.randn(Out, In) * 0.05).to(dtype), torch.randn(Out).to(dtype)
     la, lb = (torch.randn(8, In) * 0.05).to(dtype), (torch.randn(Out, 8) * 0.05).to(dtype)
@@ -130,11 +135,15 @@ def test_batched_variant(dev, B, In, Out, dtype, rdtype, mode):
         if "conv" in mode:
             kw.update(conv_state=cst_d, conv_weight=cw.to(dev), conv_bias=cb.to(dev), conv_offset=off)
         assert applies(x.to(dev), Wt.to(dev), nw.to(dev), la.to(dev) if "lora" in mode else None, bias.to(dev))
+        assert form(x.to(dev), Wt.to(dev), bias.to(dev), **kw) == kernel
         r = norm_linear(x.to(dev), Wt.to(dev), bias.to(dev), **kw)
         out = r if mode == "gate" else r[0]
         n0 = q * torch.rsqrt((q * q).mean(-1, keepdim=True) + 1e-5) * nw.double()
         if dtype == torch.bfloat16:
-            n0 = n0.to(dtype).double()                      # the batched kernel keeps u in bf16 (upstream's rounding point)
+            # under bf16 weights both kernels for two to eight sequences keep u in LDS as bf16 (lds_u<bf16_t>: upstream's rounding point; the
+            # kernel rounds the UN-normalised u, this reference the normalised n); every bf16 case here takes the matrix form, the bf16 vector
+            # form is reached in test_norm_linear_slices.py
+            n0 = n0.to(dtype).double()
         y0 = n0 @ Wt.double().t() + bias.double()
         if "lora" in mode:
             y0 = y0 + 4.0 * (n0 @ la.double().t()) @ lb.double().t()

@@ -36,7 +36,19 @@ backward's own arithmetic is measured):
 
 with a = OP_ARITH = 1e-4, the allowance of fp32 arithmetic with fast exp / rcp / rsqrt and long fp32 sums.  dw / db of the norms
 and the conv are fp32 sums: q = 0, so a dropped row (1 / sqrt(rows) of rel-L2) or a double-counted partial is far outside the
-bound, where the flat 1.5e-2 of rounds 1 - 6 hid it."""
+bound, where the flat 1.5e-2 of rounds 1 - 6 hid it.
+
+omk_norm_linear (tests/test_norm_linear_slices.py) comes under the same rule, per (sequence, block of 16 output rows), with its two
+documented internal rounding points reproduced by the reference and nothing else.  (1) With bf16 weights the kernels for two to eight
+sequences (BATCHED and MATRIX) keep u = (x + residual | x silu(z)) * w in LDS as bf16, and the LoRA input is the same rounded u: the
+reference forms u in fp32 in the kernel's order of operations, rounds it to bf16 and goes on in fp64 (the sum of squares takes the
+unrounded q, as the kernel does).  Without a gate that u is bit-identical to the kernel's.  With a gate the kernel's silu_fast differs from
+the exact sigmoid by a few fp32 ulps, so an element of u next to a bf16 rounding midpoint could round the other way; the bound is NOT
+widened for that: the inputs are chosen on the reference alone -- every element of z whose exact u lies within relative
+MIDPOINT_REL = 2^-19 (about 16 fp32 ulps: three roundings, a hardware exp2 and a reciprocal) of a midpoint is drawn again, and each
+gated row asserts that none is left (near_bf16_midpoint).  (2) The conv tail rounds the projected value to the activation dtype before it
+enters the tap sum and becomes the newest state column: that stored column is checked against the unrounded projection (one rounding of
+the exact value), and the conv reference takes it as stored, like a backward reference takes the forward's saved tensors."""
 import math
 
 import torch
@@ -95,7 +107,7 @@ def op_bound(ref, dtype, arith=OP_ARITH):
 SLICE_FLOOR = 0.1
 
 
-def slice_check(name, got, ref, dtype, keep, arith=OP_ARITH, bound=None, groups=None):
+def slice_check(name, got, ref, dtype, keep, arith=OP_ARITH, bound=None, groups=None, sizes=None):
     """op_bound on every slice of one output (the selective scan; module docstring for the rule).  The first `keep` dimensions index
     the slices, the others are reduced: out / du / ddelta / dz (B, D, L) keep 2 = a (batch, channel) row over L; input-dependent
     dB / dC (B, G, N, L) keep 3; dA and constant dB / dC (D, N) keep 1; states (B, D, N) keep 2; dD / ddelta_bias (D) keep 1 = each
@@ -108,6 +120,8 @@ def slice_check(name, got, ref, dtype, keep, arith=OP_ARITH, bound=None, groups=
     by 1e-6 may round the other way).  `groups` (a tensor of ids over the last slice dimension, i.e. per channel): the RMS of the floor
     is taken inside each group where that is SMALLER than the tensor's -- channels of different decay regimes in one launch, whose
     slices differ by orders of magnitude, are each judged on their own scale and never on a larger one than without groups.
+    `sizes` (a tensor over the slices): the number of real elements of each slice where ragged slices were padded with zeros on both
+    sides (column_blocks below) -- a slice of one real element takes the half-ulp q like a slice of one element.
     `bound`: a flat number per slice in place of op_bound (two launches that must agree).  Fails naming the tensor, the slice, its error, q and bound; returns
     (worst error, q of that slice, its bound, share of slices that met the floor)."""
     got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
@@ -127,7 +141,8 @@ def slice_check(name, got, ref, dtype, keep, arith=OP_ARITH, bound=None, groups=
     if dtype in (torch.float32, torch.float64):
         q = torch.zeros_like(err)
     else:
-        q = 0.5 * torch.finfo(dtype).eps * norms / den if r2.shape[-1] == 1 else (r2.to(dtype).double() - r2).norm(dim=-1) / den
+        half, meas = 0.5 * torch.finfo(dtype).eps * norms / den, (r2.to(dtype).double() - r2).norm(dim=-1) / den
+        q = half if r2.shape[-1] == 1 else (meas if sizes is None else torch.where(sizes.expand(lead) == 1, half, meas))
     lim = torch.full_like(err, bound) if bound is not None else 1.1 * (q * q + arith * arith).sqrt()
     share = (norms < floor).double().mean().item()
     i = int((err / lim).argmax())
@@ -135,3 +150,26 @@ def slice_check(name, got, ref, dtype, keep, arith=OP_ARITH, bound=None, groups=
     e, qq, b = err.flatten()[i].item(), q.flatten()[i].item(), lim.flatten()[i].item()
     assert e <= b, f"{name}: slice {idx} error {e:.3e} q {qq:.3e} bound {b:.3e} ({int((err > lim).sum())} of {err.numel()} slices over)"
     return e, qq, b, share
+
+
+def column_blocks(got, ref, lo, hi, align=0, width=16):
+    """Columns [lo, hi) of two (rows, columns) tensors cut into blocks of `width` columns whose edges lie at align + k * width, for
+    slice_check: returns (got, ref) as (rows, blocks, width) in fp64, ragged first / last blocks padded with zeros in both (a zero adds
+    nothing to a slice's norm, error or rounding), and the number of real columns of every block (slice_check's `sizes`)."""
+    first = lo - (lo - align) % width
+    edges = [(max(a, lo), min(a + width, hi)) for a in range(first, hi, width)]
+    g3, r3 = (torch.zeros(ref.shape[0], len(edges), width, dtype=torch.float64) for _ in range(2))
+    for j, (a, b) in enumerate(edges):
+        g3[:, j, :b - a], r3[:, j, :b - a] = got[:, a:b].double().cpu(), ref[:, a:b].double().cpu()
+    return g3, r3, torch.tensor([b - a for a, b in edges])
+
+
+MIDPOINT_REL = 2.0 ** -19
+
+
+def near_bf16_midpoint(u, rel_dist=MIDPOINT_REL):
+    """Mask of the elements of the fp64 tensor u that lie within rel_dist * |u| of the midpoint of two neighbouring bf16 values (module
+    docstring, norm_linear): |u| = t * 2^e with t in [128, 256) has the bf16 grid at the integers of t."""
+    mant, _ = torch.frexp(u.abs().double())
+    t = mant * 256.0
+    return ((t - t.floor() - 0.5).abs() <= t * rel_dist) & (u != 0)
