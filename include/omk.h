@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define OMK_ABI_VERSION 16
+#define OMK_ABI_VERSION 17
 #define OMK_MAX_DIMS 5
 
 typedef enum { OMK_OK = 0, OMK_EINVAL = -1, OMK_EARCH = -2, OMK_ELAUNCH = -3, OMK_EUNSUPPORTED = -4 } omk_status;
@@ -577,6 +577,60 @@ typedef struct {
   int32_t top_n;             /* 0 .. 64 */
 } OmkTokenLogprobs;
 int omk_token_logprobs(const OmkTokenLogprobs* p, omk_stream stream);
+
+/* ---- ABI 17: presence and frequency penalties as a device-built edit list for omk_sample_rows ------------------------------------------
+ * One launch in front of the sampler, one workgroup per row, nothing read from the host: row b's edit list for OMK_SAMPLE_ROWS_EDIT is built
+ * from its history and merged with the request's own list.  The sampler kernels are not touched.  In fp32 unless said otherwise:
+ *   len     = clamp(history_lens[b], 0, history_cap); the COUNTED RANGE is history[b][clamp(count_start[b], 0, len) .. len)
+ *   c_i     = how often token i occurs in the counted range (ids outside [0, vocab) are skipped)
+ *   delta_i = 0 when c_i == 0, else -((frequency[b] * float(c_i)) + presence[b]) -- the product and the sum are rounded SEPARATELY, never
+ *             a fused multiply-add; a non-finite frequency[b] or presence[b] counts as 0
+ * With the list this launch writes, omk_sample_rows sees (p_i and round_T as ABI 14 / 16 define them, val_i the value of the FIRST user
+ * entry that names i):
+ *   i listed and counted:      e_i = round_T(float(p_i) + (val_i + delta_i))      (the inner sum first)
+ *   i listed, not counted:     e_i = round_T(float(p_i) + val_i)                  (ABI 16 as it is)
+ *   i not listed, counted:     e_i = round_T(float(p_i) + delta_i); -inf in an allow-only row (the allowed set wins)
+ *   neither:                   e_i = p_i; -inf in an allow-only row
+ * Allow-only as in ABI 16: edit_mode[b] == 1 and the user list holds a valid id (without one the row is unconstrained and gets the
+ * penalties).  Row b's output:
+ *   1. its n_user = clamp(edit_lens[b], 0, edit_cap) user entries first, in their order, ids unchanged (invalid ones too); the value of a
+ *      valid id with c_id > 0 is edit_vals + delta_id (-inf stays -inf), every other value is unchanged
+ *   2. not allow-only: behind them one entry (i, delta_i) for every distinct counted token i that no valid user entry names, in the order
+ *      of their first occurrence in the counted range
+ *   3. out_lens[b] = the total, clamped to out_cap; entries that do not fit are dropped, entries behind out_lens[b] are not written
+ *   4. out_mode[b] = 1 for an allow-only row, else 0
+ *   5. active[b] == 0 (optional): the row writes nothing
+ *   6. both penalties zero or non-finite, or an empty counted range: the user list, as it is
+ * Correct for a counted range of any length up to history_cap; the work grows with its square, and it is sized for the at most 512 entries
+ * a row's list holds in omk_sample_rows.  The outputs must not overlap the user list.  Capturable; every array may be rewritten between
+ * replays.  OMK_EINVAL: a required array missing (history, history_lens, count_start, frequency, presence, the four outputs), edit_ids
+ * without edit_vals or edit_lens, a negative cap or batch, a vocabulary outside [1, 2^31), with more than one row a row stride below the
+ * width of its array.  batch == 0: OMK_OK, nothing is launched.                                                                      */
+typedef struct {
+  const void* history;       /* device int64 (batch, history_cap), row b at history + b * history_stride */
+  const void* history_lens;  /* device int32 (batch) */
+  const void* count_start;   /* device int32 (batch): where in the row's history the counted range begins */
+  const void* frequency;     /* device f32 (batch) */
+  const void* presence;      /* device f32 (batch) */
+  const void* active;        /* optional device int32 (batch); NULL = every row */
+  int64_t history_stride;    /* elements between the rows of history */
+  int64_t history_cap;       /* width of history */
+  const void* edit_ids;      /* optional user list, the layout of OmkSampleRows: device int64 (batch, edit_cap) */
+  const void* edit_vals;     /* device f32, the layout of edit_ids; required with edit_ids */
+  const void* edit_lens;     /* device int32 (batch); required with edit_ids */
+  const void* edit_mode;     /* optional device int32 (batch), 1 = allow-only; NULL = 0 everywhere */
+  int64_t edit_stride;       /* elements between the rows of edit_ids and of edit_vals */
+  int64_t edit_cap;          /* width of edit_ids and edit_vals; 0 = no user list */
+  void* out_ids;             /* out: device int64 (batch, out_cap), row b at out_ids + b * out_stride */
+  void* out_vals;            /* out: device f32, the layout of out_ids */
+  void* out_lens;            /* out: device int32 (batch) */
+  void* out_mode;            /* out: device int32 (batch) */
+  int64_t out_stride;        /* elements between the rows of out_ids and of out_vals */
+  int64_t out_cap;           /* width of out_ids and out_vals */
+  int64_t batch;             /* rows */
+  int64_t vocab;             /* ids outside [0, vocab) are skipped */
+} OmkPenaltyEdits;
+int omk_penalty_edits(const OmkPenaltyEdits* p, omk_stream stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-OMK_ABI_VERSION = 16
+OMK_ABI_VERSION = 17
 OMK_MAX_DIMS = 5
 OMK_EUNSUPPORTED = -4   # omk_status: the kernel does not take this call (the caller may have another way)
 NL_FORM_GENERIC, NL_FORM_FAST, NL_FORM_BATCHED, NL_FORM_MATRIX = 0, 1, 2, 3   # omk_norm_linear_form (ABI 12)
@@ -105,8 +105,14 @@ SAMPLE_ROWS_PLAIN, SAMPLE_ROWS_PENALTY, SAMPLE_ROWS_EDIT = 0, 1, 2   # omk_sampl
 # ABI 15: log-probabilities of the sampled tokens, the top_n tokens of every row, the sampled token's rank (include/omk.h)
 TokenLogprobs = _S("OmkTokenLogprobs", [(n, _t) for n in ("logits", "logprob", "rank", "top_ids", "top_logprobs")]
                    + [("ids", C.c_void_p), ("active", C.c_void_p), ("top_n", _i)])
+# ABI 17: presence and frequency penalties as a device-built edit list in front of omk_sample_rows (include/omk.h)
+PenaltyEdits = _S("OmkPenaltyEdits", [(n, C.c_void_p) for n in ("history", "history_lens", "count_start", "frequency", "presence", "active")]
+                  + [("history_stride", _i64), ("history_cap", _i64)]
+                  + [(n, C.c_void_p) for n in ("edit_ids", "edit_vals", "edit_lens", "edit_mode")] + [("edit_stride", _i64), ("edit_cap", _i64)]
+                  + [(n, C.c_void_p) for n in ("out_ids", "out_vals", "out_lens", "out_mode")] + [("out_stride", _i64), ("out_cap", _i64)]
+                  + [("batch", _i64), ("vocab", _i64)])
 
-STRUCTS = {s.__name__: s for s in (Sample, SampleRows, TokenLogprobs, CrossEntropy, OmkTensor, AddNormFwd, AddNormBwd, NormGatedFwd, NormGatedBwd, Conv1dFwd, Conv1dBwd,
+STRUCTS = {s.__name__: s for s in (Sample, SampleRows, TokenLogprobs, PenaltyEdits, CrossEntropy, OmkTensor, AddNormFwd, AddNormBwd, NormGatedFwd, NormGatedBwd, Conv1dFwd, Conv1dBwd,
                                    Conv1dUpdate, StateUpdate, StateExtend, SelScanFwd, SelScanBwd, NormLinear, LoraAdd, LoraUpBwd, SsdFwd, SsdBwd)}
 
 # every symbol include/omk.h declares
@@ -118,7 +124,7 @@ SYMBOLS = [
     "omk_selective_state_update", "omk_selective_state_extend", "omk_norm_linear", "omk_norm_linear_form", "omk_lora_add", "omk_lora_up_bwd",
     "omk_selective_scan_fwd", "omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_selective_scan_bwd_workspace_bytes", "omk_selective_scan_bwd",
     "omk_ssd_scan_fwd_workspace_bytes", "omk_ssd_scan_fwd_window_states_bytes", "omk_ssd_scan_fwd", "omk_ssd_scan_bwd_workspace_bytes", "omk_ssd_scan_bwd",
-    "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample", "omk_sample_rows", "omk_sample_rows_form", "omk_token_logprobs",
+    "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample", "omk_sample_rows", "omk_sample_rows_form", "omk_token_logprobs", "omk_penalty_edits",
 ]
 
 

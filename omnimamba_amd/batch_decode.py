@@ -32,7 +32,13 @@ import torch
 from . import generation as G
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
 from . import sampling as _sampling
-from .sampling import SamplingParams, TokenLogprobs, edit_list, has_edits, pack_edits, pack_rows, sample_rows
+from .sampling import (MAX_EDITS, SamplingParams, TokenLogprobs, apply_logit_edits, edit_list, has_count_penalties, has_edits, pack_count_penalties,
+                       pack_edits, pack_rows, sample_rows)
+
+# A draw with presence / frequency penalties takes the fused path (sampling.penalty_edits + the edit launch) while the rows' user width plus
+# the ids their requests have sampled so far fit this many entries; past it the draw edits a copy.  Equal to MAX_EDITS; a name of its own
+# so that a test can lower it.
+PENALTY_FUSED_MAX = MAX_EDITS
 
 
 @dataclass
@@ -81,7 +87,7 @@ class _Bucket:
                 s.synchronize()
             torch.cuda.current_stream().wait_stream(s)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, pool=mempool):
+            with G.capture(self.graph, pool=mempool):
                 self.logits = self._fwd()
 
     def _fwd(self):
@@ -115,6 +121,23 @@ class _Bucket:
             st.update(pack_edits([SamplingParams()] * self.nb, self.input_ids.device, width=width))
         return st
 
+    def row_penalties(self, need=None):
+        """Static frequency / presence / count_start rows next to the row settings, and (need given) the static merged edit buffers that
+        sampling.penalty_edits writes for the edit launch: a power of two wide, at least `need` and at most MAX_EDITS, made anew only when
+        the width has to grow."""
+        st, dev = self.row_settings(), self.input_ids.device
+        if "frequency" not in st:
+            st.update({k: v.clone() for k, v in pack_count_penalties([SamplingParams()] * self.nb, dev).items()})
+            st["count_start"] = torch.zeros(self.nb, dtype=torch.int32, device=dev)
+        if need is not None and ("merged" not in st or st["merged"]["edit_ids"].shape[1] < need):
+            w = 1
+            while w < need:
+                w *= 2
+            w = min(w, MAX_EDITS)
+            st["merged"] = {"edit_ids": torch.zeros(self.nb, w, dtype=torch.long, device=dev), "edit_vals": torch.zeros(self.nb, w, device=dev),
+                            "edit_lens": torch.zeros(self.nb, dtype=torch.int32, device=dev), "edit_mode": torch.zeros(self.nb, dtype=torch.int32, device=dev)}
+        return st
+
 
 class _RowSampler:
     """decode_ragged(sampling=...): every draw of the call through ONE row-wise launch (sampling.sample_rows), request i with
@@ -123,7 +146,10 @@ class _RowSampler:
     input_ids followed by its sampled ids.  Its length is ids_len[i] + count[i] on the host; the device copy the kernel reads is the
     bucket's static history_lens, advanced on the device between row changes.  With logit edits somewhere (logit_bias, allowed or banned
     ids, min_new_tokens) every draw carries the rows' edit lists, `width` entries wide: the longest list of the call and one entry for the
-    EOS ban of min_new_tokens, which is in a row's list while its request has sampled fewer ids than that."""
+    EOS ban of min_new_tokens, which is in a row's list while its request has sampled fewer ids than that.  With a presence or frequency
+    penalty somewhere the pool owns the history buffer as well and every draw carries the rows' frequency / presence / count_start, the
+    length of a request's input_ids: only the ids it sampled in this call count.  Which path such a draw takes is decided on the host from
+    `count` and `width` (_draw): penalty_edits + the edit launch while they fit PENALTY_FUSED_MAX entries, a torch-edited copy past it."""
 
     def __init__(self, c, params, requests, lens, dev, eos=None):
         self.c, self.params, self.dev, self.eos = c, params, dev, eos
@@ -133,8 +159,10 @@ class _RowSampler:
         self.ids_len = [r[0].shape[1] for r in requests]
         self.requests = requests
         self.pen = any(p.repetition_penalty != 1.0 for p in params)
+        self.cpen = any(has_count_penalties(p) for p in params)
+        self.hist_on = self.pen or self.cpen       # the pool owns a history buffer
         self.prev = None                           # (bucket size, requests of the rows) of the last step
-        if self.pen:
+        if self.hist_on:
             cap = max(c["max_seqlen"], max(l + m for l, m in zip(self.ids_len, lens)))
             h = c.get("history")
             if h is None or h.shape[1] < cap or h.device != dev:
@@ -157,17 +185,36 @@ class _RowSampler:
     def _edits(self, reqs):
         return pack_edits([self.params[i] for i in reqs], self.dev, self._bans(reqs), width=self.width)
 
+    def _draw(self, logits, kw, reqs, merged=None):
+        """One row-wise draw with the keyword arguments `kw` of sample_rows for rows that belong to the requests `reqs`.  With presence /
+        frequency penalties in the call (kw carries frequency, presence and count_start then) the host picks the path: the fused one while
+        the user width plus the most ids a request of `reqs` has sampled fit PENALTY_FUSED_MAX entries -- merged(need) hands out the static
+        buffers of the merged lists --, past it the plain launch on a copy edited with torch."""
+        if not self.cpen:
+            return sample_rows(logits, **kw)
+        cmax = max(self.count[i] for i in reqs)
+        need = self.width + cmax
+        if need <= PENALTY_FUSED_MAX:
+            return sample_rows(logits, **kw, count_max=cmax, merged=None if merged is None else merged(need))
+        plain = {k: kw[k] for k in ("top_k", "top_p", "temperature", "min_p", "seeds", "steps", "active", "out") if k in kw}
+        work = apply_logit_edits(logits, kw.get("edit_ids"), kw.get("edit_vals"), kw.get("edit_lens"), kw.get("edit_mode"), penalty=kw.get("penalty"),
+                                 history=kw["history"], history_lens=kw["history_lens"], frequency=kw["frequency"], presence=kw["presence"],
+                                 count_start=kw["count_start"])
+        return sample_rows(work, **plain)
+
     def admit(self, reqs, slots, logits):
         """The first id of the requests `reqs` (just admitted into `slots`) from their prefill / extend logits (len(reqs), vocab)."""
         pk = self._settings(reqs)
         if self.edit:
             pk.update(self._edits(reqs))
-        if self.pen:
+        if self.hist_on:
             rows = torch.tensor(slots, dtype=torch.long).to(self.dev, non_blocking=True)
             for i, s in zip(reqs, slots):
                 self.hist[s, :self.ids_len[i]].copy_(self.requests[i][0][0], non_blocking=True)
             hl = torch.tensor([self.ids_len[i] for i in reqs], dtype=torch.long).to(self.dev, non_blocking=True)
-            toks = sample_rows(logits, **pk, history=self._rows_history(rows, reqs), history_lens=hl.int())
+            if self.cpen:
+                pk.update(pack_count_penalties([self.params[i] for i in reqs], self.dev), count_start=hl.int())
+            toks = self._draw(logits, dict(pk, history=self._rows_history(rows, reqs), history_lens=hl.int()), reqs)
             self.hist.index_put_((rows, hl), toks)
         else:
             pk.pop("penalty")
@@ -184,24 +231,32 @@ class _RowSampler:
         if self.edit:
             st = bk.row_edits(self.width)
             key += (tuple(bool(b) for b in self._bans([i for i, _, _ in live])),)
+        if self.cpen:
+            st = bk.row_penalties()
         if key != self.prev:
             reqs = [i for i, _, _ in live]
             pk = self._settings(reqs)
             if self.edit:
                 pk.update(self._edits(reqs))
+            if self.cpen:
+                pk.update(pack_count_penalties([self.params[i] for i in reqs], self.dev),
+                          count_start=torch.tensor([self.ids_len[i] for i in reqs], dtype=torch.int32).to(self.dev, non_blocking=True))
             for k, v in pk.items():
                 st[k][:nl].copy_(v)
             st["active"].copy_(torch.tensor([1] * nl + [0] * (bk.nb - nl), dtype=torch.int32), non_blocking=True)
-            if self.pen:
+            if self.hist_on:
                 st["history_lens"].copy_(torch.tensor([self.ids_len[i] + self.count[i] for i in reqs] + [0] * (bk.nb - nl), dtype=torch.int32),
                                          non_blocking=True)
             self.prev = key
         kw = {k: st[k] for k in ("top_k", "top_p", "temperature", "min_p", "seeds", "steps", "active", "out")}
         if self.edit:
             kw.update({k: st[k] for k in ("edit_ids", "edit_vals", "edit_lens", "edit_mode")})
-        if self.pen:
-            toks = sample_rows(logits, **kw, penalty=st["penalty"], history=self._rows_history(rows, [i for i, _, _ in live]),
-                               history_lens=st["history_lens"])[:nl]
+        if self.hist_on:
+            reqs = [i for i, _, _ in live]
+            if self.cpen:
+                kw.update({k: st[k] for k in ("frequency", "presence", "count_start")})
+            toks = self._draw(logits, dict(kw, penalty=st["penalty"], history=self._rows_history(rows, reqs), history_lens=st["history_lens"]),
+                              reqs, merged=lambda need: bk.row_penalties(need)["merged"])[:nl]
             self.hist.index_put_((rows[:nl], st["history_lens"][:nl].long()), toks)
             st["history_lens"].add_(1)
         else:
@@ -427,6 +482,11 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     omk_sample_rows ABI 16); the lists live in static per-bucket tensors that are rewritten only when the rows change.  min_new_tokens bans
     eos_token_id (required then) until the request has sampled that many ids in this call; the rows are repacked on the step where the ban
     ends.  The requests without constraints draw the ids they draw without constrained neighbours; logprobs stay those of the raw logits.
+    Presence and frequency penalties (SamplingParams.presence_penalty, frequency_penalty): over the ids the request has sampled IN THIS CALL
+    (its input_ids do not count; a follow-up turn starts at zero).  When a request of the call has one, every draw carries the rows'
+    penalties: sampling.penalty_edits builds the rows' lists on the device (merged with their own edits, static per-bucket buffers) and the
+    edit launch draws -- two launches, no host read -- while the user width plus the ids sampled so far fit PENALTY_FUSED_MAX entries; past
+    that the draw edits a copy with sampling.apply_logit_edits.  The ids are the same on both paths.
 
     logprobs: None -- off.  An int N in [0, 64] for every request, or a list with one entry per request (an int, or None for a request
     that wants no record): the call returns ONE MORE element behind what it returns otherwise (ids_list, logprobs_list) or (ids_list,

@@ -6,6 +6,8 @@ which the omk_* kernels allow because they never allocate, synchronise or read h
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import time
 from dataclasses import dataclass, field
 from typing import Optional
@@ -13,6 +15,27 @@ from typing import Optional
 import torch
 
 from . import sampling as SMP
+
+
+@contextlib.contextmanager
+def capture(graph, pool=None):
+    """torch.cuda.graph(graph, pool=pool) with Python's cyclic garbage collected IN FRONT of the capture and the collector off inside it.
+    A model and its decoding caches refer to each other (model._ragged_cache -> buckets -> model), so a dropped model with its captured
+    graphs and device buffers is freed only by the cyclic collector -- whenever its allocation counters say so.  A run of the GPU suite
+    aborted with the collector running inside PrefillGraph's capture ("Fatal Python error: Aborted ... Garbage-collecting"); that the
+    release of such a cycle was the device call the capturing thread may not make is SUPPOSED -- which object's release aborted was not
+    shown -- and with this in place the suite passes.  torch.cuda.graph collected on entry itself until that became optional
+    (torch.compiler.config.force_cudagraph_gc, off by default in 2.10).  gc.disable() holds for the whole process: captures here are made
+    from one thread, and no other thread is expected to rely on the collector during the milliseconds a capture takes."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, pool=pool):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 @dataclass
@@ -150,7 +173,7 @@ class StepGraph:
                 torch.distributed.barrier()
         torch.cuda.current_stream().wait_stream(s)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=mempool):
+        with capture(self.graph, pool=mempool):
             self.logits = fwd()
         inference_params.seqlen_offset = off
 
@@ -192,7 +215,7 @@ class PrefillGraph:
             s.synchronize()
         torch.cuda.current_stream().wait_stream(s)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=mempool):
+        with capture(self.graph, pool=mempool):
             self.logits = fwd()
         inference_params.seqlen_offset = off
 
@@ -253,7 +276,7 @@ class GreedyLoopGraph:
         torch.cuda.current_stream().wait_stream(s)
         self.graph = torch.cuda.CUDAGraph()
         self.position_ids.zero_()
-        with torch.cuda.graph(self.graph):
+        with capture(self.graph):
             step()
         inference_params.seqlen_offset = off
 

@@ -216,7 +216,8 @@ class OmniMambaPath(nn.Module):
         sampling: one sampling.SamplingParams for every request or a list with one per request -- each request sampled with its own
         settings, repetition penalty and random stream in the shared steps (decode_ragged); temperature, top_k and
         top_p are not read then.  Its logit_bias, allowed_token_ids, banned_token_ids and min_new_tokens constrain what the request may
-        emit (yes/no, A-D, digits only; min_new_tokens needs eos_token_id), applied inside the same launch.
+        emit (yes/no, A-D, digits only; min_new_tokens needs eos_token_id), applied inside the same launch.  Its
+        presence_penalty and frequency_penalty act on the ids the request has sampled in this call.
         logprobs: an int N in [0, 64] for every request, or a list with one entry (N or None) per request: the call returns one more
         element, per request a sampling.TokenLogprobs aligned with its sampled ids -- the log-probability and rank of each sampled id and
         the N most likely tokens of each step, of the raw logits (decode_ragged).  None: off."""

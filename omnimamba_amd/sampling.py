@@ -57,7 +57,11 @@ class SamplingParams:
     Constraints on what the request may emit (off by default; the rule is omk_sample_rows', ABI 16, applied behind the repetition penalty):
     logit_bias -- a mapping or pairs id -> float added to the token's logit (finite, or -inf: a ban); allowed_token_ids -- only these ids
     may be drawn; banned_token_ids -- never drawn; min_new_tokens -- the call's eos_token_id is banned until the request has sampled that
-    many ids in the call.  logit_bias is kept as a tuple of (id, value) pairs, the id sets as tuples."""
+    many ids in the call.  logit_bias is kept as a tuple of (id, value) pairs, the id sets as tuples.
+
+    presence_penalty / frequency_penalty (0.0 = off, both finite): the OpenAI-style penalties over the ids the request has SAMPLED in the call
+    (not its prompt) -- a token sampled c > 0 times gets -((frequency_penalty * c) + presence_penalty) added to its logit, behind the
+    repetition penalty and together with the request's own edits (omk_penalty_edits, ABI 17)."""
     top_k: int = 1
     top_p: float = 0.0
     min_p: float = 0.0
@@ -69,8 +73,15 @@ class SamplingParams:
     allowed_token_ids: Optional[Sequence[int]] = None
     banned_token_ids: Optional[Sequence[int]] = None
     min_new_tokens: int = 0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
 
     def __post_init__(self):
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = float(getattr(self, name))
+            if not math.isfinite(v):
+                raise ValueError(f"SamplingParams: {name} must be finite, got {v}")
+            object.__setattr__(self, name, v)
         bias = self.logit_bias
         bias = tuple((int(i), float(v)) for i, v in (bias.items() if isinstance(bias, Mapping) else (bias or ())))
         for i, v in bias:
@@ -117,6 +128,19 @@ def pack_rows(params_list: Sequence[SamplingParams], device) -> dict:
     return {"top_k": k, "top_p": f[0], "temperature": f[1], "min_p": f[2], "penalty": f[3], "seeds": i[0], "steps": i[1]}
 
 
+def has_count_penalties(p: SamplingParams) -> bool:
+    """Whether the request has a presence or a frequency penalty that is not 0."""
+    return p.presence_penalty != 0.0 or p.frequency_penalty != 0.0
+
+
+def pack_count_penalties(params_list: Sequence[SamplingParams], device) -> dict:
+    """The penalty tensors of sample_rows / penalty_edits for a list of SamplingParams, row b from params_list[b]: a dict with frequency
+    and presence (float32 (n,)).  (pack_rows keeps its keys: callers splat it into sample_rows.)"""
+    n = len(params_list)
+    f = torch.tensor([[p.frequency_penalty, p.presence_penalty] for p in params_list], dtype=torch.float32).reshape(n, 2).t().contiguous().to(device)
+    return {"frequency": f[0], "presence": f[1]}
+
+
 def has_edits(p: SamplingParams) -> bool:
     """Whether the request's own settings edit its logits (min_new_tokens aside: that is the caller's extra ban)."""
     return bool(p.logit_bias) or p.allowed_token_ids is not None or bool(p.banned_token_ids)
@@ -160,14 +184,39 @@ def pack_edits(params_list: Sequence[SamplingParams], device, extra_bans: Option
 
 def apply_logit_edits(logits: torch.Tensor, edit_ids: Optional[torch.Tensor] = None, edit_vals: Optional[torch.Tensor] = None,
                       edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None, *, penalty: Optional[torch.Tensor] = None,
-                      history: Optional[torch.Tensor] = None, history_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      history: Optional[torch.Tensor] = None, history_lens: Optional[torch.Tensor] = None,
+                      frequency: Optional[torch.Tensor] = None, presence: Optional[torch.Tensor] = None,
+                      count_start: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The rule of omk_sample_rows (include/omk.h, ABI 14 and 16) in torch, on a copy: the repetition penalty over history[b, :history_lens[b]]
     (rounded to the dtype of the logits), then the edits -- a listed token gets round(float(p) + the value of its FIRST entry), an unlisted
     token of an allow-only row whose list holds a valid id gets -inf.  Lengths are clamped, ids outside [0, vocab) skipped, as the kernel
-    does.  What sample_rows draws from when the library declines the fused launch, and the statement the tests check that launch against."""
+    does.  What sample_rows draws from when the library declines the fused launch, and the statement the tests check that launch against.
+    frequency / presence (float32 (n,), either may be None = 0) with history, history_lens and count_start (int32 (n,), None = 0): the
+    presence and frequency penalties of ABI 17 -- a token that occurs c > 0 times in history[b, count_start[b]:history_lens[b]] gets
+    delta = -((frequency[b] * c) + presence[b]) (product and sum rounded separately; a non-finite penalty counts as 0): a listed token
+    round(float(p) + (value + delta)), an unlisted one round(float(p) + delta) unless the row is allow-only.  All three None: the function
+    as it was."""
     n, V = logits.shape
     dev = logits.device
     work = logits
+    counted = None
+    if frequency is not None or presence is not None:
+        if history is None or history_lens is None:
+            raise ValueError("apply_logit_edits: frequency / presence need history and history_lens")
+        cap = history.shape[1]
+        hl = history_lens.long().clamp(0, cap)
+        cs = torch.zeros_like(hl) if count_start is None else torch.minimum(count_start.long().clamp(min=0), hl)
+        pos = torch.arange(cap, device=dev)[None]
+        live = (pos >= cs[:, None]) & (pos < hl[:, None]) & (history >= 0) & (history < V)
+        # integer counts; dead entries go to a spare column
+        cnt = torch.zeros(n, V + 1, dtype=torch.int64, device=dev).scatter_add_(1, torch.where(live, history, torch.full_like(history, V)),
+                                                                                 torch.ones_like(history))[:, :V]
+        zero = torch.zeros(n, dtype=torch.float32, device=dev)
+        fr = zero if frequency is None else torch.where(torch.isfinite(frequency), frequency.float(), zero)
+        pr = zero if presence is None else torch.where(torch.isfinite(presence), presence.float(), zero)
+        prod = fr[:, None] * cnt.float()          # (two roundings: the product, then the sum)
+        delta = -(prod + pr[:, None])
+        counted = cnt > 0
     if penalty is not None and history is not None:
         # a mask of the history ids -- every write is True, so duplicates and the order of the writes do not matter; dead entries go to a
         # spare column
@@ -178,6 +227,8 @@ def apply_logit_edits(logits: torch.Tensor, edit_ids: Optional[torch.Tensor] = N
         lf = logits.float()
         work = torch.where(mask, torch.where(lf < 0, lf * pen, lf / pen).to(logits.dtype), logits)
     if edit_ids is None or edit_ids.shape[1] == 0:
+        if counted is not None:
+            return torch.where(counted, (work.float() + delta).to(logits.dtype), work)
         return work.clone() if work is logits else work
     cap = edit_ids.shape[1]
     pos = torch.arange(cap, device=dev)[None].expand(n, cap)
@@ -188,8 +239,12 @@ def apply_logit_edits(logits: torch.Tensor, edit_ids: Optional[torch.Tensor] = N
     listed = first < cap
     add = edit_vals.float().gather(1, first.clamp(max=cap - 1))
     allow = (edit_mode == 1 if edit_mode is not None else torch.zeros(n, dtype=torch.bool, device=dev)) & listed.any(1)
-    edited = (work.float() + add).to(logits.dtype)
-    return torch.where(listed, edited, torch.where(allow[:, None], torch.full_like(work, float("-inf")), work))
+    if counted is None:
+        edited = (work.float() + add).to(logits.dtype)
+        return torch.where(listed, edited, torch.where(allow[:, None], torch.full_like(work, float("-inf")), work))
+    edited = (work.float() + torch.where(counted, add + delta, add)).to(logits.dtype)     # (the inner sum first)
+    unlisted = torch.where(counted, (work.float() + delta).to(logits.dtype), work)
+    return torch.where(listed, edited, torch.where(allow[:, None], torch.full_like(work, float("-inf")), unlisted))
 
 
 def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev, what: str = "sample_rows"):
@@ -200,11 +255,69 @@ def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev, what: str = "
     return t.data_ptr()
 
 
+PENALTY_MAX_VOCAB = 65536     # tokens the id map of the sampler's edit launch holds (SAMPLE_PEN_MAX_V of sample.hip)
+
+
+def _rows2d(t, dtype, n, name, dev, what):
+    if t.dtype != dtype or t.device != dev or t.dim() != 2 or t.shape[0] != n or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: {name} must be {dtype} (batch, cap) with unit last stride on {dev}")
+
+
+def penalty_edits(history: torch.Tensor, history_lens: torch.Tensor, count_start: torch.Tensor, frequency: torch.Tensor, presence: torch.Tensor,
+                  vocab: int, *, active: Optional[torch.Tensor] = None, edit_ids: Optional[torch.Tensor] = None, edit_vals: Optional[torch.Tensor] = None,
+                  edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None, out: Optional[dict] = None,
+                  out_cap: Optional[int] = None) -> dict:
+    """ONE launch (omk_penalty_edits, ABI 17; include/omk.h has the rule): per row the edit list that makes omk_sample_rows apply the presence
+    and frequency penalties over history[b, count_start[b]:history_lens[b]] -- the row's user entries (edit_ids / edit_vals / edit_lens /
+    edit_mode, optional, the layouts of sample_rows) with the delta of a counted id added to its value, then (id, delta) for every other
+    distinct counted token in the order of first occurrence.  Returns a dict edit_ids (int64 (n, cap)), edit_vals (float32), edit_lens,
+    edit_mode (int32 (n,)) to splat into sample_rows.  out: such a dict of caller-owned buffers (they must not be the user list); otherwise
+    they are allocated out_cap wide (default: user width + history width, at least 1; what does not fit is dropped; the lengths and modes
+    are zero-filled, two small fill launches, the ids and values are not initialised behind a row's length).  No host read:
+    capturable, every tensor may be rewritten between replays."""
+    lib = get_lib()
+    what = "penalty_edits"
+    n, dev = history.shape[0], history.device
+    _rows2d(history, torch.int64, n, "history", dev, what)
+    p = K.PenaltyEdits(history=history.data_ptr(), history_stride=history.stride(0), history_cap=history.shape[1],
+                       history_lens=_ptr(history_lens, torch.int32, n, "history_lens", dev, what), count_start=_ptr(count_start, torch.int32, n, "count_start", dev, what),
+                       frequency=_ptr(frequency, torch.float32, n, "frequency", dev, what), presence=_ptr(presence, torch.float32, n, "presence", dev, what),
+                       active=_ptr(active, torch.int32, n, "active", dev, what), batch=n, vocab=int(vocab))
+    width = 0
+    if edit_ids is not None:
+        _rows2d(edit_ids, torch.int64, n, "edit_ids", dev, what)
+        if edit_vals is not None and (edit_vals.dtype != torch.float32 or edit_vals.device != dev or edit_vals.shape != edit_ids.shape or edit_vals.stride() != edit_ids.stride()):
+            raise ValueError("penalty_edits: edit_vals must be float32 with the shape and strides of edit_ids on the device of history")
+        width = edit_ids.shape[1]
+        p.edit_ids, p.edit_stride, p.edit_cap = edit_ids.data_ptr(), edit_ids.stride(0), width
+        p.edit_vals = None if edit_vals is None else edit_vals.data_ptr()
+        p.edit_lens, p.edit_mode = _ptr(edit_lens, torch.int32, n, "edit_lens", dev, what), _ptr(edit_mode, torch.int32, n, "edit_mode", dev, what)
+    if out is None:
+        cap = max(1, width + history.shape[1]) if out_cap is None else int(out_cap)
+        # (entries behind a row's length are never read: the two wide buffers are left as allocated)
+        out = {"edit_ids": torch.empty(n, cap, dtype=torch.int64, device=dev), "edit_vals": torch.empty(n, cap, dtype=torch.float32, device=dev),
+               "edit_lens": torch.zeros(n, dtype=torch.int32, device=dev), "edit_mode": torch.zeros(n, dtype=torch.int32, device=dev)}
+    oi, ov = out["edit_ids"], out["edit_vals"]
+    _rows2d(oi, torch.int64, n, "out edit_ids", dev, what)
+    if ov.dtype != torch.float32 or ov.device != dev or ov.shape != oi.shape or ov.stride() != oi.stride():
+        raise ValueError("penalty_edits: out edit_vals must be float32 with the shape and strides of out edit_ids")
+    if edit_ids is not None and (oi.data_ptr() == edit_ids.data_ptr() or (edit_vals is not None and ov.data_ptr() == edit_vals.data_ptr())):
+        raise ValueError("penalty_edits: the output buffers must not be the user list")
+    p.out_ids, p.out_vals, p.out_stride, p.out_cap = oi.data_ptr(), ov.data_ptr(), oi.stride(0), oi.shape[1]
+    p.out_lens, p.out_mode = _ptr(out["edit_lens"], torch.int32, n, "out edit_lens", dev, what), _ptr(out["edit_mode"], torch.int32, n, "out edit_mode", dev, what)
+    if n > 0 and (p.out_ids is None or p.history is None):      # (an empty tensor has no data pointer: a zero-width history or output)
+        raise ValueError("penalty_edits: history and the output buffers must be at least one entry wide")
+    K.run(lib, "omk_penalty_edits", p, history)
+    return out
+
+
 def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: Optional[torch.Tensor], temperature: Optional[torch.Tensor],
                 min_p: Optional[torch.Tensor], seeds: Optional[torch.Tensor], steps: Optional[torch.Tensor], penalty: Optional[torch.Tensor] = None,
                 history: Optional[torch.Tensor] = None, history_lens: Optional[torch.Tensor] = None, active: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None, edit_ids: Optional[torch.Tensor] = None, edit_vals: Optional[torch.Tensor] = None,
-                edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None) -> torch.Tensor:
+                edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None, frequency: Optional[torch.Tensor] = None,
+                presence: Optional[torch.Tensor] = None, count_start: Optional[torch.Tensor] = None, count_max: Optional[int] = None,
+                merged: Optional[dict] = None) -> torch.Tensor:
     """(batch, vocab) -> (batch,) int64 ids in ONE launch, row b sampled with its own settings: top_k (int32), top_p, temperature, min_p
     (float32), seeds and steps (int64; the seed's 64 bits) -- device tensors of (batch,).  Row b draws what
     sample_device(logits[b:b+1], ..., seed=seeds[b], offset=steps[b]) draws: its id does not depend on its place in the batch.
@@ -213,7 +326,22 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
     rows with 0 write nothing.  edit_ids (int64 (batch, cap), unit last stride) with edit_vals (float32, the same shape and strides) and
     edit_lens (int32), optionally edit_mode (int32): per-row logit edits behind the penalty, fused (pack_edits makes them, apply_logit_edits
     states the rule).  No host read: capturable, the tensors may be rewritten between replays.  A vocabulary too large for the kernel's id
-    map, or more than MAX_EDITS entries per row: the penalty and the edits are applied to a copy with torch and the plain launch draws."""
+    map, or more than MAX_EDITS entries per row: the penalty and the edits are applied to a copy with torch and the plain launch draws.
+    frequency / presence (float32, either may be None = 0) with history, history_lens and count_start (int32, None = 0): the presence and
+    frequency penalties over history[b, count_start[b]:history_lens[b]] (apply_logit_edits states the rule).  count_max: the host-known upper
+    bound of the rows' counted lengths (default: the width of history).  It is taken on trust -- the launch cannot check it: if a row
+    counts more distinct tokens than count_max, the merged list is cut at edit width + count_max entries and the tokens that do not fit
+    get NO penalty.  With a vocabulary of at most PENALTY_MAX_VOCAB tokens and
+    edit width + count_max <= MAX_EDITS: TWO kernels of the library and no host read (with `merged` nothing else; without it the buffers
+    are allocated and their lengths zero-filled first) -- penalty_edits builds the rows' merged lists (into `merged`, a dict
+    of caller-owned static buffers as penalty_edits returns it, at least edit width + count_max and at most MAX_EDITS wide; allocated when
+    None), then the edit launch draws.  Otherwise a copy is edited with apply_logit_edits and the plain launch draws.  Both None: the
+    function as it was."""
+    if frequency is not None or presence is not None:
+        return _rows_count_penalties(logits, dict(top_k=top_k, top_p=top_p, temperature=temperature, min_p=min_p, seeds=seeds, steps=steps, active=active, out=out),
+                                     dict(penalty=penalty, history=history, history_lens=history_lens),
+                                     dict(edit_ids=edit_ids, edit_vals=edit_vals, edit_lens=edit_lens, edit_mode=edit_mode),
+                                     frequency, presence, count_start, count_max, merged)
     p, out = _rows_call(logits, top_k=top_k, top_p=top_p, temperature=temperature, min_p=min_p, seeds=seeds, steps=steps, penalty=penalty, history=history,
                    history_lens=history_lens, active=active, out=out, edit_ids=edit_ids, edit_vals=edit_vals, edit_lens=edit_lens, edit_mode=edit_mode)
     lib = get_lib()
@@ -225,6 +353,34 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
     p.edit_cap = 0
     K.run(lib, "omk_sample_rows", p, logits)
     return out
+
+
+def _rows_count_penalties(logits, base, rep, user, frequency, presence, count_start, count_max, merged):
+    """sample_rows with a presence / frequency penalty: penalty_edits + the edit launch, or the plain launch on an edited copy."""
+    n, dev = logits.shape[0], logits.device
+    history, history_lens = rep["history"], rep["history_lens"]
+    if history is None or history_lens is None:
+        raise ValueError("sample_rows: frequency / presence need history and history_lens")
+    zero = None
+    if frequency is None or presence is None or count_start is None:
+        zero = torch.zeros(n, dtype=torch.float32, device=dev)
+    frequency = zero if frequency is None else frequency
+    presence = zero if presence is None else presence
+    count_start = zero.int() if count_start is None else count_start
+    count_max = history.shape[1] if count_max is None else int(count_max)
+    if count_max < 0:
+        raise ValueError(f"sample_rows: count_max must be >= 0, got {count_max}")
+    width = 0 if user["edit_ids"] is None else user["edit_ids"].shape[1]
+    need = width + count_max
+    if merged is not None and not need <= merged["edit_ids"].shape[1]:
+        raise ValueError(f"sample_rows: the merged buffers hold {merged['edit_ids'].shape[1]} entries a row, edit width + count_max is {need}")
+    cap = max(1, need) if merged is None else merged["edit_ids"].shape[1]
+    if n > 0 and history.shape[1] > 0 and logits.shape[1] <= PENALTY_MAX_VOCAB and need <= MAX_EDITS and cap <= MAX_EDITS:
+        ed = penalty_edits(history, history_lens, count_start, frequency, presence, logits.shape[1], active=base["active"],
+                           **(user if width else {}), out=merged, out_cap=cap)
+        return sample_rows(logits, **base, **rep, **ed)
+    work = apply_logit_edits(logits, **user, **rep, frequency=frequency, presence=presence, count_start=count_start)
+    return sample_rows(work, **base)
 
 
 def sample_rows_form(logits: torch.Tensor, **kw) -> int:

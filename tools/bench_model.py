@@ -236,7 +236,7 @@ def bench_decode_mmu_batch(args, dev):
         with _AdmissionClock() as clk:
             model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
         burst = clk.first_token_s[:min(args.max_batch, len(qs))]
-        samp = _sampling_variants(args, model, feats, qs, lens, n_tok, opts) if args.sampling in ("mixed", "constrained") else {}
+        samp = _sampling_variants(args, model, feats, qs, lens, n_tok, opts) if args.sampling in ("mixed", "constrained", "penalties") else {}
         if args.logprobs is not None:
             samp.update(_logprobs_variant(args, model, feats, qs, lens, n_tok, opts, rag))
         got = [r.shape[1] for r in rag]
@@ -264,7 +264,9 @@ def _sampling_variants(args, model, feats, qs, lens, n_tok, opts):
     alternate, --reps times each (every time is printed); ragged_tokens_per_s of the same line is the greedy run.
     --sampling constrained: (3) against (4) the same mixed requests, every second one with a 4-id allowed set and a logit_bias on 16 ids
     (the edit launch of the row-wise sampler in every draw of the call; the set is the first four of the biased ids, and the merge rule
-    of sampling.pack_edits drops the biases outside it: lists of four entries); the ids differ, the number of tokens does not (no EOS)."""
+    of sampling.pack_edits drops the biases outside it: lists of four entries); the ids differ, the number of tokens does not (no EOS).
+    --sampling penalties: (3) against (5) the same mixed requests, every one with presence_penalty 0.5 and frequency_penalty 0.3 (every
+    draw of the call: omk_penalty_edits + the edit launch while a request has sampled at most 512 ids, a torch-edited copy past that)."""
     from omnimamba_amd.sampling import SamplingParams as SP
     kinds = [SP(), SP(top_k=20, top_p=0.9), SP(top_k=0, top_p=0.9), SP(top_k=20, repetition_penalty=1.3), SP(top_k=0, min_p=0.05)]
     from dataclasses import replace
@@ -276,6 +278,9 @@ def _sampling_variants(args, model, feats, qs, lens, n_tok, opts):
         cons = [replace(p, allowed_token_ids=[(997 * (i + 1) + 131 * j) % V for j in range(4)],
                         logit_bias={(997 * (i + 1) + 131 * j) % V: 0.25 * j - 2.0 for j in range(16)}) if i % 2 else p for i, p in enumerate(mixed)]
         runs = {"mixed_row_wise": dict(sampling=mixed), "constrained_row_wise": dict(sampling=cons)}
+    if args.sampling == "penalties":
+        pens = [replace(p, presence_penalty=0.5, frequency_penalty=0.3) for p in mixed]
+        runs = {"mixed_row_wise": dict(sampling=mixed), "penalties_row_wise": dict(sampling=pens)}
     times = {k: [] for k in runs}
     for k, kw in runs.items():       # warm-up: the setting tensors of every bucket, the history buffer
         model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts, **kw)
@@ -519,9 +524,10 @@ def main():
     ap.add_argument("--turn2-ids", type=int, default=24, help="mmu_followup: ids of the second question (with the pending id: up to mamba2.EXTEND_SCAN_MAX_T "
                                                                   "positions take the extend kernel, more the chunked scan)")
     ap.add_argument("--extend-batch", type=int, default=1, help="mmu_followup: also time mmu_continue with this many turns per grouped extend (1 = off)")
-    ap.add_argument("--sampling", choices=["greedy", "mixed", "constrained"], default="greedy",
+    ap.add_argument("--sampling", choices=["greedy", "mixed", "constrained", "penalties"], default="greedy",
                     help="decode_mmu_batch: mixed = also time uniform top_k 20 (old path) and per-request settings (row-wise launch); "
-                         "constrained = the mixed settings against the same with an allowed set and a logit_bias on every second request")
+                         "constrained = the mixed settings against the same with an allowed set and a logit_bias on every second request; "
+                         "penalties = the mixed settings against the same with a presence and a frequency penalty on every request")
     ap.add_argument("--logprobs", type=int, default=None, help="decode_mmu_batch: also time the greedy run with logprobs=N (token_logprobs behind every draw)")
     ap.add_argument("--reps", type=int, default=1, help="decode_mmu_batch: timed repetitions of the ragged run")
     ap.add_argument("--dtypes", default="f32,bf16", help="decode_mmu_batch: weight dtypes to run")
