@@ -632,6 +632,42 @@ typedef struct {
 } OmkPenaltyEdits;
 int omk_penalty_edits(const OmkPenaltyEdits* p, omk_stream stream);
 
+/* ---- guided decoding: a per-row token bitmask in the row-wise sampler (added under ABI 17: additive, no existing layout changed) -------
+ * New symbols and one new struct only: OmkSampleRows is what it was byte for byte, omk_sample_rows and omk_sample_rows_form keep their
+ * behaviour and their values 0 / 1 / 2, so every existing caller stays valid and the version number did not move.
+ * Row b carries mask_words 32-bit words at mask + b * mask_stride: bit (i & 31) of word (i >> 5) set = token i may be drawn (the format
+ * grammar engines emit per step).  With e_i what ABI 14 / 16 / 17 define for token i of row b (repetition penalty, then the edits, -inf
+ * for the unlisted tokens of an allow-only row), every branch sees, in every one of its passes and through the one loader:
+ *   m_i = e_i    when the row is unmasked (mask_on[b] == 0) or bit i of its mask is set
+ *   m_i = -inf   otherwise
+ * The mask is applied LAST: a masked-out token stays -inf even when an edit entry gives it a bias, and an allow-only row draws from the
+ * intersection of its list and its mask.  `logits` and `mask` are never written.  Bits at positions >= vocab are ignored.  Nothing in the
+ * arrays is trusted: a mask_on[b] other than 0 counts as 1.  Inactive rows (active[b] == 0) read neither their mask row nor mask_on[b].
+ * A row whose mask leaves no finite logit gives an unspecified id in [0, vocab) in bounded time (ABI 16's "a row left without a finite
+ * logit").  mask == NULL: the call IS omk_sample_rows(&p->rows) -- the same plan, the same kernels, and the form function returns what
+ * omk_sample_rows_form returns.  With a mask two more instantiations take the call:
+ *   OMK_SAMPLE_ROWS_MASK       no penalty history and no edit list: no id map; dynamic LDS holds the row's ceil(vocab / 32) words (at most
+ *                              8 192 B) next to the 44 792 B static
+ *   OMK_SAMPLE_ROWS_EDIT_MASK  the ABI 16 instantiation (id map, list in whole buckets, one word) with the words behind the list; edit_cap
+ *                              == 0 is legal here (a penalty history with a mask and no list).  At most 44 800 + 65 536 + 4 096 + 4 +
+ *                              8 192 = 122 628 B of the 163 840 B of a workgroup
+ * OMK_EINVAL: a negative mask_words or mask_stride, mask_words < ceil(vocab / 32), with more than one row mask_stride < mask_words, and
+ * whatever omk_sample_rows refuses.  OMK_EUNSUPPORTED: a mask with vocab > 65 536 (one bound for everything the sampler keeps in LDS:
+ * mask a copy instead), and what omk_sample_rows declines.  Capturable: nothing is read from the host, every array may be rewritten
+ * between replays.                                                                                                                     */
+typedef struct {
+  OmkSampleRows rows;        /* everything omk_sample_rows takes, with its meaning unchanged */
+  const void* mask;          /* optional device int32 (batch, mask_words): bit (i & 31) of word (i >> 5) set = token i may be drawn */
+  const void* mask_on;       /* optional device int32 (batch): 0 = the row ignores its mask; NULL = every row is masked */
+  int64_t mask_stride;       /* elements between the rows of mask */
+  int64_t mask_words;        /* width of mask, >= ceil(vocab / 32) */
+} OmkSampleRowsMasked;
+int omk_sample_rows_masked(const OmkSampleRowsMasked* p, omk_stream stream);
+/* Which launch omk_sample_rows_masked takes for *p: OMK_SAMPLE_ROWS_* (0 / 1 / 2 without a mask), or the negative omk_status. */
+#define OMK_SAMPLE_ROWS_MASK 3       /* bit array only: no id map */
+#define OMK_SAMPLE_ROWS_EDIT_MASK 4  /* id map (+ edit list) and the bit array */
+int omk_sample_rows_masked_form(const OmkSampleRowsMasked* p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,9 @@ SampleRows = _S("OmkSampleRows", [("logits", _t), ("out_ids", _t)]
                 + [("history_stride", _i64), ("history_cap", _i64)]
                 + [(n, C.c_void_p) for n in ("edit_ids", "edit_vals", "edit_lens", "edit_mode")] + [("edit_stride", _i64), ("edit_cap", _i64)])   # ABI 16: per-row logit edits
 SAMPLE_ROWS_PLAIN, SAMPLE_ROWS_PENALTY, SAMPLE_ROWS_EDIT = 0, 1, 2   # omk_sample_rows_form (ABI 16)
+# guided decoding (added under ABI 17: additive, no existing layout changed): OmkSampleRows and a per-row token bitmask (include/omk.h)
+SampleRowsMasked = _S("OmkSampleRowsMasked", [("rows", SampleRows), ("mask", C.c_void_p), ("mask_on", C.c_void_p), ("mask_stride", _i64), ("mask_words", _i64)])
+SAMPLE_ROWS_MASK, SAMPLE_ROWS_EDIT_MASK = 3, 4   # omk_sample_rows_masked_form
 # ABI 15: log-probabilities of the sampled tokens, the top_n tokens of every row, the sampled token's rank (include/omk.h)
 TokenLogprobs = _S("OmkTokenLogprobs", [(n, _t) for n in ("logits", "logprob", "rank", "top_ids", "top_logprobs")]
                    + [("ids", C.c_void_p), ("active", C.c_void_p), ("top_n", _i)])
@@ -112,7 +115,7 @@ PenaltyEdits = _S("OmkPenaltyEdits", [(n, C.c_void_p) for n in ("history", "hist
                   + [(n, C.c_void_p) for n in ("out_ids", "out_vals", "out_lens", "out_mode")] + [("out_stride", _i64), ("out_cap", _i64)]
                   + [("batch", _i64), ("vocab", _i64)])
 
-STRUCTS = {s.__name__: s for s in (Sample, SampleRows, TokenLogprobs, PenaltyEdits, CrossEntropy, OmkTensor, AddNormFwd, AddNormBwd, NormGatedFwd, NormGatedBwd, Conv1dFwd, Conv1dBwd,
+STRUCTS = {s.__name__: s for s in (Sample, SampleRows, SampleRowsMasked, TokenLogprobs, PenaltyEdits, CrossEntropy, OmkTensor, AddNormFwd, AddNormBwd, NormGatedFwd, NormGatedBwd, Conv1dFwd, Conv1dBwd,
                                    Conv1dUpdate, StateUpdate, StateExtend, SelScanFwd, SelScanBwd, NormLinear, LoraAdd, LoraUpBwd, SsdFwd, SsdBwd)}
 
 # every symbol include/omk.h declares
@@ -125,6 +128,7 @@ SYMBOLS = [
     "omk_selective_scan_fwd", "omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_selective_scan_bwd_workspace_bytes", "omk_selective_scan_bwd",
     "omk_ssd_scan_fwd_workspace_bytes", "omk_ssd_scan_fwd_window_states_bytes", "omk_ssd_scan_fwd", "omk_ssd_scan_bwd_workspace_bytes", "omk_ssd_scan_bwd",
     "omk_cross_entropy", "omk_lora_up_bwd_parts", "omk_sample", "omk_sample_rows", "omk_sample_rows_form", "omk_token_logprobs", "omk_penalty_edits",
+    "omk_sample_rows_masked", "omk_sample_rows_masked_form",
 ]
 
 
@@ -141,7 +145,7 @@ def bind(lib: C.CDLL) -> C.CDLL:
         if s.endswith("_workspace_bytes") or s.endswith("_window_states_bytes"):
             fn.restype = C.c_size_t
             fn.argtypes = [C.c_void_p]
-        elif s in ("omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_norm_linear_form", "omk_sample_rows_form"):
+        elif s in ("omk_selective_scan_fwd_form", "omk_selective_scan_bwd_form", "omk_norm_linear_form", "omk_sample_rows_form", "omk_sample_rows_masked_form"):
             fn.restype = C.c_int
             fn.argtypes = [C.c_void_p]
         elif s == "omk_lora_up_bwd_parts":

@@ -32,8 +32,8 @@ import torch
 from . import generation as G
 from .generation import InferenceParams, PrefillGraph, MAX_PREFILL_GRAPHS, _prefill_graph_ok, sample
 from . import sampling as _sampling
-from .sampling import (MAX_EDITS, SamplingParams, TokenLogprobs, apply_logit_edits, edit_list, has_count_penalties, has_edits, pack_count_penalties,
-                       pack_edits, pack_rows, sample_rows)
+from .sampling import (MAX_EDITS, SamplingParams, TokenLogprobs, apply_logit_edits, apply_token_mask, edit_list, has_count_penalties, has_edits,
+                       mask_words, pack_count_penalties, pack_edits, pack_rows, sample_rows)
 
 # A draw with presence / frequency penalties takes the fused path (sampling.penalty_edits + the edit launch) while the rows' user width plus
 # the ids their requests have sampled so far fit this many entries; past it the draw edits a copy.  Equal to MAX_EDITS; a name of its own
@@ -138,6 +138,27 @@ class _Bucket:
                             "edit_lens": torch.zeros(self.nb, dtype=torch.int32, device=dev), "edit_mode": torch.zeros(self.nb, dtype=torch.int32, device=dev)}
         return st
 
+    def row_masks(self, words):
+        """Static token-mask buffers of guided decoding next to the row settings, made on first use: the device (nb, words) int32 mask the
+        masked launch reads, the (nb,) mask_on flags, and ONE pinned host staging buffer the guides' masks are gathered in."""
+        st, dev = self.row_settings(), self.input_ids.device
+        if "token_mask" not in st or st["token_mask"].shape[1] != words:
+            st["token_mask"] = torch.full((self.nb, words), -1, dtype=torch.int32, device=dev)
+            st["mask_on"] = torch.zeros(self.nb, dtype=torch.int32, device=dev)
+            st["mask_stage"] = torch.full((self.nb, words), -1, dtype=torch.int32, pin_memory=dev.type == "cuda")
+        return st
+
+
+def _guide_mask(g, i, words):
+    """What guide `g` of request i allows in its next draw: None, or its int32 (words,) CPU mask -- anything else is a ValueError."""
+    m = g.mask()
+    if m is None:
+        return None
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.int32 or m.dim() != 1 or m.shape[0] != words or m.device.type != "cpu":
+        what = f"{m.dtype} {tuple(m.shape)} on {m.device}" if isinstance(m, torch.Tensor) else type(m).__name__
+        raise ValueError(f"decode_ragged: the guide of request {i} must return None or an int32 CPU tensor of ({words},) (sampling.pack_token_mask), got {what}")
+    return m
+
 
 class _RowSampler:
     """decode_ragged(sampling=...): every draw of the call through ONE row-wise launch (sampling.sample_rows), request i with
@@ -149,10 +170,15 @@ class _RowSampler:
     EOS ban of min_new_tokens, which is in a row's list while its request has sampled fewer ids than that.  With a presence or frequency
     penalty somewhere the pool owns the history buffer as well and every draw carries the rows' frequency / presence / count_start, the
     length of a request's input_ids: only the ids it sampled in this call count.  Which path such a draw takes is decided on the host from
-    `count` and `width` (_draw): penalty_edits + the edit launch while they fit PENALTY_FUSED_MAX entries, a torch-edited copy past it."""
+    `count` and `width` (_draw): penalty_edits + the edit launch while they fit PENALTY_FUSED_MAX entries, a torch-edited copy past it.
+    With a guide somewhere (`guides`: per request None or an object with mask() / advance()) every draw with a guided row carries the rows'
+    token masks (sampling.sample_rows(token_mask=, mask_on=)): mask() is called once in front of each draw of a guided request, and the
+    caller hands every sampled id back through advance()."""
 
-    def __init__(self, c, params, requests, lens, dev, eos=None):
+    def __init__(self, c, params, requests, lens, dev, eos=None, guides=None):
         self.c, self.params, self.dev, self.eos = c, params, dev, eos
+        self.guides = guides if guides is not None and any(g is not None for g in guides) else None
+        self.prev_on = None                        # the mask_on flags the bucket of the last step holds
         self.edit = any(has_edits(p) or p.min_new_tokens > 0 for p in params)
         self.width = 1 + max(len(edit_list(p)[0]) for p in params) if self.edit else 0
         self.count = [0] * len(params)             # ids sampled so far, per request
@@ -192,6 +218,7 @@ class _RowSampler:
         buffers of the merged lists --, past it the plain launch on a copy edited with torch."""
         if not self.cpen:
             return sample_rows(logits, **kw)
+        guide = {k: kw[k] for k in ("token_mask", "mask_on") if k in kw}
         cmax = max(self.count[i] for i in reqs)
         need = self.width + cmax
         if need <= PENALTY_FUSED_MAX:
@@ -200,11 +227,15 @@ class _RowSampler:
         work = apply_logit_edits(logits, kw.get("edit_ids"), kw.get("edit_vals"), kw.get("edit_lens"), kw.get("edit_mode"), penalty=kw.get("penalty"),
                                  history=kw["history"], history_lens=kw["history_lens"], frequency=kw["frequency"], presence=kw["presence"],
                                  count_start=kw["count_start"])
+        if guide:
+            work = apply_token_mask(work, **guide)
         return sample_rows(work, **plain)
 
     def admit(self, reqs, slots, logits):
         """The first id of the requests `reqs` (just admitted into `slots`) from their prefill / extend logits (len(reqs), vocab)."""
+        gk = self._admit_masks(reqs, logits.shape[1])      # (first: a guide's ValueError comes before anything of the draw is launched)
         pk = self._settings(reqs)
+        pk.update(gk)
         if self.edit:
             pk.update(self._edits(reqs))
         if self.hist_on:
@@ -224,10 +255,48 @@ class _RowSampler:
         self.prev = None
         return toks
 
+    def advance(self, i, tok):
+        """Request i sampled `tok` (a host int)."""
+        if self.guides is not None and self.guides[i] is not None:
+            self.guides[i].advance(tok)
+
+    def _admit_masks(self, reqs, vocab):
+        """The mask keywords of an admission draw: none when no request of `reqs` is masked in it."""
+        if self.guides is None:
+            return {}
+        w = mask_words(vocab)
+        ms = [None if self.guides[i] is None else _guide_mask(self.guides[i], i, w) for i in reqs]
+        if all(m is None for m in ms):
+            return {}
+        tm = torch.stack([torch.full((w,), -1, dtype=torch.int32) if m is None else m for m in ms])
+        on = torch.tensor([int(m is not None) for m in ms], dtype=torch.int32)
+        return {"token_mask": tm.to(self.dev), "mask_on": on.to(self.dev)}
+
+    def _step_masks(self, bk, live, vocab, rows_changed):
+        """The mask keywords of a step of a guided call: the live guided rows' masks go into the bucket's pinned staging rows and ONE
+        non-blocking copy moves them to the static device mask; mask_on is rewritten only when the rows changed or a guide switched between
+        None and a mask.  Reusing the staging buffer is safe because a call with guides reads the sampled ids on the host after every draw
+        (decode_ragged's toks.tolist(), which advance() is fed from): the copy of step n is complete before the host writes step n + 1's
+        rows."""
+        w, nl = mask_words(vocab), len(live)
+        ms = [None if self.guides[i] is None else _guide_mask(self.guides[i], i, w) for i, _, _ in live]
+        st = bk.row_masks(w)
+        on = tuple(int(m is not None) for m in ms)
+        for r, m in enumerate(ms):
+            if m is not None:
+                st["mask_stage"][r].copy_(m)
+        if any(on):
+            st["token_mask"][:nl].copy_(st["mask_stage"][:nl], non_blocking=True)
+        if rows_changed or (bk.nb, on) != self.prev_on:
+            st["mask_on"].copy_(torch.tensor(list(on) + [0] * (bk.nb - nl), dtype=torch.int32), non_blocking=True)
+            self.prev_on = (bk.nb, on)
+        return {"token_mask": st["token_mask"], "mask_on": st["mask_on"]}
+
     def step(self, bk, live, rows, logits):
         """One id for every live row of bucket `bk` from the step's logits (bk.nb, vocab); rows: the slots of the bucket's rows (device)."""
         st, nl = bk.row_settings(), len(live)
         key = (bk.nb, tuple(i for i, _, _ in live))
+        gk = {} if self.guides is None else self._step_masks(bk, live, logits.shape[1], key[:2] != (self.prev or ())[:2])
         if self.edit:
             st = bk.row_edits(self.width)
             key += (tuple(bool(b) for b in self._bans([i for i, _, _ in live])),)
@@ -249,6 +318,7 @@ class _RowSampler:
                                          non_blocking=True)
             self.prev = key
         kw = {k: st[k] for k in ("top_k", "top_p", "temperature", "min_p", "seeds", "steps", "active", "out")}
+        kw.update(gk)
         if self.edit:
             kw.update({k: st[k] for k in ("edit_ids", "edit_vals", "edit_lens", "edit_mode")})
         if self.hist_on:
@@ -449,7 +519,8 @@ def _save(c, slot, seqlen, pending_id, task):
 
 @torch.inference_mode()
 def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_token_id=None, top_k=1, top_p=0.0, temperature=1.0,
-                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None, logprobs=None):
+                  min_p=0.0, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None, logprobs=None,
+                  guides=None):
     """requests: list of (input_ids (1, Li), input_embeddings (1, Pi, d)); max_length: an int or one per request, with
     generation.decode's meaning.  Returns one LongTensor (1, Li + n_i) per request: what ``decode(input_ids_i, input_embeddings_i,
     model, max_length_i, ...)`` returns for that request alone -- prompt ids, sampled ids, EOS included, and the IndexError of a step
@@ -495,7 +566,18 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     most likely tokens (N = 0: shape (n_i, 0)).  All of the RAW logits the draw saw: no temperature, filter or repetition penalty (a greedy
     request has rank 1 everywhere).  Every draw is followed by one sampling.token_logprobs launch at the largest N among its rows; the
     results stay on the device (the model's) until the call returns, no host synchronisation is added, and with cg the launch reads the
-    bucket's static logits before the next replay.  The sampled ids and the states are those of the call without logprobs."""
+    bucket's static logits before the next replay.  The sampled ids and the states are those of the call without logprobs.
+
+    guides: None -- off.  A list with one entry per request: None, or a GUIDE -- any object with mask() -> None or an int32 (ceil(vocab /
+    32),) CPU tensor (bit (i & 31) of word (i >> 5) set = token i may be drawn; None = unconstrained for this draw), called once in front of
+    every draw of its request, and advance(token_id), called with every id the request samples, in order, EOS included
+    (sampling.ChoiceGuide is one; a grammar engine's matcher is another).  Needs `sampling` (the row-wise path).  Every draw of a guided
+    request -- prefill, extend, grouped or not, and the step -- carries its mask into the row-wise launch (omk_sample_rows_masked: the mask
+    is applied last, behind the penalties and the edits); per bucket a static device mask, the mask_on flags and one pinned staging
+    buffer are made on first use.  The call reads the sampled ids on the host after every draw (as with an eos_token_id).  A mask of the
+    wrong dtype, shape or device raises ValueError before anything of that draw is launched.  Requests without a guide draw the ids they
+    draw without guided neighbours (mask_on 0); logprobs stay those of the raw logits.  A call in which no request has a guide launches
+    what the call without `guides` launches."""
     n = len(requests)
     if logprobs is not None:
         want = [logprobs] * n if isinstance(logprobs, int) else list(logprobs)
@@ -530,6 +612,15 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             raise ValueError(f"decode_ragged: sampling is one SamplingParams or a list of {n}, one per request")
         if eos_token_id is None and any(p.min_new_tokens > 0 for p in sampling):
             raise ValueError("decode_ragged: min_new_tokens > 0 needs an eos_token_id to keep out of the first ids")
+    if guides is not None:
+        if sampling is None:
+            raise ValueError("decode_ragged: guides need sampling (one SamplingParams or a list): the masks are applied by the row-wise sampler launch")
+        guides = list(guides)
+        if len(guides) != n:
+            raise ValueError(f"decode_ragged: guides is None or a list of {n}, one entry (a guide or None) per request")
+        for g in guides:
+            if g is not None and not (callable(getattr(g, "mask", None)) and callable(getattr(g, "advance", None))):
+                raise ValueError("decode_ragged: a guide is None or an object with mask() and advance(token_id)")
     dev = requests[0][1].device
     if hasattr(model, "prepare_decode"):
         model.prepare_decode(task)
@@ -543,7 +634,7 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             c["buckets"][nb] = _Bucket(model, c["pool"], nb, c["max_seqlen"], task, cg, c["mempool"])
         return c["buckets"][nb]
 
-    rs = None if sampling is None else _RowSampler(c, sampling, requests, lens, dev, eos_token_id)
+    rs = None if sampling is None else _RowSampler(c, sampling, requests, lens, dev, eos_token_id, guides)
     # the first id(s) of the requests `reqs` admitted into `slots`, from their prefill / extend logits
     draw = lambda lg, reqs, slots: (sample(lg, top_k=top_k, top_p=top_p, min_p=min_p, temperature=temperature) if rs is None
                                     else rs.admit(reqs, slots, lg))
@@ -560,7 +651,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
     pieces = [[] for _ in range(n)]      # per request: the positions of its ids in cat(drawn), in sampling order
     queue, free = deque(range(n)), list(range(max_batch))
     live = []                            # rows of the step: [request, slot, offset]
-    check_eos = eos_token_id is not None or return_states
+    guided = rs is not None and rs.guides is not None
+    check_eos = eos_token_id is not None or return_states or guided     # (guides are fed the sampled ids: the host reads them every draw)
     states = [None] * n
 
     def retire(i, s, off, tok):
@@ -615,6 +707,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
                     off = emb.shape[1]
                 admitted = [(i, s, off, tok, int(tok[0]) if check_eos else None)]
             for i, s, off, tok, tok_h in admitted:
+                if guided:
+                    rs.advance(i, tok_h)
                 last[s:s + 1].copy_(tok)
                 drawn.append(tok)
                 pieces[i].append(n_drawn)
@@ -655,6 +749,8 @@ def decode_ragged(requests, model, max_length, *, max_batch=8, task="mmu", eos_t
             i, s, off = row
             row[2] = off = off + 1
             pieces[i].append(n_drawn + r)
+            if guided:
+                rs.advance(i, toks_h[r])
             if finished(i, toks_h[r] if check_eos else None, off):
                 retire(i, s, off, toks_h[r] if check_eos else None)
             else:

@@ -51,6 +51,7 @@ size_t omk_sizeof(const char* n) {
   OMK_SZ(OmkTensor); OMK_SZ(OmkAddNormFwd); OMK_SZ(OmkAddNormBwd); OMK_SZ(OmkNormGatedFwd); OMK_SZ(OmkNormGatedBwd);
   OMK_SZ(OmkConv1dFwd); OMK_SZ(OmkConv1dBwd); OMK_SZ(OmkConv1dUpdate); OMK_SZ(OmkStateUpdate); OMK_SZ(OmkStateExtend); OMK_SZ(OmkSelScanFwd);
   OMK_SZ(OmkSelScanBwd); OMK_SZ(OmkNormLinear); OMK_SZ(OmkLoraAdd); OMK_SZ(OmkLoraUpBwd); OMK_SZ(OmkSsdFwd); OMK_SZ(OmkSsdBwd); OMK_SZ(OmkCrossEntropy); OMK_SZ(OmkSample); OMK_SZ(OmkSampleRows); OMK_SZ(OmkTokenLogprobs); OMK_SZ(OmkPenaltyEdits);
+  OMK_SZ(OmkSampleRowsMasked);
 #undef OMK_SZ
   return 0;
 }

@@ -106,6 +106,12 @@ struct BatchCfg {
 
 // What the row loader consults besides the row itself: nothing, the id map of the history, or the id map and the row's edit list.
 constexpr int SM_NONE = 0, SM_PEN = 1, SM_EDIT = 2;
+// Guided decoding: the row's token bitmask (one bit per token, LDS) behind whatever else the loader consults -- SM_MASK: nothing else (no id
+// map: nothing to clear); SM_EDIT_MASK: SM_EDIT as it is with the bit array behind the list.  The id-map byte has no free bit left (below),
+// so the mask has its own storage and its own instantiations.
+constexpr int SM_MASK = 3, SM_EDIT_MASK = 4;
+constexpr bool sm_edits(int mode) { return mode == SM_EDIT || mode == SM_EDIT_MASK; }
+constexpr bool sm_masked(int mode) { return mode == SM_MASK || mode == SM_EDIT_MASK; }
 // A byte of the id map.  Bit 0: the token is in the row's history.  SM_EDIT only -- bit 1: the token is in the row's edit list; bits 2 - 7:
 // the BUCKET (entry index / EDIT_BUCKET) of the first entry that names it.  The loader reads the EDIT_BUCKET entries of that bucket and
 // takes the first match: the first entry wins, in 8 LDS reads whatever the length of the list.  (Scanning the whole list instead, as first
@@ -147,9 +153,11 @@ __device__ __forceinline__ void map_mark_edit(unsigned char* map, int id, int j)
 // (LDS, one byte per token) marks the ids of the row's history; the loader penalises a marked logit and rounds it to T as the in-place torch
 // version does, so every pass sees the same penalised row.  SM_EDIT: behind the penalty the loader adds the value of the first entry of `ed`
 // that names the token (one more rounding to T), and an allow-only row reads -inf for every token its list does not name.  ALIASED picks the
-// layout of the large LDS buffers, Cfg is RowCfg or BatchCfg.
+// layout of the large LDS buffers, Cfg is RowCfg or BatchCfg.  SM_MASK / SM_EDIT_MASK: `bits` (LDS, ceil(V / 32) words) is the row's token
+// mask, all ones for a row that ignores its mask; LAST in the loader, a token whose bit is clear reads -inf whatever the edits gave it.
 template <class T, int MODE, bool ALIASED, class Cfg>
-__device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg a, const unsigned char* pmap, const RowEdits ed = {}) {
+__device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg a, const unsigned char* pmap, const RowEdits ed = {},
+                                           const uint32_t* bits = nullptr) {
   // hist / hm8 / hc8: the counters of the radix passes, eight copies of every counter, picked by the lane: the keys of a row share their top
   // byte(s), and 64 lanes adding to ONE LDS address are 64 serial atomics (copy c of digit d lives at 8 d + c: the copies of a digit sit in
   // different banks).  sc64 / sc32 / scf: the buffers of the block scans.  Two layouts:
@@ -184,7 +192,7 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg
   auto ld = [&](int i) -> float {
     float v = to_f32(rowp[i]);
     if constexpr (MODE == SM_PEN) { if (pmap[i]) v = to_f32(from_f32<T>(v < 0.f ? v * a.pen : v / a.pen)); }
-    if constexpr (MODE == SM_EDIT) {
+    if constexpr (sm_edits(MODE)) {
       const unsigned m = pmap[i];
       if (m & MAP_HIST) v = to_f32(from_f32<T>(v < 0.f ? v * a.pen : v / a.pen));
       if (m & MAP_EDIT) {
@@ -197,6 +205,8 @@ __device__ __forceinline__ void sample_row(const T* rowp, const int V, const Cfg
         v = to_f32(from_f32<T>(v + ed.vals[jf]));
       } else if (ed.allow) v = -INFINITY;
     }
+    // (in the strided passes 32 consecutive lanes read one word: a broadcast, not a bank conflict)
+    if constexpr (sm_masked(MODE)) { if (!((bits[i >> 5] >> (i & 31)) & 1u)) v = -INFINITY; }
     return v;
   };
   // one pass over the row, thread-strided (coalesced), four requests in flight per lane
@@ -499,12 +509,17 @@ struct SampleRowsArgs {
   int64_t hs; int hcap;
   const int64_t* edit_ids; const float* edit_vals; const int* edit_lens; const int* edit_mode;   // SM_EDIT only
   int64_t es; int ecap;
+  const uint32_t* mask; const int* mask_on; int64_t ms;   // SM_MASK / SM_EDIT_MASK only (behind everything the older instantiations read)
 };
+
+// words of a row's token mask in LDS
+__host__ __device__ constexpr int mask_lds_words(int V) { return (V + 31) / 32; }
 
 // omk_sample_rows: row b's settings come from the device arrays.  Nothing in them is trusted: see the clamps (include/omk.h).
 // MODE >= SM_PEN: dynamic LDS holds the id map of the row's history, (V rounded up to 4) bytes.  SM_EDIT: the map (V rounded up to 16 bytes),
 // behind it the row's edit list in whole buckets (edit_lds_entries(ecap) ids as int32, as many values) and one word that says whether any of
-// its ids was valid.
+// its ids was valid.  SM_MASK: dynamic LDS holds the row's mask_lds_words(V) mask words and nothing else.  SM_EDIT_MASK: the SM_EDIT layout
+// with the mask words behind the any-valid word; a.ecap == 0 is legal (a history with a mask and no list: no bucket, allow false).
 template <class T, int MODE>
 __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
   const int row = blockIdx.x, tid = threadIdx.x;
@@ -516,7 +531,10 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
   int k = a.top_k[row];
   float tp = a.top_p[row], t = a.temperature[row], mp = a.min_p[row];
   unsigned long long sd = a.seeds[row], st = (unsigned long long)a.steps[row];
+  int mon = 1;   // SM_MASK / SM_EDIT_MASK: the row's mask_on entry joins the same round (no array: every row is masked)
+  if constexpr (sm_masked(MODE)) mon = *(a.mask_on ? a.mask_on + row : a.top_k + row);
   OMK_OPAQUE_S(k); OMK_OPAQUE_S(tp); OMK_OPAQUE_S(t); OMK_OPAQUE_S(mp); OMK_OPAQUE_S(sd); OMK_OPAQUE_S(st); OMK_OPAQUE_S(act);
+  if constexpr (sm_masked(MODE)) OMK_OPAQUE_S(mon);
   if (a.active && act == 0) return;   // (uniform over the workgroup, in front of every barrier)
   RowCfg c;
   c.top_k = uniform_i(k < 0 ? 0 : (k > SAMPLE_KMAX ? SAMPLE_KMAX : k));   // (the clamp is a VALU v_med3: back into a scalar register, as omk_sample's argument is)
@@ -526,6 +544,20 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
   c.seed = sd; c.step = st; c.c0 = 0u; c.pen = 1.f; c.out = a.out + row;
   const unsigned char* pmap = nullptr;
   RowEdits ed = {};
+  const uint32_t* bits = nullptr;
+  // The row's mask words into LDS, all ones for a row that ignores its mask (mask_on[row] == 0): the loader stays uniform, no "is this row
+  // masked" test in the passes.  An unmasked row does not read its mask row.  (The caller's barrier publishes the words.)
+  auto stage_mask = [&](uint32_t* w) {
+    const bool masked = !a.mask_on || mon != 0;
+    const uint32_t* mrow = a.mask + (int64_t)row * a.ms;
+    for (int i = tid; i < mask_lds_words(a.V); i += SNT) w[i] = masked ? mrow[i] : 0xffffffffu;
+  };
+  if constexpr (MODE == SM_MASK) {
+    OMK_DYN_SMEM(dyn);
+    stage_mask((uint32_t*)dyn);
+    block_sync();
+    bits = (const uint32_t*)dyn;
+  }
   if constexpr (MODE == SM_PEN) {
     OMK_DYN_SMEM(dyn);
     unsigned char* const map = (unsigned char*)dyn;
@@ -541,7 +573,7 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
     block_sync();
     pmap = map;
   }
-  if constexpr (MODE == SM_EDIT) {
+  if constexpr (sm_edits(MODE)) {
     OMK_DYN_SMEM(dyn);
     unsigned char* const map = (unsigned char*)dyn;
     const int ecap8 = edit_lds_entries(a.ecap);
@@ -551,7 +583,9 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
     // (the penalty and the history are optional here: a launch with edits alone marks no history)
     const float pen = a.penalty ? a.penalty[row] : 1.f;
     int hl = a.history ? a.history_lens[row] : 0;
-    int el = a.edit_lens[row];
+    int el;
+    if constexpr (MODE == SM_EDIT_MASK) el = a.ecap > 0 ? a.edit_lens[row] : 0;   // (a mask and a history without a list)
+    else el = a.edit_lens[row];
     const int em = a.edit_mode ? a.edit_mode[row] : 0;
     hl = hl < 0 ? 0 : (hl > a.hcap ? a.hcap : hl);
     el = el < 0 ? 0 : (el > a.ecap ? a.ecap : el);
@@ -559,6 +593,7 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
     else c.pen = pen;
     for (int i = tid; i < (a.V + 3) / 4; i += SNT) ((uint32_t*)map)[i] = 0u;
     if (tid == 0) *any_valid = 0u;
+    if constexpr (MODE == SM_EDIT_MASK) { stage_mask(any_valid + 1); bits = any_valid + 1; }
     block_sync();
     const int64_t* hrow = a.history + (int64_t)row * a.hs;
     for (int j = tid; j < hl; j += SNT) { const int64_t id = hrow[j]; if (id >= 0 && id < (int64_t)a.V) map[id] = (unsigned char)MAP_HIST; }
@@ -577,7 +612,7 @@ __global__ __launch_bounds__(SNT) void sample_rows_kernel(SampleRowsArgs a) {
     ed.allow = em == 1 && uniform_i((int)*any_valid) != 0;   // allow-only without a valid id: unconstrained
     pmap = map;
   }
-  sample_row<T, MODE, true>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, pmap, ed);
+  sample_row<T, MODE, true>((const T*)a.logits + (int64_t)row * a.ls, a.V, c, pmap, ed, bits);
 }
 
 }  // namespace omk
@@ -707,4 +742,57 @@ extern "C" int omk_sample_rows(const OmkSampleRows* p, omk_stream stream) {
     });
   }
   return finish_launch("sample_rows");
+}
+
+// ---- guided decoding: omk_sample_rows_masked (added under ABI 17; include/omk.h has the rule) ------------------------------------------
+// THE selector of omk_sample_rows_masked: sample_rows_plan decides everything about p->rows as it always did; without a mask that is the
+// whole answer.  With one, the checks of the mask, and which of the two masked instantiations takes the call: OMK_SAMPLE_ROWS_MASK when the
+// base plan needs no id map, OMK_SAMPLE_ROWS_EDIT_MASK otherwise (the base plan's history and list, either may be absent).
+static int sample_rows_masked_plan(const OmkSampleRowsMasked* p, SampleRowsPlan& pl) {
+  OMK_REQUIRE(p, "sample_rows_masked: no arguments");
+  const int base = sample_rows_plan(&p->rows, pl);
+  if (base < 0 || !p->mask) return base;
+  const int form = base == OMK_SAMPLE_ROWS_PLAIN ? OMK_SAMPLE_ROWS_MASK : OMK_SAMPLE_ROWS_EDIT_MASK;
+  OMK_REQUIRE(p->mask_words >= 0 && p->mask_stride >= 0, "sample_rows_masked: mask_words and mask_stride must not be negative");
+  if (pl.empty) return form;
+  SampleRowsArgs& a = pl.a;
+  OMK_REQUIRE(p->mask_words >= (int64_t)mask_lds_words(a.V), "sample_rows_masked: mask_words %lld holds fewer than the %d tokens of the vocabulary",
+              (long long)p->mask_words, a.V);
+  OMK_REQUIRE(p->rows.logits.shape[0] <= 1 || p->mask_stride >= p->mask_words, "sample_rows_masked: mask_stride %lld is below mask_words %lld",
+              (long long)p->mask_stride, (long long)p->mask_words);
+  if (a.V > SAMPLE_PEN_MAX_V)
+    return fail(OMK_EUNSUPPORTED, "sample_rows_masked: the sampler keeps the mask of at most %lld tokens in LDS, the vocabulary has %d", (long long)SAMPLE_PEN_MAX_V, a.V);
+  a.mask = (const uint32_t*)p->mask; a.mask_on = (const int*)p->mask_on; a.ms = p->mask_stride;
+  const size_t mask_bytes = (size_t)mask_lds_words(a.V) * 4;
+  if (form == OMK_SAMPLE_ROWS_MASK) { pl.smem = mask_bytes; return form; }
+  // (a penalty launch becomes the edit layout with an empty list: a.ecap is 0 there, and the plan left the edit arrays NULL)
+  pl.smem = edit_map_bytes(a.V) + (size_t)edit_lds_entries(a.ecap) * 8 + 4 + mask_bytes;
+  return form;
+}
+
+extern "C" int omk_sample_rows_masked_form(const OmkSampleRowsMasked* p) {
+  SampleRowsPlan pl;
+  return sample_rows_masked_plan(p, pl);
+}
+
+extern "C" int omk_sample_rows_masked(const OmkSampleRowsMasked* p, omk_stream stream) {
+  if (p && !p->mask) return omk_sample_rows(&p->rows, stream);   // no mask: the call IS omk_sample_rows
+  SampleRowsPlan pl;
+  const int form = sample_rows_masked_plan(p, pl);
+  if (form < 0) return form;
+  if (pl.empty) return OMK_OK;
+  const SampleRowsArgs& a = pl.a;
+  const size_t smem = pl.smem;
+  dim3 grid((unsigned)p->rows.logits.shape[0]), block(SNT);
+  const int dt = p->rows.logits.dtype;
+  if (form == OMK_SAMPLE_ROWS_MASK) {
+    // (at most 8 192 B of dynamic LDS: inside what every kernel may ask for without a grant)
+    OMK_DISPATCH_DTYPE(dt, T, OMK_LAUNCH((sample_rows_kernel<T, SM_MASK>), grid, block, smem, stream, a));
+  } else {
+    OMK_DISPATCH_DTYPE(dt, T, {
+      if (grant_map_lds<T, SM_EDIT_MASK>(smem)) return fail(OMK_ELAUNCH, "sample_rows_masked: cannot reserve %zu bytes of LDS for the id map, the edit list and the mask", smem);
+      OMK_LAUNCH((sample_rows_kernel<T, SM_EDIT_MASK>), grid, block, smem, stream, a);
+    });
+  }
+  return finish_launch("sample_rows_masked");
 }

@@ -206,7 +206,7 @@ class OmniMambaPath(nn.Module):
     @torch.no_grad()
     def mmu_generate_batch(self, images_feat_list, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1,
                            top_p=0.0, max_batch=8, cg=True, return_states=False, prefill_batch=1, prefill_bucket=0, sampling=None,
-                           logprobs=None):
+                           logprobs=None, guides=None):
         """Many MMU requests at once (continuous batching, omnimamba_amd/batch_decode.py): request i is images_feat_list[i] (1, n_img,
         fused_vision_dim) with the question input_ids_list[i] (1, T_i), its prompt built as in mmu_generate.  max_length: an int or one
         per request.  Returns one id tensor per request, each equal to what mmu_generate returns for that request alone.
@@ -220,18 +220,22 @@ class OmniMambaPath(nn.Module):
         presence_penalty and frequency_penalty act on the ids the request has sampled in this call.
         logprobs: an int N in [0, 64] for every request, or a list with one entry (N or None) per request: the call returns one more
         element, per request a sampling.TokenLogprobs aligned with its sampled ids -- the log-probability and rank of each sampled id and
-        the N most likely tokens of each step, of the raw logits (decode_ragged).  None: off."""
+        the N most likely tokens of each step, of the raw logits (decode_ragged).  None: off.
+        guides: None, or a list with one entry per request -- None, or a guide (sampling.ChoiceGuide, or any object with mask() and
+        advance(token_id)): the packed token bitmask it returns in front of every draw of its request is applied inside the row-wise
+        launch (structured output; needs `sampling`; decode_ragged)."""
         from .batch_decode import decode_ragged
         if len(images_feat_list) != len(input_ids_list):
             raise ValueError("mmu_generate_batch: one images_feat per question")
         reqs = [self._mmu_prompt(f, q) for f, q in zip(images_feat_list, input_ids_list)]
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
                              top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=return_states,
-                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, sampling=sampling, logprobs=logprobs)
+                             prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, sampling=sampling, logprobs=logprobs,
+                             **({} if guides is None else {"guides": guides}))
 
     @torch.no_grad()
     def mmu_continue(self, states, input_ids_list, max_length=2048, eos_token_id=None, temperature=1.0, top_k=1, top_p=0.0, max_batch=8,
-                     cg=True, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None, logprobs=None):
+                     cg=True, prefill_batch=1, prefill_bucket=0, extend_batch=1, sampling=None, logprobs=None, guides=None):
         """The follow-up turn of each conversation: states[i] is the DecodeState its previous turn returned (mmu_generate_batch or
         mmu_continue with states), input_ids_list[i] (1, T_i) the new turn's ids, already templated by the caller.  The conversation is
         not re-prefilled: the state takes the previous turn's last sampled id and the new ids (text only, embedded with
@@ -242,7 +246,8 @@ class OmniMambaPath(nn.Module):
         are extended by one right-padded pass (decode_ragged; off by default, DESIGN.md 4.6 says what was measured).
         sampling: as in mmu_generate_batch; a conversation continues its random stream with step0 = the ids its earlier turns sampled.
         Constraints (allowed or banned ids, logit_bias, min_new_tokens) hold from the turn's first id on; min_new_tokens counts this turn's ids.
-        logprobs: as in mmu_generate_batch; the call then returns (ids, states, logprobs), the records covering this turn's sampled ids."""
+        logprobs: as in mmu_generate_batch; the call then returns (ids, states, logprobs), the records covering this turn's sampled ids.
+        guides: as in mmu_generate_batch; a guide constrains this turn's ids from the first one on."""
         from .batch_decode import decode_ragged
         if len(states) != len(input_ids_list):
             raise ValueError("mmu_continue: one state per conversation")
@@ -250,7 +255,7 @@ class OmniMambaPath(nn.Module):
         return decode_ragged(reqs, self.llm_backbone.mamba, max_length, max_batch=max_batch, task="mmu", eos_token_id=eos_token_id,
                              top_k=top_k, top_p=top_p, temperature=temperature, cg=cg, return_states=True,
                              prefill_batch=prefill_batch, prefill_bucket=prefill_bucket, extend_batch=extend_batch, sampling=sampling,
-                             logprobs=logprobs)
+                             logprobs=logprobs, **({} if guides is None else {"guides": guides}))
 
     # ---- T2I generation (omnimamba.py:311-337 minus the VQ decoder network)
     @torch.no_grad()

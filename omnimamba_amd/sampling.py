@@ -247,6 +247,91 @@ def apply_logit_edits(logits: torch.Tensor, edit_ids: Optional[torch.Tensor] = N
     return torch.where(listed, edited, torch.where(allow[:, None], torch.full_like(work, float("-inf")), unlisted))
 
 
+# ---- guided decoding: per-row token bitmasks (omk_sample_rows_masked; include/omk.h has the rule) ----------------------------------------
+
+def mask_words(vocab: int) -> int:
+    """Words of a packed token mask over `vocab` tokens."""
+    return (int(vocab) + 31) // 32
+
+
+def pack_token_mask(allowed_ids, vocab: int) -> torch.Tensor:
+    """The packed mask that allows exactly `allowed_ids`: a CPU int32 tensor of (ceil(vocab / 32),), bit (i & 31) of word (i >> 5) set =
+    token i may be drawn (the bit order of include/omk.h, and of the masks grammar engines emit).  An id outside [0, vocab): ValueError."""
+    import numpy as np
+    vocab = int(vocab)
+    ids = np.asarray(list(allowed_ids), dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= vocab):
+        raise ValueError(f"pack_token_mask: ids must be in [0, {vocab})")
+    bits = np.zeros(mask_words(vocab) * 32, dtype=np.uint8)
+    bits[ids] = 1
+    return torch.from_numpy(np.packbits(bits, bitorder="little").view("<u4").astype(np.int32))
+
+
+def apply_token_mask(logits: torch.Tensor, token_mask: torch.Tensor, mask_on: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mask rule of omk_sample_rows_masked in torch, on a copy: token i of row b keeps its logit when bit (i & 31) of
+    token_mask[b, i >> 5] is set or mask_on[b] == 0 (mask_on None: every row is masked), and reads -inf otherwise.  token_mask: int32
+    (batch, W >= ceil(vocab / 32)); bits at positions >= vocab are ignored.  What sample_rows draws from when the library declines the
+    masked launch, and the statement the tests check that launch against."""
+    n, V = logits.shape
+    if token_mask.dtype != torch.int32 or token_mask.dim() != 2 or token_mask.shape[0] != n or token_mask.shape[1] < mask_words(V) or token_mask.device != logits.device:
+        raise ValueError(f"apply_token_mask: token_mask must be int32 ({n}, >= {mask_words(V)}) on {logits.device}")
+    idx = torch.arange(V, device=logits.device)
+    keep = ((token_mask[:, idx >> 5] >> (idx & 31)[None]) & 1).bool()
+    if mask_on is not None:
+        keep = keep | (mask_on == 0)[:, None]
+    return torch.where(keep, logits, torch.full_like(logits, float("-inf")))
+
+
+class ChoiceGuide:
+    """A guide that makes its request emit exactly one of `choices` (token-id sequences) and then `eos_token_id`: a walk down the trie of
+    the choices.  Where a complete choice is also a proper prefix of another, EOS and the continuation are both allowed.
+
+    The guide protocol (decode_ragged(guides=...); no base class is required) is two methods:
+      mask() -> Optional[Tensor]    an int32 (ceil(vocab / 32),) CPU tensor in the bit order of pack_token_mask, or None = unconstrained for
+                                    this draw; called once in front of every draw of the guide's request
+      advance(token_id: int)        called with every id the request samples, in order, EOS included
+    Empty `choices`, an empty sequence, an id outside [0, vocab), or EOS inside a choice: ValueError."""
+
+    def __init__(self, choices, vocab: int, eos_token_id: int):
+        self.vocab, self.eos = int(vocab), int(eos_token_id)
+        if not 0 <= self.eos < self.vocab:
+            raise ValueError(f"ChoiceGuide: eos_token_id must be in [0, {self.vocab})")
+        choices = [[int(t) for t in c] for c in choices]
+        if not choices:
+            raise ValueError("ChoiceGuide: choices is a non-empty list of token-id sequences")
+        self.root = {"next": {}, "end": False, "mask": None}
+        for c in choices:
+            if not c:
+                raise ValueError("ChoiceGuide: a choice is a non-empty token-id sequence")
+            node = self.root
+            for t in c:
+                if not 0 <= t < self.vocab or t == self.eos:
+                    raise ValueError(f"ChoiceGuide: a choice holds ids in [0, {self.vocab}) other than eos_token_id, got {t}")
+                node = node["next"].setdefault(t, {"next": {}, "end": False, "mask": None})
+            node["end"] = True
+        self.node, self.done = self.root, False
+        self._eos_mask = pack_token_mask([self.eos], self.vocab)
+
+    def mask(self) -> torch.Tensor:
+        if self.done:
+            return self._eos_mask       # (a request that goes on behind its EOS can only repeat it)
+        node = self.node
+        if node["mask"] is None:
+            node["mask"] = pack_token_mask(list(node["next"]) + ([self.eos] if node["end"] else []), self.vocab)
+        return node["mask"]
+
+    def advance(self, token_id: int) -> None:
+        token_id = int(token_id)
+        if self.done:
+            return
+        if token_id == self.eos and self.node["end"]:
+            self.done = True
+        elif token_id in self.node["next"]:
+            self.node = self.node["next"][token_id]
+        else:
+            raise ValueError(f"ChoiceGuide: id {token_id} is not one the guide allowed at this point")
+
+
 def _ptr(t: Optional[torch.Tensor], dtype, n: int, name: str, dev, what: str = "sample_rows"):
     if t is None:
         return None
@@ -317,7 +402,7 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
                 out: Optional[torch.Tensor] = None, edit_ids: Optional[torch.Tensor] = None, edit_vals: Optional[torch.Tensor] = None,
                 edit_lens: Optional[torch.Tensor] = None, edit_mode: Optional[torch.Tensor] = None, frequency: Optional[torch.Tensor] = None,
                 presence: Optional[torch.Tensor] = None, count_start: Optional[torch.Tensor] = None, count_max: Optional[int] = None,
-                merged: Optional[dict] = None) -> torch.Tensor:
+                merged: Optional[dict] = None, token_mask: Optional[torch.Tensor] = None, mask_on: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(batch, vocab) -> (batch,) int64 ids in ONE launch, row b sampled with its own settings: top_k (int32), top_p, temperature, min_p
     (float32), seeds and steps (int64; the seed's 64 bits) -- device tensors of (batch,).  Row b draws what
     sample_device(logits[b:b+1], ..., seed=seeds[b], offset=steps[b]) draws: its id does not depend on its place in the batch.
@@ -336,18 +421,32 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
     are allocated and their lengths zero-filled first) -- penalty_edits builds the rows' merged lists (into `merged`, a dict
     of caller-owned static buffers as penalty_edits returns it, at least edit width + count_max and at most MAX_EDITS wide; allocated when
     None), then the edit launch draws.  Otherwise a copy is edited with apply_logit_edits and the plain launch draws.  Both None: the
-    function as it was."""
+    function as it was.
+    token_mask (int32 (batch, W >= ceil(vocab / 32)), unit last stride, on the device of logits; pack_token_mask gives a row) with mask_on
+    (int32 (batch,), optional: 0 = the row ignores its mask): guided decoding -- a token whose bit is clear is never drawn, applied LAST,
+    behind the penalties and the edits, inside the launch (omk_sample_rows_masked; apply_token_mask states the rule).  With frequency /
+    presence: penalty_edits first, then the masked launch.  Where the library declines (a vocabulary above PENALTY_MAX_VOCAB, more than
+    MAX_EDITS entries), the mask is applied to the copy as well and the plain launch draws.  token_mask None: the function as it was,
+    through omk_sample_rows."""
+    if token_mask is None and mask_on is not None:
+        raise ValueError("sample_rows: mask_on needs token_mask")
     if frequency is not None or presence is not None:
         return _rows_count_penalties(logits, dict(top_k=top_k, top_p=top_p, temperature=temperature, min_p=min_p, seeds=seeds, steps=steps, active=active, out=out),
                                      dict(penalty=penalty, history=history, history_lens=history_lens),
                                      dict(edit_ids=edit_ids, edit_vals=edit_vals, edit_lens=edit_lens, edit_mode=edit_mode),
-                                     frequency, presence, count_start, count_max, merged)
+                                     frequency, presence, count_start, count_max, merged,
+                                     {} if token_mask is None else dict(token_mask=token_mask, mask_on=mask_on))
     p, out = _rows_call(logits, top_k=top_k, top_p=top_p, temperature=temperature, min_p=min_p, seeds=seeds, steps=steps, penalty=penalty, history=history,
                    history_lens=history_lens, active=active, out=out, edit_ids=edit_ids, edit_vals=edit_vals, edit_lens=edit_lens, edit_mode=edit_mode)
     lib = get_lib()
-    if K.try_run(lib, "omk_sample_rows", p, logits):
+    if token_mask is not None:
+        if K.try_run(lib, "omk_sample_rows_masked", _masked_call(p, logits, token_mask, mask_on), logits):
+            return out
+    elif K.try_run(lib, "omk_sample_rows", p, logits):
         return out
     work = apply_logit_edits(logits, edit_ids, edit_vals, edit_lens, edit_mode, penalty=penalty, history=history, history_lens=history_lens)
+    if token_mask is not None:
+        work = apply_token_mask(work, token_mask, mask_on)
     p.logits = K.T(work)
     p.penalty = p.history = p.history_lens = p.edit_ids = p.edit_vals = p.edit_lens = p.edit_mode = None
     p.edit_cap = 0
@@ -355,7 +454,7 @@ def sample_rows(logits: torch.Tensor, *, top_k: Optional[torch.Tensor], top_p: O
     return out
 
 
-def _rows_count_penalties(logits, base, rep, user, frequency, presence, count_start, count_max, merged):
+def _rows_count_penalties(logits, base, rep, user, frequency, presence, count_start, count_max, merged, guide):
     """sample_rows with a presence / frequency penalty: penalty_edits + the edit launch, or the plain launch on an edited copy."""
     n, dev = logits.shape[0], logits.device
     history, history_lens = rep["history"], rep["history_lens"]
@@ -378,16 +477,32 @@ def _rows_count_penalties(logits, base, rep, user, frequency, presence, count_st
     if n > 0 and history.shape[1] > 0 and logits.shape[1] <= PENALTY_MAX_VOCAB and need <= MAX_EDITS and cap <= MAX_EDITS:
         ed = penalty_edits(history, history_lens, count_start, frequency, presence, logits.shape[1], active=base["active"],
                            **(user if width else {}), out=merged, out_cap=cap)
-        return sample_rows(logits, **base, **rep, **ed)
+        return sample_rows(logits, **base, **rep, **ed, **guide)
     work = apply_logit_edits(logits, **user, **rep, frequency=frequency, presence=presence, count_start=count_start)
+    if guide:
+        work = apply_token_mask(work, **guide)
     return sample_rows(work, **base)
 
 
 def sample_rows_form(logits: torch.Tensor, **kw) -> int:
-    """Which launch sample_rows(logits, **kw) takes -- K.SAMPLE_ROWS_PLAIN / _PENALTY / _EDIT, or the negative omk_status the library refuses
-    the call with.  The launch's own decision (omk_sample_rows_form); nothing is launched."""
+    """Which launch sample_rows(logits, **kw) takes -- K.SAMPLE_ROWS_PLAIN / _PENALTY / _EDIT, with a token_mask K.SAMPLE_ROWS_MASK /
+    _EDIT_MASK, or the negative omk_status the library refuses the call with.  The launch's own decision (omk_sample_rows_form /
+    omk_sample_rows_masked_form); nothing is launched."""
     import ctypes
-    return int(get_lib().omk_sample_rows_form(ctypes.byref(_rows_call(logits, **kw)[0])))
+    token_mask, mask_on = kw.pop("token_mask", None), kw.pop("mask_on", None)
+    p = _rows_call(logits, **kw)[0]
+    if token_mask is None:
+        return int(get_lib().omk_sample_rows_form(ctypes.byref(p)))
+    return int(get_lib().omk_sample_rows_masked_form(ctypes.byref(_masked_call(p, logits, token_mask, mask_on))))
+
+
+def _masked_call(p, logits, token_mask, mask_on):
+    """(the OmkSampleRowsMasked around the OmkSampleRows `p` of a sample_rows call; the width of the mask is the library's to check)"""
+    n, dev = logits.shape[0], logits.device
+    if token_mask.dtype != torch.int32 or token_mask.device != dev or token_mask.dim() != 2 or token_mask.shape[0] != n or (token_mask.shape[1] > 1 and token_mask.stride(1) != 1):
+        raise ValueError("sample_rows: token_mask must be int32 (batch, words) with unit last stride on the device of logits")
+    return K.SampleRowsMasked(rows=p, mask=token_mask.data_ptr(), mask_on=_ptr(mask_on, torch.int32, n, "mask_on", dev),
+                              mask_stride=token_mask.stride(0), mask_words=token_mask.shape[1])
 
 
 def _rows_call(logits, *, top_k, top_p, temperature, min_p, seeds, steps, penalty=None, history=None, history_lens=None, active=None, out=None,

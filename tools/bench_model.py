@@ -236,7 +236,7 @@ def bench_decode_mmu_batch(args, dev):
         with _AdmissionClock() as clk:
             model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts)
         burst = clk.first_token_s[:min(args.max_batch, len(qs))]
-        samp = _sampling_variants(args, model, feats, qs, lens, n_tok, opts) if args.sampling in ("mixed", "constrained", "penalties") else {}
+        samp = _sampling_variants(args, model, feats, qs, lens, n_tok, opts) if args.sampling in ("mixed", "constrained", "penalties", "guided") else {}
         if args.logprobs is not None:
             samp.update(_logprobs_variant(args, model, feats, qs, lens, n_tok, opts, rag))
         got = [r.shape[1] for r in rag]
@@ -266,7 +266,12 @@ def _sampling_variants(args, model, feats, qs, lens, n_tok, opts):
     (the edit launch of the row-wise sampler in every draw of the call; the set is the first four of the biased ids, and the merge rule
     of sampling.pack_edits drops the biases outside it: lists of four entries); the ids differ, the number of tokens does not (no EOS).
     --sampling penalties: (3) against (5) the same mixed requests, every one with presence_penalty 0.5 and frequency_penalty 0.3 (every
-    draw of the call: omk_penalty_edits + the edit launch while a request has sampled at most 512 ids, a torch-edited copy past that)."""
+    draw of the call: omk_penalty_edits + the edit launch while a request has sampled at most 512 ids, a torch-edited copy past that).
+    --sampling guided: (3) against the same mixed requests with guides (decode_ragged(guides=...): the masked row-wise launch in every draw
+    and a host read of the ids per step) -- (6) every request a sampling.ChoiceGuide over four fixed sequences (no EOS is given to the
+    call: a request that has finished its choice goes on emitting the guide's EOS id, so the number of tokens is the same) and (7) every
+    request a dense guide that allows a pseudo-random half of the vocabulary, one of 16 precomputed masks in turn.  Fresh guides for every
+    run; the time spent inside the guides' mask() and advance() is reported per run (guide_s_all)."""
     from omnimamba_amd.sampling import SamplingParams as SP
     kinds = [SP(), SP(top_k=20, top_p=0.9), SP(top_k=0, top_p=0.9), SP(top_k=20, repetition_penalty=1.3), SP(top_k=0, min_p=0.05)]
     from dataclasses import replace
@@ -281,20 +286,68 @@ def _sampling_variants(args, model, feats, qs, lens, n_tok, opts):
     if args.sampling == "penalties":
         pens = [replace(p, presence_penalty=0.5, frequency_penalty=0.3) for p in mixed]
         runs = {"mixed_row_wise": dict(sampling=mixed), "penalties_row_wise": dict(sampling=pens)}
+    guide_s = {}
+    if args.sampling == "guided":
+        from omnimamba_amd.sampling import ChoiceGuide, pack_token_mask
+        V = model.cfg.vocab_size
+        spent = [0.0]
+
+        class Timed:      # (the guide's own Python time, apart from the launches)
+            def __init__(self, g):
+                self.g = g
+
+            def mask(self):
+                t0 = time.perf_counter()
+                m = self.g.mask()
+                spent[0] += time.perf_counter() - t0
+                return m
+
+            def advance(self, tok):
+                t0 = time.perf_counter()
+                self.g.advance(tok)
+                spent[0] += time.perf_counter() - t0
+
+        gen = torch.Generator().manual_seed(7)
+        dense_masks = [pack_token_mask(torch.randperm(V, generator=gen)[: V // 2].tolist(), V) for _ in range(16)]
+
+        class Dense:
+            def __init__(self, i):
+                self.n = i
+
+            def mask(self):
+                return dense_masks[self.n % 16]
+
+            def advance(self, tok):
+                self.n += 1
+
+        choices = lambda i: [[(101 * (i + 1) + 17 * c + 3 * j) % (V - 1) for j in range(2 + 3 * c)] for c in range(4)]
+        runs = {"mixed_row_wise": dict(sampling=mixed),
+                "guided_choice_row_wise": lambda: dict(sampling=mixed, guides=[Timed(ChoiceGuide(choices(i), V, V - 1)) for i in range(len(qs))]),
+                "guided_dense_row_wise": lambda: dict(sampling=mixed, guides=[Timed(Dense(i)) for i in range(len(qs))])}
+        guide_s = {k: [] for k in runs if k != "mixed_row_wise"}
     times = {k: [] for k in runs}
+    kwargs = lambda kw: kw() if callable(kw) else kw      # (guides are stateful: a fresh set for every run)
     for k, kw in runs.items():       # warm-up: the setting tensors of every bucket, the history buffer
-        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts, **kw)
+        model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts, **kwargs(kw))
     torch.cuda.synchronize()
     for _ in range(max(args.reps, 1)):
         for k, kw in runs.items():
+            kw = kwargs(kw)
+            if k in guide_s:
+                spent[0] = 0.0
             t0 = time.perf_counter()
             model.mmu_generate_batch(feats, qs, max_length=lens, max_batch=args.max_batch, cg=True, **opts, **kw)
             torch.cuda.synchronize()
             times[k].append(time.perf_counter() - t0)
+            if k in guide_s:
+                guide_s[k].append(spent[0])
     out = {}
     for k, ts in times.items():
         out[k + "_tokens_per_s"] = round(n_tok / sorted(ts)[len(ts) // 2], 1)
         out[k + "_tokens_per_s_all"] = [round(n_tok / t, 1) for t in ts]
+        out[k + "_s_all"] = [round(t, 4) for t in ts]
+    for k, ts in guide_s.items():
+        out[k + "_guide_s_all"] = [round(t, 4) for t in ts]
     return {"sampling": out}
 
 
@@ -524,10 +577,11 @@ def main():
     ap.add_argument("--turn2-ids", type=int, default=24, help="mmu_followup: ids of the second question (with the pending id: up to mamba2.EXTEND_SCAN_MAX_T "
                                                                   "positions take the extend kernel, more the chunked scan)")
     ap.add_argument("--extend-batch", type=int, default=1, help="mmu_followup: also time mmu_continue with this many turns per grouped extend (1 = off)")
-    ap.add_argument("--sampling", choices=["greedy", "mixed", "constrained", "penalties"], default="greedy",
+    ap.add_argument("--sampling", choices=["greedy", "mixed", "constrained", "penalties", "guided"], default="greedy",
                     help="decode_mmu_batch: mixed = also time uniform top_k 20 (old path) and per-request settings (row-wise launch); "
                          "constrained = the mixed settings against the same with an allowed set and a logit_bias on every second request; "
-                         "penalties = the mixed settings against the same with a presence and a frequency penalty on every request")
+                         "penalties = the mixed settings against the same with a presence and a frequency penalty on every request; "
+                         "guided = the mixed settings against the same with a ChoiceGuide / a dense pseudo-random guide on every request")
     ap.add_argument("--logprobs", type=int, default=None, help="decode_mmu_batch: also time the greedy run with logprobs=N (token_logprobs behind every draw)")
     ap.add_argument("--reps", type=int, default=1, help="decode_mmu_batch: timed repetitions of the ragged run")
     ap.add_argument("--dtypes", default="f32,bf16", help="decode_mmu_batch: weight dtypes to run")
